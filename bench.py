@@ -2,6 +2,7 @@
 """bench.py — headline benchmark of the MI355X dwarf backend.
 
   python bench.py [--gpus N] [--steps K] [--warmup W] [--dwarf scan|sort|groupby|join|all] [--no-cpu] [--no-pjoin] [--no-sweep]
+                  [--dump-outputs DIR]
 
 One "step" = one pass of the hot path over one batch of synthetic input already resident in HBM.
 N = 1 (default): the configuration BASELINE.json's metric is quoted on — TwoPassScan (stream compaction
@@ -26,7 +27,9 @@ fault aborts the process) costs `pjoin` an `error` entry, never the contract lin
 Rehearsal knobs (not for reported numbers): DBENCH_BACKEND=gloo lets several ranks share one GPU (the C++ RCCL leg
 is skipped), DBENCH_PJOIN_LOG2 shrinks the partitioned join.
 
-Prints ONE JSON line on rank 0 with the contract fields plus "roofline" and "cpu_baseline".
+Prints ONE JSON line on rank 0 with the contract fields plus "roofline" and "cpu_baseline"; `ms_per_step` is the wall
+clock of one of the --steps timed scan steps.  --dump-outputs DIR also writes what the last timed step computed (the
+compacted column and its count, dump_outputs) as .npy files; the inputs are seeded, so two builds can be compared.
 The oracle (oracle/) is used ONLY for the cpu_baseline leg and a one-off result check; the timed path is
 libdbhip.so through the C ABI.
 """
@@ -123,7 +126,7 @@ def _peak_source():
 # ---------------------------------------------------------------------------------------------------
 # single-GPU dwarfs
 # ---------------------------------------------------------------------------------------------------
-def bench_scan(steps, warmup, log2n=28, filt=5, cold=False):
+def bench_scan(steps, warmup, log2n=28, filt=5, cold=False, keep_output=False):
     import torch
     from dwarf_bench_amd import ops
     n = 1 << log2n
@@ -138,6 +141,8 @@ def bench_scan(steps, warmup, log2n=28, filt=5, cold=False):
         run()
     torch.cuda.synchronize()
     wall_ms = (time.perf_counter() - t0) * 1e3 / steps
+    # what the last timed step handed its caller, read back before any other launch reuses the plan's buffers
+    output = plan.result().cpu() if keep_output else None
     ev = _event_times_us(run, steps)
     matches = plan.result().numel()
     alg_bytes = 4 * n + 4 * matches  # 4*N*(1+s)
@@ -162,8 +167,27 @@ def bench_scan(steps, warmup, log2n=28, filt=5, cold=False):
         "kernel_us_min": min(ev), "mrows_per_s": n / (wall_ms * 1e3), "matches": matches,
         "algorithmic_bytes": alg_bytes, "achieved_gbs": alg_bytes / avg_us / 1e3,
         "workload": f"TwoPassScan copy_if(x<{filt}) 2^{log2n} int32 uniform[1,10000]",
-        "src": src, "plan": plan,
+        "src": src, "plan": plan, "output": output,
     }
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(directory: str, scan: dict) -> None:
+    """--dump-outputs: the headline scan's result as of its last timed step, as a caller of ops.CopyIfLt receives it —
+    the selected values in input order (int32 in [1, 10000], exact in float32) and their count (float64) — so that two
+    builds run with the same arguments (same seeded input) can be compared output for output."""
+    import numpy as np
+    arrays = {"scan_out": scan["output"].numpy().astype(np.float32),
+              "scan_out_size": np.array([scan["output"].numel()], dtype=np.float64)}
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_LIMIT_BYTES:  # 4e-4 of 2^28 rows pass x < 5: about 0.4 MB
+        raise SystemExit(f"bench.py: --dump-outputs would write {total} bytes, more than {DUMP_LIMIT_BYTES}")
+    out = Path(directory)
+    out.mkdir(parents=True, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(out / f"{name}.npy", a)
 
 
 def bench_sort(steps, warmup, log2n=24, bits=8, reference_range=False):
@@ -846,11 +870,15 @@ def main():
     ap.add_argument("--no-pjoin", action="store_true", help="skip the single-GPU 2^30 x 2^30 join (profiling passes)")
     ap.add_argument("--no-sweep", action="store_true", help="skip the scan selectivity sweep and the reference-range "
                     "sorts (counter passes: keeps every scan / sort dispatch at the BASELINE configuration)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the headline scan's output of its last timed step "
+                    "to DIR/<name>.npy (rank 0)")
     ap.add_argument("--pjoin-child", action="store_true", help=argparse.SUPPRESS)  # see run_pjoin_children
     args = ap.parse_args()
 
     if args.gpus < 1:
         raise SystemExit("bench.py: --gpus must be >= 1")
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("bench.py: --steps must be >= 1 and --warmup >= 0")
     if args.gpus > 1 and not ("WORLD_SIZE" in os.environ and "RANK" in os.environ) and not args.pjoin_child:
         # no launcher around this process: be the launcher (before torch is imported or the GPU touched)
         raise SystemExit(self_launch(args.gpus, sys.argv[1:]))
@@ -902,8 +930,11 @@ def main():
 
     # ---- headline: scan 2^28 (BASELINE.json's metric configuration)
     barrier()
-    scan = bench_scan(args.steps, args.warmup, cold=(n_gpus == 1 and not args.no_sweep))
+    scan = bench_scan(args.steps, args.warmup, cold=(n_gpus == 1 and not args.no_sweep),
+                      keep_output=bool(args.dump_outputs) and rank == 0)
     barrier()
+    if scan["output"] is not None:
+        dump_outputs(args.dump_outputs, scan)
     ms = scan["ms_per_step"]
     if dist is not None:
         t = torch.tensor([ms], dtype=torch.float64, device="cuda")

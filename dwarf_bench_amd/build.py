@@ -102,7 +102,8 @@ def build_oracle(force: bool = False) -> Path:
 
 def build_ref(force: bool = False) -> Path | None:
     """Compile the reference pieces that build with plain g++ from where they lie (oracle/Makefile)."""
-    if not Path("/root/reference").exists() or not (ORACLE / "Makefile").exists():
+    # os.path.isdir, not Path.exists: a user who may not enter the parent directory gets False, not PermissionError
+    if not os.path.isdir("/root/reference") or not (ORACLE / "Makefile").exists():
         return None
     _run(["make", "-s", "-C", ORACLE, "ref"] + (["-B"] if force else []))
     return ORACLE / "_ref"

@@ -5,7 +5,8 @@
 //   hip_library_usage [rows] [iterations]        defaults: 1024 rows, 10 iterations
 //
 // The reference's own sample (example/bench_usage/main.cpp in kurapov-peter/dwarf_bench) also compiles unchanged
-// against this build's <bench.hpp>; tests/test_host_layer.py checks that.  This file is the HIP-side counterpart.
+// against this build's <bench.hpp>; tests/test_host_layer.py checks a client written in its style
+// (tests/cpp/bench_usage_client.cpp).  This file is the HIP-side counterpart.
 #include <bench.hpp>
 
 #include <algorithm>

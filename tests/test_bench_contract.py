@@ -65,10 +65,17 @@ def test_headline_profile_recomputes_the_roofline_fractions():
 def test_bench_defaults_and_help():
     r = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--help"], capture_output=True, text=True, timeout=120)
     assert r.returncode == 0
-    for flag in ("--gpus", "--steps", "--warmup"):
+    for flag in ("--gpus", "--steps", "--warmup", "--dump-outputs"):
         assert flag in r.stdout
     src = (ROOT / "bench.py").read_text()
     assert 'add_argument("--gpus", type=int, default=1)' in src
+
+
+def test_bench_refuses_zero_steps():
+    """ms_per_step is the time of one of the --steps timed steps: there is none to time with --steps 0"""
+    r = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--steps", "0"], capture_output=True, text=True, timeout=120)
+    assert r.returncode != 0 and "--steps must be >= 1" in r.stderr
+    assert not [l for l in r.stdout.splitlines() if l.startswith("{")]
 
 
 def test_bench_refuses_to_run_without_a_gpu():
