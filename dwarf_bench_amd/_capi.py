@@ -50,6 +50,11 @@ SIGNATURES = {
     "dbhip_bitmask_table_reset": (_int, [_vp, _sz, _sz, _vp]),
     "dbhip_bitmask_table_insert_u32": (_int, [_vp, _vp, _sz, _vp, _sz, _sz, _int, _u32, _int, _vp]),
     "dbhip_bitmask_table_lookup_u32": (_int, [_vp, _sz, _vp, _sz, _int, _u32, _vp, _vp, _vp]),
+    "dbhip_cuckoo_table_workspace_bytes": (_sz, [_sz]),
+    "dbhip_cuckoo_table_reset": (_int, [_vp, _sz, _sz, _vp]),
+    "dbhip_cuckoo_table_insert_u32": (_int, [_vp, _vp, _sz, _vp, _sz, _sz, _int, _u32, _u32, _u32, _int, _vp, _vp]),
+    "dbhip_cuckoo_table_lookup_u32": (_int, [_vp, _sz, _vp, _sz, _int, _u32, _u32, _vp, _vp, _vp]),
+    "dbhip_cuckoo_table_export_u32": (_int, [_vp, _sz, _vp, _vp, _vp]),
     "dbhip_pjoin_partition_workspace_bytes": (_sz, [_sz, _u32]),
     "dbhip_pjoin_partition_u32": (_int, [_vp, _sz, _u64, _u32, _vp, _vp, _vp, _vp, _sz, _vp]),
     "dbhip_gather_u32": (_int, [_vp, _vp, _sz, _vp, _vp]),

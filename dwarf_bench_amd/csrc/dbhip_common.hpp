@@ -109,4 +109,17 @@ __host__ __device__ __forceinline__ uint32_t fmix32(uint32_t h) {
   return h;
 }
 
+__host__ __device__ __forceinline__ uint32_t rotl32(uint32_t x, int r) { return (x << r) | (x >> (32 - r)); }
+
+// MurmurHash3_x86_32 of one 4-byte key (the reference's hasher, common/dpcpp/hashfunctions.hpp:64-130, with _len = 4:
+// one block, no tail).  The bitmask-claimed table and the cuckoo table take it modulo their size.
+__host__ __device__ __forceinline__ uint32_t murmur3_x86_32_u32(uint32_t key, uint32_t seed) {
+  uint32_t k1 = key * 0xcc9e2d51u;
+  k1 = rotl32(k1, 15) * 0x1b873593u;
+  uint32_t h1 = seed ^ k1;
+  h1 = rotl32(h1, 13) * 5u + 0xe6546b64u;
+  h1 ^= 4u;
+  return fmix32(h1);
+}
+
 }  // namespace dbhip

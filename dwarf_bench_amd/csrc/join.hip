@@ -265,15 +265,9 @@ inline BmLayout bm_layout(size_t size) {
   return L;
 }
 
-__device__ __forceinline__ unsigned rotl32(unsigned x, int r) { return (x << r) | (x >> (32 - r)); }
 __device__ __forceinline__ unsigned bm_hash(unsigned key, int kind, unsigned seed, unsigned size) {
   if (kind == 0) return key % size;
-  unsigned k1 = key * 0xcc9e2d51u;  // one 4-byte block, no tail (hashfunctions.hpp:94-133, _len = 4)
-  k1 = rotl32(k1, 15) * 0x1b873593u;
-  unsigned h1 = seed ^ k1;
-  h1 = rotl32(h1, 13) * 5u + 0xe6546b64u;
-  h1 ^= 4u;
-  return fmix32(h1) % size;
+  return murmur3_x86_32_u32(key, seed) % size;
 }
 
 // One departure from hashtable.hpp:70-92, not visible where the reference is well defined: `minor += occupied`

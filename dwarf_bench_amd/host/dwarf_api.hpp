@@ -164,6 +164,9 @@ class Registry {
 };
 
 void populate_registry();  // register_dwarfs.cpp:20-56: here it registers the ...Hip dwarfs
+// the reference's EXPERIMENTAL block (register_dwarfs.cpp:41-47, CMakeLists.txt ENABLE_EXPERIMENTAL): the dwarfs only the
+// dwarf_bench_experimental CLI registers, after populate_registry()
+void populate_experimental_registry();
 
 namespace helpers {
 // $DWARF_BENCH_ROOT or the executable's directory (common/common.cpp:38-41, without Boost.DLL)

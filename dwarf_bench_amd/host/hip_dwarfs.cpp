@@ -903,6 +903,112 @@ void NestedLoopJoinHip::run(const RunOptions &opts) {
 void NestedLoopJoinHip::init(const RunOptions &opts) { common_init(*this, opts); }
 
 // =====================================================================================================
+// CuckooHashBuildHip — build timing of the cuckoo table (hash/cuckoo_hash_build.cpp:8-134): unique keys from the
+// make_unique_random twin, vals = keys, ht_size = 4n (:14).  Hasher pair: hash_kind 2 (splitmix64), not the reference's
+// two Murmur3 seeds, whose positions come in swapped pairs and cannot hold 2^24 keys for any seeds (include/dbhip.h,
+// DESIGN.md §4.6).  The timed region is the reference's rebuild loop (:43-92):
+// reset, insert, read the status word, and again with the next seed pair while a row reports a dropped pair, at most
+// kCuckooMaxAttempts times (the reference retries without bound).  Seeds: the deterministic sequence of
+// ops.cuckoo_seed_pair (the reference draws them at random), one sequence per iteration.  kernel_time = the sum of
+// the attempts' reset + insert.  Afterwards every key must be found with its own value (:104-119); a build that failed
+// every attempt is "Incorrect results".
+namespace {
+constexpr int kCuckooMaxAttempts = 16;
+constexpr int kCuckooHashKind = 2;
+uint64_t splitmix64(uint64_t seed, uint64_t i) {  // dbhip mix64 (csrc/dbhip_common.hpp)
+  uint64_t z = (i + 1) * 0x9E3779B97F4A7C15ull + seed * 0xD1B54A32D192ED03ull;
+  z ^= z >> 30;
+  z *= 0xBF58476D1CE4E5B9ull;
+  z ^= z >> 27;
+  z *= 0x94D049BB133111EBull;
+  z ^= z >> 31;
+  return z;
+}
+void cuckoo_seed_pair(uint64_t seed, uint64_t attempt, uint32_t *s1, uint32_t *s2) {  // = ops.cuckoo_seed_pair
+  *s1 = static_cast<uint32_t>(splitmix64(seed, 2 * attempt));
+  *s2 = static_cast<uint32_t>(splitmix64(seed, 2 * attempt + 1));
+  if (*s2 == *s1) *s2 ^= 1u;
+}
+}  // namespace
+
+CuckooHashBuildHip::CuckooHashBuildHip() : Dwarf("CuckooHashBuildHip") {}
+void CuckooHashBuildHip::_run(const size_t n, Meter &meter) {
+  const RunOptions &opts = meter.opts();
+  banner("CuckooHashBuildHip");
+  if (10ull * n > 0xFFFFFFFFull) fail("CuckooHashBuildHip: keys are drawn from [0, 10*n) and must fit 32 bits");
+  const size_t ht_size = n ? 4 * n : 1;  // cuckoo_hash_build.cpp:14
+  DevBuf<uint32_t> keys(n), vals(n), found(n);
+  db_ok(dbhip_gen_unique_sorted_u32(keys.get(), n, 11, 0, nullptr), "gen");  // make_unique_random (:12)
+  const size_t ws_bytes = dbhip_cuckoo_table_workspace_bytes(ht_size);
+  DevBuf<unsigned char> ws(ws_bytes);
+  const bool host_check = n <= validate_limit();
+  CheckWords chk;
+  std::array<uint64_t, 4> key_fp{};
+  if (!host_check) {  // sortedness + multiset fingerprint of the keys: what the looked-up values must reproduce
+    db_ok(dbhip_check_sorted_u32(keys.get(), n, 0, chk.dev(), nullptr), "dbhip_check_sorted_u32");
+    key_fp = chk.get();
+  }
+  hip_ok(hipDeviceSynchronize(), "sync");
+  Events ev;
+  for (size_t it = 0; it < opts.iterations; ++it) {
+    auto result = std::make_unique<Result>();
+    uint32_t s1 = 0, s2 = 0;
+    int attempts = 0;
+    bool built = false;
+    Duration kernel{0};
+    const auto host_start = clk::now();
+    while (!built && attempts < kCuckooMaxAttempts) {
+      cuckoo_seed_pair(it, attempts, &s1, &s2);
+      ++attempts;
+      hip_ok(hipEventRecord(ev.a, nullptr), "event");
+      db_ok(dbhip_cuckoo_table_reset(ws.get(), ws_bytes, ht_size, nullptr), "dbhip_cuckoo_table_reset");
+      db_ok(dbhip_cuckoo_table_insert_u32(keys.get(), keys.get(), n, ws.get(), ws_bytes, ht_size, kCuckooHashKind, s1, s2, 0, 0,
+                                          nullptr, nullptr),
+            "dbhip_cuckoo_table_insert_u32");
+      hip_ok(hipEventRecord(ev.b, nullptr), "event");
+      uint32_t st = 0xFFFFFFFFu;
+      db_ok(dbhip_workspace_status(ws.get(), &st, nullptr), "dbhip_workspace_status");  // synchronises
+      kernel += ev.elapsed();
+      if (st != DBHIP_DEV_OK && st != DBHIP_DEV_TABLE_FULL)
+        fail("CuckooHashBuildHip: device status " + std::to_string(st));
+      built = st == DBHIP_DEV_OK;
+    }
+    const auto host_end = clk::now();
+    result->host_time = host_end - host_start;
+    result->kernel_time = kernel;
+    std::cout << "CuckooHashBuildHip: " << n << " keys, " << ht_size << " slots: " << attempts
+              << (attempts == 1 ? " attempt" : " attempts") << (built ? "" : ", every one failed") << "\n";
+    bool ok = built;
+    if (ok && n) {  // cuckoo_hash_build.cpp:104-119: every key is found, here also with its own value
+      db_ok(dbhip_cuckoo_table_lookup_u32(keys.get(), n, ws.get(), ht_size, kCuckooHashKind, s1, s2, vals.get(), found.get(), nullptr),
+            "dbhip_cuckoo_table_lookup_u32");
+      hip_ok(hipStreamSynchronize(nullptr), "sync");
+      if (inject_fault()) poke_xor(vals.get() + n / 2, 1u);
+      if (host_check) {
+        const auto hf = found.to_host(n);
+        ok = std::all_of(hf.begin(), hf.end(), [](uint32_t f) { return f == 1u; }) && vals.to_host(n) == keys.to_host(n);
+      } else {  // found: n ones; vals: ascending with the keys' multiset fingerprint, i.e. equal to the sorted keys
+        db_ok(dbhip_check_sorted_u32(found.get(), n, 0, chk.dev(), nullptr), "dbhip_check_sorted_u32");
+        const auto g = chk.get();
+        ok = g[0] == 0 && g[2] == n;
+        db_ok(dbhip_check_sorted_u32(vals.get(), n, 0, chk.dev(), nullptr), "dbhip_check_sorted_u32");
+        const auto v = chk.get();
+        ok = ok && v[0] == 0 && v[1] == key_fp[1] && v[2] == key_fp[2];
+      }
+    }
+    if (!ok) {
+      std::cerr << "Incorrect results" << std::endl;
+      result->valid = false;
+    }
+    meter.add_result(size_param(n), std::move(result));
+  }
+}
+void CuckooHashBuildHip::run(const RunOptions &opts) {
+  for (auto size : opts.input_size) _run(size, meter());
+}
+void CuckooHashBuildHip::init(const RunOptions &opts) { common_init(*this, opts); }
+
+// =====================================================================================================
 // PartitionedJoinHip — the radix-partitioned hash join of SURVEY 8(e) behind the Dwarf hook: one process driving
 // `--gpus P` ranks through pjoin::Engine (pjoin_engine.hpp: per-rank compute and exchange streams, counts by
 // ncclAllGather, exchange of R overlapping partition S, exchange of S overlapping build R).  No reference

@@ -35,5 +35,7 @@ DBHIP_DECLARE_DWARF(HashBuildNonBitmaskHip);  // hash/hash_build_non_bitmask.cpp
 DBHIP_DECLARE_DWARF(ProbeHip);                // probe/slab_probe.cpp:9-107 (table built untimed, lookups timed)
 DBHIP_DECLARE_DWARF(ReduceHip);               // reduce/reduce.cpp:27-98 (int sum)
 DBHIP_DECLARE_DWARF(NestedLoopJoinHip);       // join/nested_join.cpp:10-110 (dense cell matrix, small n)
+// the reference's EXPERIMENTAL block: registered by populate_experimental_registry() only
+DBHIP_DECLARE_DWARF(CuckooHashBuildHip);      // hash/cuckoo_hash_build.cpp:8-134 (lock-free cuckoo table, rebuild on failure)
 
 #undef DBHIP_DECLARE_DWARF

@@ -3,6 +3,8 @@
 //   dwarf_bench <Dwarf|list> [--input_size N [N ...]] [--iterations K] [--device cpu|gpu|igpu|hip]
 //               [--report_path FILE] [--groups_count G] [--executors E] [--gpus P] [--help]
 // Exit codes as in the reference: 1 for an unknown dwarf, 0 otherwise — also after a caught exception.
+// Built twice: `dwarf_bench`, and with -DEXPERIMENTAL `dwarf_bench_experimental`, which also registers the reference's
+// EXPERIMENTAL dwarfs that have a HIP counterpart (populate_experimental_registry).
 #include <iostream>
 #include <memory>
 #include <sstream>
@@ -32,6 +34,9 @@ bool is_flag(const std::string &s) { return s.rfind("--", 0) == 0; }
 
 int main(int argc, char *argv[]) {
   populate_registry();
+#ifdef EXPERIMENTAL
+  populate_experimental_registry();  // dwarf_bench_experimental
+#endif
   Registry *registry = Registry::instance();
 
   auto opts = std::make_unique<RunOptions>();

@@ -2,6 +2,8 @@
 // registers its dwarfs under EXPERIMENTAL / DPCPP_ENABLED / CUDA_ENABLED guards; this build has one
 // guard, HIP_ENABLED, and registers the hand-written gfx950 dwarfs — plus, unguarded, the two HOST dwarfs of the hot
 // path under the reference's own names (cpu_dwarfs.cpp: TwoPassScan for --device=cpu, TBBSort).
+// populate_experimental_registry() is the reference's `#ifdef EXPERIMENTAL` block (:41-47): only the
+// dwarf_bench_experimental CLI (main.cpp built with -DEXPERIMENTAL) calls it.
 #include "cpu_dwarfs.hpp"
 #include "dwarf_api.hpp"
 #include "hip_dwarfs.hpp"
@@ -24,5 +26,12 @@ void populate_registry() {
   registry->registerd(new ProbeHip());
   registry->registerd(new ReduceHip());
   registry->registerd(new NestedLoopJoinHip());
+#endif
+}
+
+void populate_experimental_registry() {
+#ifdef HIP_ENABLED
+  Registry *registry = Registry::instance();
+  registry->registerd(new CuckooHashBuildHip());  // hash/cuckoo_hash_build.cpp (register_dwarfs.cpp:44 in the reference)
 #endif
 }

@@ -439,6 +439,111 @@ class BitmaskTable:
 
 
 # ---------------------------------------------------------------------------------------------
+# cuckoo table (CuckooHashtable counterpart, common/dpcpp/cuckoo_hashtable.hpp)
+# ---------------------------------------------------------------------------------------------
+def cuckoo_seed_pair(seed: int, attempt: int) -> tuple[int, int]:
+    """The (seed1, seed2) of build attempt `attempt`: the low words of splitmix64(seed, 2a) and (seed, 2a + 1), seed2
+    nudged off seed1.  The reference draws them at random (helpers::make_random); a fixed sequence makes a failing build
+    reproducible.  CuckooHashBuildHip (host/hip_dwarfs.cpp) uses the same sequence."""
+    m = (1 << 64) - 1
+
+    def mix(i: int) -> int:
+        z = ((i + 1) * 0x9E3779B97F4A7C15 + seed * 0xD1B54A32D192ED03) & m
+        z = ((z ^ (z >> 30)) * 0xBF58476D1CE4E5B9) & m
+        z = ((z ^ (z >> 27)) * 0x94D049BB133111EB) & m
+        return (z ^ (z >> 31)) & 0xFFFFFFFF
+
+    s1, s2 = mix(2 * attempt), mix(2 * attempt + 1)
+    return s1, (s2 ^ 1 if s2 == s1 else s2)
+
+
+class CuckooTable:
+    """Two-choice cuckoo table of `table_size` 8-byte slots.  hash_kind 0: (k % size + seed) % size, 1: Murmur3(k, seed)
+    % size (the reference's hasher), 2: (mix64(seed, k) >> 32) % size (include/dbhip.h: kind 1 cannot hold millions of
+    keys); seeds = (seed1, seed2) make h1 and h2.  insert() is asynchronous; failed() / status() synchronise."""
+
+    def __init__(self, table_size: int, hash_kind: int = 1, seeds: tuple[int, int] = (0, 1), device="cuda"):
+        self.size, self.kind = table_size, hash_kind
+        self.seeds = (seeds[0] & 0xFFFFFFFF, seeds[1] & 0xFFFFFFFF)
+        self.ws_bytes = _capi.lib().dbhip_cuckoo_table_workspace_bytes(table_size)
+        self.ws = _ws(self.ws_bytes, device)
+        self.reset()
+
+    def reset(self) -> None:
+        """empty every slot and clear the status word"""
+        _capi.check(_capi.lib().dbhip_cuckoo_table_reset(self.ws.data_ptr(), self.ws_bytes, self.size, _stream()),
+                    "cuckoo_table_reset")
+
+    def insert(self, keys: torch.Tensor, vals: torch.Tensor, serial: bool = False, max_iter: int = 0,
+               want_results: bool = False):
+        """insert (keys[i], vals[i]); max_iter = exchanges per row before it gives up (0: min(n, 100000)).
+        want_results: returns an int32 tensor, 1 where the row was stored."""
+        _need(keys, torch.int32, "keys")
+        _need(vals, torch.int32, "vals")
+        n = keys.numel()
+        if vals.numel() != n:
+            raise ValueError("keys and vals differ in length")
+        res = torch.empty(max(n, 1), dtype=torch.int32, device=keys.device) if want_results else None
+        _capi.check(_capi.lib().dbhip_cuckoo_table_insert_u32(
+            keys.data_ptr(), vals.data_ptr(), n, self.ws.data_ptr(), self.ws_bytes, self.size, self.kind, self.seeds[0],
+            self.seeds[1], max_iter, int(serial), res.data_ptr() if want_results else None, _stream()),
+            "cuckoo_table_insert")
+        return res[:n] if want_results else None
+
+    def status(self) -> int:
+        """the device status word since the last reset (synchronises): DEV_TABLE_FULL, DEV_KEY_RANGE"""
+        return workspace_status(self.ws)
+
+    def failed(self) -> bool:
+        """True if a row since the last reset gave up (its eviction chain reached max_iter, a pair was dropped)"""
+        return bool(self.status() & DEV_TABLE_FULL)
+
+    def lookup(self, keys: torch.Tensor):
+        """(vals, found): the value stored with each key (0 when missing) and 1 / 0"""
+        _need(keys, torch.int32, "keys")
+        n = keys.numel()
+        vals = torch.empty(max(n, 1), dtype=torch.int32, device=keys.device)
+        found = torch.empty(max(n, 1), dtype=torch.int32, device=keys.device)
+        _capi.check(_capi.lib().dbhip_cuckoo_table_lookup_u32(keys.data_ptr(), n, self.ws.data_ptr(), self.size, self.kind,
+                                                              self.seeds[0], self.seeds[1], vals.data_ptr(),
+                                                              found.data_ptr(), _stream()), "cuckoo_table_lookup")
+        return vals[:n], found[:n]
+
+    def slots(self):
+        """(keys, vals) of every slot; an empty slot is (-1, 0) (key 0xFFFFFFFF)"""
+        keys = torch.empty(self.size, dtype=torch.int32, device=self.ws.device)
+        vals = torch.empty(self.size, dtype=torch.int32, device=self.ws.device)
+        _capi.check(_capi.lib().dbhip_cuckoo_table_export_u32(self.ws.data_ptr(), self.size, keys.data_ptr(),
+                                                              vals.data_ptr(), _stream()), "cuckoo_table_export")
+        return keys, vals
+
+
+def cuckoo_build(keys: torch.Tensor, vals: torch.Tensor, table_size: int | None = None, max_attempts: int = 16,
+                 seed: int = 0, hash_kind: int = 2):
+    """Build a cuckoo table over (keys, vals), rebuilding with the next seed pair (cuckoo_seed_pair(seed, attempt))
+    while an insert reports a dropped pair, as hash/cuckoo_hash_build.cpp:43-92 does.  table_size defaults to 4 * n
+    (:14).  hash_kind defaults to 2: with the reference's Murmur3 pair (1) large builds fail for every seed pair.
+    Returns (table, attempts); raises after max_attempts failed builds, and at once on any other device status."""
+    n = keys.numel()
+    size = table_size if table_size is not None else max(4 * n, 1)
+    table = None
+    for attempt in range(max_attempts):
+        seeds = cuckoo_seed_pair(seed, attempt)
+        if table is None:
+            table = CuckooTable(size, hash_kind, seeds, device=keys.device)
+        else:
+            table.seeds = seeds
+            table.reset()
+        table.insert(keys, vals)
+        st = table.status()
+        if st == DEV_OK:
+            return table, attempt + 1
+        if st != DEV_TABLE_FULL:
+            raise _capi.DbhipError(f"cuckoo_build: device status {st:#x}")
+    raise _capi.DbhipError(f"cuckoo_build: {max_attempts} attempts failed at {n} keys in {size} slots")
+
+
+# ---------------------------------------------------------------------------------------------
 # exclusive prefix sum (scan/scan.cl:44-66, tests/scan_tests.cpp:14-21, dpl_wrapper.hpp:18-25)
 # ---------------------------------------------------------------------------------------------
 class ExclusiveScan:

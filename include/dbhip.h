@@ -29,6 +29,8 @@
  *   dbhip_groupby_partial/merge_u32  groupby/groupby_local.cpp:52-112 (the two timed phases of GroupByLocal)
  *   dbhip_bitmask_table_*     common/dpcpp/hashtable.hpp:5-93 (SimpleNonOwningHashTable) <- hash/hash_build.cpp:8-98,
  *                             join/join.cpp:30-38, tests/hash_table_tests.cpp
+ *   dbhip_cuckoo_table_*      common/dpcpp/cuckoo_hashtable.hpp (CuckooHashtable) <- hash/cuckoo_hash_build.cpp:8-120,
+ *                             tests/cuckoo_hashtable_tests.cpp
  *   dbhip_reduce_sum_i32      reduce/reduce.cpp:27-88
  *   dbhip_nested_join_u32     join/nested_join.cpp:52-66
  *   dbhip_pjoin_*             no reference counterpart (multi-GPU radix-partitioned join)
@@ -62,7 +64,9 @@ extern "C" {
 #define DBHIP_DEV_KEY_RANGE 2u     /* group key >= groups_count, or the 0xFFFFFFFF sentinel as a join build key */
 #define DBHIP_DEV_TABLE_FULL 4u    /* open-addressing table wrapped without finding a slot: the bitmask-claimed table (a
                                       table that really is full: the reference spins forever there) and the small-input
-                                      unique-key table.  NOT the LDS-partitioned joins (dbhip_join_build* / _radix_* /
+                                      unique-key table; the cuckoo table: an insert's eviction chain reached max_iter
+                                      exchanges and the pair it carried was dropped (a normal result: rebuild with other
+                                      seeds).  NOT the LDS-partitioned joins (dbhip_join_build* / _radix_* /
                                       dbhip_ujoin_* from 2^16 rows): a partition with more distinct keys than its 3072-slot
                                       LDS sub-table holds is built in a spill table of its own, any keys join (the one
                                       exception: a one-to-many build of exactly 2^31 rows has no spare bit to mark such a
@@ -244,6 +248,39 @@ int dbhip_bitmask_table_insert_u32(const uint32_t *keys, const uint32_t *vals, s
 int dbhip_bitmask_table_lookup_u32(const uint32_t *keys, size_t n, const void *workspace, size_t table_size,
                                    int hash_kind, uint32_t seed, uint32_t *out_vals, uint32_t *out_found,
                                    dbhip_stream_t stream);
+
+/* ---- cuckoo table: HIP counterpart of CuckooHashtable (common/dpcpp/cuckoo_hashtable.hpp), the table of the
+ * reference's CuckooHashBuild dwarf.  Two positions per key, h1(k) and h2(k): hash_kind 0 = (k % size + seed) % size
+ * (StaticSimpleHasher / StaticSimpleHasherWithOffset, hashfunctions.hpp:33-41), 1 = MurmurHash3_x86_32(k, seed) % size
+ * (hashfunctions.hpp:64-130), 2 = (mix64(seed, k) >> 32) % size (the generators' splitmix64); seed1 makes h1, seed2
+ * makes h2.  Kind 1 is the reference's pair, but two Murmur3 seeds are related by an XOR: for every key there is a key
+ * whose two positions are the same two slots swapped, and from about 2^22 keys a build fails for any seeds (DESIGN.md
+ * §4).  Kind 2 is the pair for large builds.  Workspace: header | slots[table_size] of 8 bytes,
+ * key in the low word and value in the high word, empty = key 0xFFFFFFFF / value 0; table_size <= 2^32 - 1.
+ *   reset   clears the status word and empties every slot.
+ *   insert  lock-free: each row carries its (key, value) pair through a chain of 64-bit atomic exchanges, from h1(key)
+ *           on, each evicted pair moving to its other position (cuckoo_hashtable.hpp:43-63); the chain ends at an empty
+ *           slot or after max_iter exchanges (0 = the reference's min(n, 100000); at most 2^20), where the pair carried
+ *           last is DROPPED, as in the reference, and DBHIP_DEV_TABLE_FULL is ORed into the status word.  Key
+ *           0xFFFFFFFF is not stored (DBHIP_DEV_KEY_RANGE).  out_inserted (nullable) gets 1 / 0 per row.  The status
+ *           word accumulates until the next reset.  serial != 0 inserts with ONE work-item in input order (reproduces
+ *           the slot layouts and per-insert results of the reference's cuckoo_hashtable_tests).
+ *           Rebuilding with other seeds after a failure is the caller's job (hash/cuckoo_hash_build.cpp:43-92).
+ *   lookup  after an insert call has finished (a pair that is being moved sits in no slot): h1(k), then h2(k) only if
+ *           the h1 slot holds another key; out_vals[i] = the value or 0, out_found[i] = 1 / 0.  The h1 slot wins when
+ *           both hold k (duplicate keys; at(), :29-37).
+ *   export  out_keys[i] / out_vals[i] = the pair in slot i (the slot layout, for tests and callers).           */
+size_t dbhip_cuckoo_table_workspace_bytes(size_t table_size);
+int dbhip_cuckoo_table_reset(void *workspace, size_t workspace_bytes, size_t table_size, dbhip_stream_t stream);
+int dbhip_cuckoo_table_insert_u32(const uint32_t *keys, const uint32_t *vals, size_t n, void *workspace,
+                                  size_t workspace_bytes, size_t table_size, int hash_kind, uint32_t seed1,
+                                  uint32_t seed2, uint32_t max_iter, int serial, uint32_t *out_inserted /* nullable */,
+                                  dbhip_stream_t stream);
+int dbhip_cuckoo_table_lookup_u32(const uint32_t *keys, size_t n, const void *workspace, size_t table_size,
+                                  int hash_kind, uint32_t seed1, uint32_t seed2, uint32_t *out_vals,
+                                  uint32_t *out_found, dbhip_stream_t stream);
+int dbhip_cuckoo_table_export_u32(const void *workspace, size_t table_size, uint32_t *out_keys,
+                                  uint32_t *out_vals, dbhip_stream_t stream);
 
 /* ---- multi-GPU radix-partitioned join: device pieces (no reference counterpart) ---------
  * Partition a local column shard into `parts` (1..1024) destination buckets by a mixed hash of

@@ -20,6 +20,8 @@ the contract numbers come from bench.py.
   size-sweep      every dwarf at sizes next to and between powers of two, 2^13 .. 2^26 (geometry cliffs)
   partition       rank-level partition (dbhip_pjoin_partition_u32) of 2^27 rows into P buckets
   reduce          2^28-row reduce (median of 15; DBHIP_RED_WGS)
+  cuckoo [lg]     cuckoo table (hash_kind 2) at 2^lg unique keys in 4 * 2^lg slots (default lg 24): reset, insert, lookups of present
+                  and of absent keys (median of 9), each checked against torch
   xscan [lg]      exclusive scan of 2^lg uint32, aligned (one launch) and offset by one element (three launches)
   graph           direct launches vs hipGraph replay of sort and join at 2^14..2^20 rows (host wall clock)
   launch-join [lg] / launch-sort [lg] / launch-all
@@ -564,6 +566,35 @@ def reduce(_):
           f"{'ok' if got == want else 'WRONG'}", flush=True)
 
 
+def cuckoo(lg):
+    lg = lg or 24
+    n = 1 << lg
+    keys = ops.gen_unique_sorted_u32(n, 11)
+    absent = bits32(u64(keys) - u64(keys) % 10 + (u64(keys) % 10 + 1) % 10)  # same decade, another digit: never generated
+    t = ops.CuckooTable(4 * n, 2, ops.cuckoo_seed_pair(0, 0))  # the dwarf's hasher pair
+    t.insert(keys, keys)
+    if t.failed():
+        raise SystemExit(f"{TAG}: the first seed pair failed at 2^{lg}")
+    r = median(times(t.reset, 9))
+
+    def build():
+        t.reset()
+        t.insert(keys, keys)
+
+    b = median(times(build, 9))
+    if t.failed():
+        raise SystemExit(f"{TAG}: a timed build failed at 2^{lg}")
+    vals, found = t.lookup(keys)
+    ok = bool((found == 1).all()) and torch.equal(vals, keys)
+    lp = median(times(lambda: t.lookup(keys), 9))
+    vals, found = t.lookup(absent)
+    ok = ok and not bool(found.any()) and not bool(vals.any())
+    la = median(times(lambda: t.lookup(absent), 9))
+    print(f"{TAG:20s} 2^{lg} keys, {4 * n} slots: reset {r:8.1f} us, reset + insert {b:8.1f} us (insert {b - r:8.1f} us, "
+          f"{n / (b - r) / 1e3:6.2f} G keys/s) | lookup present {lp:8.1f} us ({n / lp / 1e3:6.2f} G/s), absent {la:8.1f} us "
+          f"({n / la / 1e3:6.2f} G/s) | {'ok' if ok else 'WRONG'}", flush=True)
+
+
 def xscan(lg):
     lg = lg or 28
     n = 1 << lg
@@ -681,7 +712,7 @@ def launch_all(_):
 
 
 MODES = {"radix": radix, "ramp": ramp, "radix-idle": radix_idle, "radix-stream": radix_stream, "radix-alloc": radix_alloc, "radix-offsets": radix_offsets, "radix-sizes": radix_sizes, "graph": graph, "launch-join": launch_join, "launch-sort": launch_sort, "launch-all": launch_all, "scan": scan, "sort": sort, "sort-only": sort_only, "groupby": groupby, "groupby-shapes": groupby_shapes, "groupby-skew": groupby_skew, "sort-shapes": sort_shapes, "join": join, "join-skew": join_skew, "size-sweep": size_sweep, "partition": partition,
-         "reduce": reduce, "xscan": xscan}
+         "reduce": reduce, "xscan": xscan, "cuckoo": cuckoo}
 
 if __name__ == "__main__":
     if len(sys.argv) < 2 or sys.argv[1] not in MODES:

@@ -40,7 +40,8 @@ __global__ __launch_bounds__(256) void k_gen_idx(unsigned* p, size_t n, unsigned
   const size_t stride = (size_t)gridDim.x * 256;
   for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += stride) p[i] = (unsigned)mix64(seed, i) & mask;
 }
-// mode 0: gather 4B, 1: gather 16B (idx&~3), 2: atomicAdd, 3: atomicCAS, 4: scatter 4B store, 5: scatter 8B store
+// mode 0: gather 4B, 1: gather 16B (idx&~3), 2: atomicAdd, 3: atomicCAS, 4: scatter 4B store, 5: scatter 8B store,
+// 6: 8-byte atomic swap (global_atomic_swap_x2 with return, the cuckoo insert's one operation)
 template <int MODE>
 __global__ __launch_bounds__(256) void k_random(const unsigned* __restrict__ idx, size_t n, unsigned* table, unsigned* out) {
   unsigned acc = 0;
@@ -52,7 +53,8 @@ __global__ __launch_bounds__(256) void k_random(const unsigned* __restrict__ idx
     else if (MODE == 2) atomicAdd(&table[j], 1u);
     else if (MODE == 3) acc += atomicCAS(&table[j], 0xFFFFFFFFu, (unsigned)i);
     else if (MODE == 4) table[j] = (unsigned)i;
-    else { uint2 v = make_uint2((unsigned)i, j); *reinterpret_cast<uint2*>(table + (j & ~1u)) = v; }
+    else if (MODE == 5) { uint2 v = make_uint2((unsigned)i, j); *reinterpret_cast<uint2*>(table + (j & ~1u)) = v; }
+    else acc += (unsigned)atomicExch(reinterpret_cast<unsigned long long*>(table) + (j >> 1), (unsigned long long)i << 32 | j);
   }
   if (acc == 0x12345678u) out[0] = acc;
 }
@@ -108,8 +110,9 @@ int main() {
     float ac = timeit([&] { hipLaunchKernelGGL((k_random<3>), dim3(cus * 8), dim3(256), 0, 0, idx, M, b, out); }, 3);
     float s4 = timeit([&] { hipLaunchKernelGGL((k_random<4>), dim3(cus * 8), dim3(256), 0, 0, idx, M, b, out); });
     float s8 = timeit([&] { hipLaunchKernelGGL((k_random<5>), dim3(cus * 8), dim3(256), 0, 0, idx, M, b, out); });
-    printf("random 2^26 ops, table %5zu MiB: gather4 %.0f us (%.1f G/s) gather16 %.0f us | atomicAdd %.0f us (%.1f G/s) atomicCAS %.0f us | scatter4 %.0f us (%.1f G/s) scatter8 %.0f us\n",
-           ((size_t)4 << lg) >> 20, g4 * 1e3, M / g4 / 1e6, g16 * 1e3, aa * 1e3, M / aa / 1e6, ac * 1e3, s4 * 1e3, M / s4 / 1e6, s8 * 1e3);
+    float x8 = timeit([&] { hipLaunchKernelGGL((k_random<6>), dim3(cus * 8), dim3(256), 0, 0, idx, M, b, out); }, 3);
+    printf("random 2^26 ops, table %5zu MiB: gather4 %.0f us (%.1f G/s) gather16 %.0f us | atomicAdd %.0f us (%.1f G/s) atomicCAS %.0f us (%.1f G/s) | scatter4 %.0f us (%.1f G/s) scatter8 %.0f us | swap8 %.0f us (%.1f G/s)\n",
+           ((size_t)4 << lg) >> 20, g4 * 1e3, M / g4 / 1e6, g16 * 1e3, aa * 1e3, M / aa / 1e6, ac * 1e3, M / ac / 1e6, s4 * 1e3, M / s4 / 1e6, s8 * 1e3, x8 * 1e3, M / x8 / 1e6);
   }
   for (unsigned lbits : {4u, 8u, 12u, 15u}) {
     hipLaunchKernelGGL(k_gen_idx, dim3(cus * 8), dim3(256), 0, 0, idx, M, 0xFFFFFFFFu, 99ull);
