@@ -156,7 +156,7 @@ extern "C" int dbhip_join_radix_partition_u32(int probe_side, const uint32_t *ke
                                               size_t n_build, size_t n_probe, void *workspace, size_t workspace_bytes,
                                               dbhip_stream_t stream) {
   if (n != (probe_side ? n_probe : n_build) || (n && !keys)) return DBHIP_EINVAL;
-  if (n_build > kJlMaxRows || n_probe > 0xFFFFFFFFull) return DBHIP_EINVAL;
+  if (n_build > kJlMaxRows || n_probe > jr_max_probe_rows()) return DBHIP_EINVAL;
   if (!ws_ok(workspace, workspace_bytes, join_radix_workspace_bytes(n_build, n_probe))) return DBHIP_EWORKSPACE;
   const DeviceInfo &dev = current_device_info();
   if (!dev.ok) return DBHIP_ENODEVICE;
@@ -167,7 +167,7 @@ extern "C" int dbhip_join_radix_match_u32(size_t n_build, size_t n_probe, uint32
                                           uint32_t *out_pos, uint32_t *out_count, void *workspace, size_t workspace_bytes,
                                           dbhip_stream_t stream) {
   if ((n_build && !ids) || (n_probe && (!out_probe_row_ids || !out_pos || !out_count))) return DBHIP_EINVAL;
-  if (n_build > kJlMaxRows || n_probe > 0xFFFFFFFFull) return DBHIP_EINVAL;
+  if (n_build > kJlMaxRows || n_probe > jr_max_probe_rows()) return DBHIP_EINVAL;
   if (!ws_ok(workspace, workspace_bytes, join_radix_workspace_bytes(n_build, n_probe))) return DBHIP_EWORKSPACE;
   const DeviceInfo &dev = current_device_info();
   if (!dev.ok) return DBHIP_ENODEVICE;

@@ -170,6 +170,7 @@ int jl_partition(const unsigned *keys, size_t n, unsigned long long first_row, u
                  unsigned *out_rids, unsigned long long *out_counts, void *workspace, hipStream_t s,
                  const DeviceInfo &dev);
 size_t join_radix_workspace_bytes(size_t n_build, size_t n_probe);
+size_t jr_max_probe_rows();  // the radix join's largest n_probe (include/dbhip.h)
 int join_radix_partition(int probe_side, const unsigned *keys, const unsigned *row_ids, size_t n, size_t n_build,
                          size_t n_probe, void *workspace, hipStream_t s, const DeviceInfo &dev);
 int join_radix_match(size_t n_build, size_t n_probe, unsigned *ids, unsigned *out_rid, unsigned *out_pos, unsigned *out_cnt,

@@ -1394,6 +1394,10 @@ __global__ __launch_bounds__(kJlBuildThreads) __attribute__((amdgpu_waves_per_eu
 // Nothing here waits for another workgroup.
 constexpr unsigned kJlSlice = 8192;        // rows of a slice: 16 per thread
 constexpr int kJlGiantThreads = 512;
+// jl_giant_ids_kernel calls jl_spill_partition, whose loops stride by kJlBuildThreads: with narrower giant workgroups
+// they would skip rows, with wider ones walk rows twice
+static_assert(kJlGiantThreads == kJlBuildThreads,
+              "jl_spill_partition runs in build (kJlBuildThreads) and giant (kJlGiantThreads) workgroups: they must be equally wide");
 // the slices of the listed giants as one flat list: s_first[g] = index of giant g's first slice (s_first[ng] = total)
 __device__ __forceinline__ unsigned jl_giant_slices(const JlGiants &giants, const unsigned long long *__restrict__ starts,
                                                     unsigned *s_first, unsigned *s_wsum, unsigned *ng_out) {
@@ -2258,6 +2262,10 @@ void jr_side(const JrLayout &L, char *base, bool probe, const unsigned **pairs, 
 
 size_t join_radix_workspace_bytes(size_t n_build, size_t n_probe) { return jr_layout(n_build, n_probe).total; }
 
+// jl_build_kernel<true, ...> walks a partition's probe rows with 32-bit indices: j0 < shi <= n_probe, then
+// j0 += 4 * kJlBuildThreads, which must not wrap past 2^32 - 1
+size_t jr_max_probe_rows() { return (static_cast<size_t>(1) << 32) - 4 * static_cast<size_t>(kJlBuildThreads); }
+
 int join_radix_partition(int probe_side, const unsigned *keys, const unsigned *row_ids, size_t n, size_t n_build,
                          size_t n_probe, void *workspace, hipStream_t s, const DeviceInfo &dev) {
   const JrLayout L = jr_layout(n_build, n_probe);
@@ -2304,6 +2312,12 @@ int join_radix_match(size_t n_build, size_t n_probe, unsigned *ids, unsigned *ou
   }
   const JlMatchArgs match{reinterpret_cast<const u32x2 *>(pp), ps, out_rid, out_pos, out_cnt};
   unsigned *status = reinterpret_cast<unsigned *>(base);
+  // the spilled-partition list and the pool cursor belong to this match, not to the partitioned sides: a second match
+  // on the same sides would list every spilled partition again (two workgroups building one table) and allocate on
+  // from the pool.  (The spill directory needs no clear: the build kernel writes every partition's entry.)
+  static_assert(kJlHdrSpillPool == kJlHdrSpilled + 1, "header words 34 and 35 are cleared together");
+  e = fill_async(status + kJlHdrSpilled, 0, 2 * sizeof(unsigned), s);
+  if (e != hipSuccess) return static_cast<int>(e);
   const JlSpill spill = jl_spill_of(base + L.spill_off, L.parts, n_build);
   if (L.max_giants) {
     hipLaunchKernelGGL((jl_build_kernel<true, false>), dim3(jl_build_grid<true>(L.parts, dev)), dim3(kJlBuildThreads), build_lds, s, bp,

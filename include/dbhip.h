@@ -200,7 +200,10 @@ int dbhip_join_probe_u32(const uint32_t *probe_keys, size_t n_probe, const void 
  * order, each probe row's id (probe_row_ids[i], or i when probe_row_ids is NULL), the offset of its ids and their
  * number.  The three steps are separate entry points so that a host can overlap them with other work (the build
  * side's partition call opens a join: it clears the status word and must come first); dbhip_join_radix_u32 runs all
- * three.  Same contract as above (the sentinel key is flagged; any other keys join).                              */
+ * three.  The match may be repeated on one partitioned pair: every match gives the same answers (the order of ids
+ * inside one key's range aside).  n_probe is at most 2^32 - 2048 (the fused kernel's 32-bit probe-row indices step
+ * 2048 rows at a time); larger sizes are DBHIP_EINVAL in the partition and match calls.  Same contract as above (the
+ * sentinel key is flagged; any other keys join).                                                                   */
 size_t dbhip_join_radix_workspace_bytes(size_t n_build, size_t n_probe);
 int dbhip_join_radix_partition_u32(int probe_side, const uint32_t *keys, const uint32_t *row_ids, size_t n,
                                    size_t n_build, size_t n_probe, void *workspace, size_t workspace_bytes,

@@ -66,3 +66,19 @@ def test_join_partition_geometry_for_every_row_count(tmp_path):
                     str(ROOT / "tests" / "cpp" / "join_layout_check.cpp"), "-o", str(exe)], check=True, timeout=600)
     r = subprocess.run([str(exe)], capture_output=True, text=True, timeout=300)
     assert r.returncode == 0 and "join layout ok" in r.stdout, r.stdout[-2000:]
+
+
+def test_radix_join_refuses_probe_sides_its_32_bit_row_indices_cannot_walk():
+    """The radix join's fused kernel steps through a partition's probe rows with 32-bit indices, 4 * 512 rows at a time:
+    n_probe above 2^32 - 2048 is DBHIP_EINVAL in the partition and match calls (include/dbhip.h).  The workspace passed
+    is one byte short of what the sizes need, so a call the bound lets through stops at the workspace check
+    (DBHIP_EWORKSPACE) before it looks for a device: the fake pointers reach nothing on a box with a GPU either."""
+    lib = _capi.lib()
+    bound = (1 << 32) - 2048
+    fake = 1 << 20  # 256-byte aligned, never dereferenced
+    n_build = 1000
+    for n_probe, want in ((bound + 1, -1), (bound, -2), ((1 << 32) - 1, -1), (1 << 32, -1)):
+        short = lib.dbhip_join_radix_workspace_bytes(n_build, n_probe) - 1
+        assert lib.dbhip_join_radix_partition_u32(1, fake, None, n_probe, n_build, n_probe, fake, short, None) == want, n_probe
+        assert lib.dbhip_join_radix_partition_u32(0, fake, None, n_build, n_build, n_probe, fake, short, None) == want, n_probe
+        assert lib.dbhip_join_radix_match_u32(n_build, n_probe, fake, fake, fake, fake, fake, short, None) == want, n_probe

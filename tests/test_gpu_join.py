@@ -8,6 +8,7 @@ import pytest
 import torch
 
 from oracle import pyoracle as po
+from tests.join_testlib import check_grouped_join, keys_of_partition, keys_of_partition_of, radix_parts
 
 pytestmark = pytest.mark.gpu
 
@@ -125,46 +126,6 @@ def test_join_2_27_rows_skewed_keys_through_the_packed_histogram():
     assert torch.equal(build[ids[p + c - 1].to(torch.int64)], probe[hit])
 
 
-def _fmix32(h):
-    h = h.astype(np.uint64)
-    h ^= h >> 16
-    h = (h * 0x85EBCA6B) & 0xFFFFFFFF
-    h ^= h >> 13
-    h = (h * 0xC2B2AE35) & 0xFFFFFFFF
-    h ^= h >> 16
-    return h
-
-
-def _keys_of_partition(n_build, partition, how_many):
-    """distinct keys that the build of n_build rows puts into one partition (join_lds.hip jl_pid: the high bits of
-    fmix32(key) * parts; parts as join_common.hpp jl_layout has them)"""
-    want = min(max(1, -(-n_build // 2048)), 1 << 20)
-    lg = want.bit_length() - 1  # floor(log2(want))
-    k2 = 1 if want <= 1024 else 1 << (lg // 2)
-    parts = -(-want // k2) * k2
-    cand = np.arange(1, 1 + how_many * parts * 2, dtype=np.uint64)
-    mine = cand[(_fmix32(cand) * parts) >> 32 == partition][:how_many]
-    assert mine.size == how_many
-    return mine.astype(np.uint32)
-
-
-def _check_grouped_join(build, probe):
-    """counts per probe row against numpy; ids a permutation of the build rows in which every key's rows are ONE run;
-    every hit's range starts and ends inside its key's run (with the count right, the range IS the run)"""
-    from dwarf_bench_amd import ops
-    plan = ops.HashJoin(len(build), len(probe))
-    plan.build(_dev(build))
-    plan.probe(_dev(probe))
-    pos, cnt, ids = (t.cpu().numpy().view(np.uint32) for t in plan.result())
-    assert np.array_equal(cnt.astype(np.uint64), po.join_counts_fast(build, probe))
-    assert np.array_equal(np.sort(ids), np.arange(len(build), dtype=np.uint32))
-    in_order = build[ids]
-    assert np.count_nonzero(in_order[1:] != in_order[:-1]) + 1 == np.unique(build).size
-    hit = cnt > 0
-    assert np.array_equal(in_order[pos[hit]], probe[hit])
-    assert np.array_equal(in_order[pos[hit] + cnt[hit] - 1], probe[hit])
-
-
 @pytest.mark.parametrize("n", [(1 << 18) + 5, 1 << 22])  # one and two scatter levels
 @pytest.mark.parametrize("kind", ["every row one key", "every other row one key", "three hot keys",
                                   "1500 keys of one partition, 40 rows each", "two giants and 1200 keys of a third"])
@@ -184,15 +145,15 @@ def test_join_build_with_giant_partitions(kind, n):
         build[(r >= 0.3) & (r < 0.6)] = 4000000000
         build[(r >= 0.6) & (r < 0.9)] = 99
     elif kind == "1500 keys of one partition, 40 rows each":  # (the partition's own ~1300 distinct keys come on top)
-        build[: 1500 * 40] = np.repeat(_keys_of_partition(n, 3, 1500), 40)
+        build[: 1500 * 40] = np.repeat(keys_of_partition(n, 3, 1500), 40)
         build = rng.permutation(build)
     else:
-        build[: 1200 * 30] = np.repeat(_keys_of_partition(n, 0, 1200), 30)
+        build[: 1200 * 30] = np.repeat(keys_of_partition(n, 0, 1200), 30)
         build[100000:150000] = 31
         build[150000:230000:2] = 32
         build = rng.permutation(build)
     probe[::7] = build[rng.integers(0, n, probe[::7].size)]  # probe rows that hit, hot keys among them
-    _check_grouped_join(build, probe)
+    check_grouped_join(build, probe)
 
 
 def test_many_giant_partitions_of_many_slices_each_count_exactly():
@@ -211,7 +172,7 @@ def test_many_giant_partitions_of_many_slices_each_count_exactly():
         at += c
     build = rng.permutation(build)
     probe = np.concatenate([hot, po.gen_uniform_u32(1 << 16, 43, 0, n - 1)]).astype(np.uint32)
-    _check_grouped_join(build, probe)
+    check_grouped_join(build, probe)
     # and through the radix join (the giants' scratch sub-tables)
     from dwarf_bench_amd import ops
     rid, pos, cnt, ids = (t.cpu().numpy().view(np.uint32) for t in ops.radix_join(_dev(build), _dev(probe)))
@@ -230,43 +191,20 @@ def test_the_no_giants_escape_hatch_still_joins_everything():
     import os, subprocess, sys
     prog = (
         "import numpy as np, torch\n"
-        "import tests.test_gpu_join as t\n"
+        "import tests.join_testlib as t\n"
         "from oracle import pyoracle as po\n"
         "rng = np.random.default_rng(3)\n"
         "n = 1 << 18\n"
         "b = po.gen_uniform_u32(n, 42, 0, n - 1); b[::2] = 777\n"
         "p = po.gen_uniform_u32(1 << 16, 43, 0, n - 1); p[::5] = 777\n"
-        "t._check_grouped_join(b, p)\n"
-        "b = po.gen_uniform_u32(n, 42, 0, n - 1); mine = t._keys_of_partition(n, 1, 3500)\n"
+        "t.check_grouped_join(b, p)\n"
+        "b = po.gen_uniform_u32(n, 42, 0, n - 1); mine = t.keys_of_partition(n, 1, 3500)\n"
         "b[: 3500 * 20] = np.repeat(mine, 20); b = rng.permutation(b); p[::3] = mine[rng.integers(0, 3500, p[::3].size)]\n"
-        "t._check_grouped_join(b, p)\n"
+        "t.check_grouped_join(b, p)\n"
         "print('no giants ok')\n")
     r = subprocess.run([sys.executable, "-c", prog], capture_output=True, text=True, timeout=600,
                        env={**os.environ, "DBHIP_JL_NO_GIANTS": "1"}, cwd=os.path.dirname(os.path.dirname(__file__)))
     assert r.returncode == 0 and "no giants ok" in r.stdout, (r.stdout[-2000:], r.stderr[-3000:])
-
-
-def _keys_of_partition_of(parts, partition, how_many):
-    cand = np.arange(1, 1 + how_many * parts * 2, dtype=np.uint64)
-    mine = cand[(_fmix32(cand) * parts) >> 32 == partition][:how_many]
-    assert mine.size == how_many
-    return mine.astype(np.uint32)
-
-
-def _radix_parts(n_build):
-    """partitions of the radix join (join_common.hpp jl_layout with kJrRowsPerPart = 1792 rows per partition)"""
-    want = min(max(1, -(-n_build // 1792)), 1 << 20)
-    lg = (want - 1).bit_length()
-    if want <= 1024:
-        k2 = 1
-    else:
-        lgs = lg - 1 if (1 << lg) != want else lg
-        k2 = 1 << (lgs // 2)
-    k1 = -(-want // k2)
-    while k1 > 1024:
-        k2 *= 2
-        k1 = -(-want // k2)
-    return k1 * k2
 
 
 SPILL_SHAPES = [  # (build rows, distinct keys put into ONE partition, rows per key): more keys than the 3072 slots of a sub-table
@@ -289,13 +227,13 @@ def test_a_partition_with_more_distinct_keys_than_slots_joins_like_any_other(n, 
     from dwarf_bench_amd import ops
     rng = np.random.default_rng(31)
     build = po.gen_uniform_u32(n, 42, 0, n - 1)
-    mine = _keys_of_partition(n, 1, keys)
+    mine = keys_of_partition(n, 1, keys)
     build[: keys * per_key] = np.repeat(mine, per_key)
     build = rng.permutation(build)
     probe = po.gen_uniform_u32(1 << 16, 43, 0, n - 1)
     probe[::3] = mine[rng.integers(0, keys, probe[::3].size)]          # hits in the spilled partition
-    probe[1::11] = _keys_of_partition(n, 1, keys + 500)[keys:][rng.integers(0, 500, probe[1::11].size)]  # and misses there
-    _check_grouped_join(build, probe)
+    probe[1::11] = keys_of_partition(n, 1, keys + 500)[keys:][rng.integers(0, 500, probe[1::11].size)]  # and misses there
+    check_grouped_join(build, probe)
     plan = ops.HashJoin(n, 16)
     plan.build(_dev(build))
     plan.probe(_dev(build[:16]))
@@ -309,9 +247,9 @@ def test_a_partition_with_more_distinct_keys_than_slots_joins_like_any_other(n, 
 def test_radix_join_of_a_partition_with_more_distinct_keys_than_slots(n, keys, per_key):
     from dwarf_bench_amd import ops
     rng = np.random.default_rng(37)
-    parts = _radix_parts(n)
+    parts = radix_parts(n)
     ha = po.gen_uniform_u32(n, 42, 0, n - 1)
-    mine = _keys_of_partition_of(parts, parts // 3, keys + 300)
+    mine = keys_of_partition_of(parts, parts // 3, keys + 300)
     ha[: keys * per_key] = np.repeat(mine[:keys], per_key)
     ha = rng.permutation(ha)
     npr = (1 << 17) + 77
@@ -395,7 +333,7 @@ def test_ujoin_of_a_partition_with_more_keys_than_slots(n, crowd):
     misses inside the spilled partition and elsewhere."""
     from dwarf_bench_amd import ops
     rng = np.random.default_rng(43)
-    mine = _keys_of_partition(n, 2, crowd + 400)
+    mine = keys_of_partition(n, 2, crowd + 400)
     rest = np.setdiff1d(po.gen_unique_sorted_u32(n, 11), mine)[: n - crowd]
     ak = np.concatenate([mine[:crowd], rest]).astype(np.uint32)
     assert np.unique(ak).size == n
