@@ -55,6 +55,12 @@ SIGNATURES = {
     "dbhip_cuckoo_table_insert_u32": (_int, [_vp, _vp, _sz, _vp, _sz, _sz, _int, _u32, _u32, _u32, _int, _vp, _vp]),
     "dbhip_cuckoo_table_lookup_u32": (_int, [_vp, _sz, _vp, _sz, _int, _u32, _u32, _vp, _vp, _vp]),
     "dbhip_cuckoo_table_export_u32": (_int, [_vp, _sz, _vp, _vp, _vp]),
+    "dbhip_slab_table_workspace_bytes": (_sz, [_sz, _sz]),
+    "dbhip_slab_table_reset": (_int, [_vp, _sz, _sz, _sz, _vp]),
+    "dbhip_slab_table_insert_u32": (_int, [_vp, _vp, _sz, _vp, _sz, _sz, _sz, _u64, _u64, _u64, _int, _vp, _vp]),
+    "dbhip_slab_table_lookup_u32": (_int, [_vp, _sz, _vp, _sz, _sz, _u64, _u64, _u64, _vp, _vp, _vp]),
+    "dbhip_slab_table_join_probe_u32": (_int, [_vp, _vp, _sz, _vp, _sz, _sz, _u64, _u64, _u64, _vp, _vp, _vp, _vp]),
+    "dbhip_slab_table_export_u32": (_int, [_vp, _sz, _sz, _vp, _vp, _vp, _vp, _vp]),
     "dbhip_pjoin_partition_workspace_bytes": (_sz, [_sz, _u32]),
     "dbhip_pjoin_partition_u32": (_int, [_vp, _sz, _u64, _u32, _vp, _vp, _vp, _vp, _sz, _vp]),
     "dbhip_gather_u32": (_int, [_vp, _vp, _sz, _vp, _vp]),

@@ -167,6 +167,9 @@ void populate_registry();  // register_dwarfs.cpp:20-56: here it registers the .
 // the reference's EXPERIMENTAL block (register_dwarfs.cpp:41-47, CMakeLists.txt ENABLE_EXPERIMENTAL): the dwarfs only the
 // dwarf_bench_experimental CLI registers, after populate_registry()
 void populate_experimental_registry();
+// the reference's slab dwarfs (register_dwarfs.cpp:44-46, inside its EXPERIMENTAL block): only the dwarf_bench_slab CLI
+// registers them, after populate_registry()
+void populate_slab_registry();
 
 namespace helpers {
 // $DWARF_BENCH_ROOT or the executable's directory (common/common.cpp:38-41, without Boost.DLL)

@@ -1009,6 +1009,241 @@ void CuckooHashBuildHip::run(const RunOptions &opts) {
 void CuckooHashBuildHip::init(const RunOptions &opts) { common_init(*this, opts); }
 
 // =====================================================================================================
+// The slab dwarfs (hash/slab_hash_build.cpp, probe/slab_probe.cpp, join/slab_join.cpp) over the lock-free slab table
+// of csrc/slab.hip.  Sizing: calculate_buckets_count(n, 60) = n / 20 buckets (at least 1: the reference takes % 0
+// below 20 rows) and a pool of as many nodes, the reference's 2 * buckets heap with the roots preallocated, plus
+// DBHIP_SLAB_INSERT_GROUPS nodes: the reference appends under a lock and wastes no node, while a lock-free append can
+// leave one unlinked node per row group, and on SlabHashBuild's hot chains below about 2^22 rows those spares alone
+// would exhaust a pool of `buckets` nodes (measured at 2^16 rows).  Hasher:
+// DefaultHasher<242792921, 653019598, 2147483647>.  The table is reset (the reference builds its AllocAdapter) before
+// host_start, untimed.  A build that reports DBHIP_DEV_TABLE_FULL is "Incorrect results".
+namespace {
+constexpr uint64_t kSlabA = 242792921, kSlabB = 653019598, kSlabP = 2147483647;
+constexpr uint64_t kSlabUniformSeed = 21;
+size_t slab_buckets(size_t n) { return std::max<size_t>(1, n / 20); }
+size_t slab_pool(size_t n) { return slab_buckets(n) + DBHIP_SLAB_INSERT_GROUPS; }
+
+// the status word of a finished build: true = every row stored; throws on anything but TABLE_FULL
+bool slab_built(const void *ws, const char *who) {
+  uint32_t st = 0xFFFFFFFFu;
+  db_ok(dbhip_workspace_status(ws, &st, nullptr), "dbhip_workspace_status");
+  if (st != DBHIP_DEV_OK && st != DBHIP_DEV_TABLE_FULL) fail(std::string(who) + ": device status " + std::to_string(st));
+  if (st == DBHIP_DEV_TABLE_FULL) std::cerr << who << ": the slab pool ran out, rows were not stored\n";
+  return st == DBHIP_DEV_OK;
+}
+
+// every key found (found = n ones) with value == key: vals against the generator itself (uniform keys) or against the
+// sorted keys' fingerprint (unique sorted keys); host comparison up to DWARF_BENCH_VALIDATE_MAX
+bool slab_found_own_keys(const DevBuf<uint32_t> &keys, const DevBuf<uint32_t> &vals, const DevBuf<uint32_t> &found,
+                         size_t n, bool uniform_keys, const std::array<uint64_t, 4> &key_fp, CheckWords &chk) {
+  if (n <= validate_limit()) {
+    const auto hf = found.to_host(n);
+    return std::all_of(hf.begin(), hf.end(), [](uint32_t f) { return f == 1u; }) && vals.to_host(n) == keys.to_host(n);
+  }
+  db_ok(dbhip_check_sorted_u32(found.get(), n, 0, chk.dev(), nullptr), "dbhip_check_sorted_u32");
+  const auto g = chk.get();
+  bool ok = g[0] == 0 && g[2] == n;  // non-decreasing 0/1 entries summing to n: all ones
+  if (uniform_keys) {
+    db_ok(dbhip_check_gen_uniform_u32(vals.get(), nullptr, n, kSlabUniformSeed, 0, 1, 10000, chk.dev(), nullptr),
+          "dbhip_check_gen_uniform_u32");
+    return ok && chk.get()[0] == 0;
+  }
+  db_ok(dbhip_check_sorted_u32(vals.get(), n, 0, chk.dev(), nullptr), "dbhip_check_sorted_u32");
+  const auto v = chk.get();
+  return ok && v[0] == 0 && v[1] == key_fp[1] && v[2] == key_fp[2];
+}
+}  // namespace
+
+// SlabHashBuildHip — hash/slab_hash_build.cpp:9-108: keys = make_random (uniform in [1, 10000], the
+// dbhip_gen_uniform_u32 twin), vals = keys, so every key repeats about n / 10000 times and about 10,000 chains grow
+// n / 320000 slabs long.  Timed: the insert alone (:41-64).  Then every key must be found (:66-99), here also with its
+// own value.
+SlabHashBuildHip::SlabHashBuildHip() : Dwarf("SlabHashBuildHip") {}
+void SlabHashBuildHip::_run(const size_t n, Meter &meter) {
+  const RunOptions &opts = meter.opts();
+  banner("SlabHashBuildHip");
+  const size_t buckets = slab_buckets(n), pool = slab_pool(n);
+  if (buckets + pool > 0xFFFFFFFFull) fail("SlabHashBuildHip: too many rows for 32-bit node ids");
+  DevBuf<uint32_t> keys(n), vals(n), found(n);
+  db_ok(dbhip_gen_uniform_u32(keys.get(), n, kSlabUniformSeed, 0, 1, 10000, nullptr), "gen");
+  const size_t ws_bytes = dbhip_slab_table_workspace_bytes(buckets, pool);
+  DevBuf<unsigned char> ws(ws_bytes);
+  CheckWords chk;
+  Events ev;
+  for (size_t it = 0; it < opts.iterations; ++it) {
+    db_ok(dbhip_slab_table_reset(ws.get(), ws_bytes, buckets, pool, nullptr), "dbhip_slab_table_reset");
+    hip_ok(hipStreamSynchronize(nullptr), "sync");
+    auto result = std::make_unique<Result>();
+    const auto host_start = clk::now();
+    hip_ok(hipEventRecord(ev.a, nullptr), "event");
+    db_ok(dbhip_slab_table_insert_u32(keys.get(), keys.get(), n, ws.get(), ws_bytes, buckets, pool, kSlabA, kSlabB,
+                                      kSlabP, 0, nullptr, nullptr),
+          "dbhip_slab_table_insert_u32");
+    hip_ok(hipEventRecord(ev.b, nullptr), "event");
+    hip_ok(hipStreamSynchronize(nullptr), "sync");
+    const auto host_end = clk::now();
+    result->host_time = host_end - host_start;
+    result->kernel_time = ev.elapsed();
+    bool ok = slab_built(ws.get(), "SlabHashBuildHip");
+    if (ok && n) {
+      db_ok(dbhip_slab_table_lookup_u32(keys.get(), n, ws.get(), buckets, pool, kSlabA, kSlabB, kSlabP, vals.get(),
+                                        found.get(), nullptr),
+            "dbhip_slab_table_lookup_u32");
+      hip_ok(hipStreamSynchronize(nullptr), "sync");
+      if (inject_fault()) poke_xor(vals.get() + n / 2, 1u);
+      ok = slab_found_own_keys(keys, vals, found, n, true, {}, chk);
+    }
+    if (!ok) {
+      std::cerr << "Incorrect results" << std::endl;
+      result->valid = false;
+    }
+    meter.add_result(size_param(n), std::move(result));
+  }
+}
+void SlabHashBuildHip::run(const RunOptions &opts) {
+  for (auto size : opts.input_size) _run(size, meter());
+}
+void SlabHashBuildHip::init(const RunOptions &opts) { common_init(*this, opts); }
+
+// SlabProbeHip — probe/slab_probe.cpp:9-107: unique keys (make_unique_random twin), vals = keys, built untimed; timed:
+// the lookups of the same keys, every one of which must be found (:100-103), here also with its own value.
+SlabProbeHip::SlabProbeHip() : Dwarf("SlabProbeHip") {}
+void SlabProbeHip::_run(const size_t n, Meter &meter) {
+  const RunOptions &opts = meter.opts();
+  banner("SlabProbeHip");
+  if (10ull * n > 0xFFFFFFFFull) fail("SlabProbeHip: keys are drawn from [0, 10*n) and must fit 32 bits");
+  const size_t buckets = slab_buckets(n), pool = slab_pool(n);
+  DevBuf<uint32_t> keys(n), vals(n), found(n);
+  db_ok(dbhip_gen_unique_sorted_u32(keys.get(), n, 11, 0, nullptr), "gen");  // slab_probe.cpp:17
+  const size_t ws_bytes = dbhip_slab_table_workspace_bytes(buckets, pool);
+  DevBuf<unsigned char> ws(ws_bytes);
+  CheckWords chk;
+  std::array<uint64_t, 4> key_fp{};
+  if (n > validate_limit()) {
+    db_ok(dbhip_check_sorted_u32(keys.get(), n, 0, chk.dev(), nullptr), "dbhip_check_sorted_u32");
+    key_fp = chk.get();
+  }
+  Events ev;
+  for (size_t it = 0; it < opts.iterations; ++it) {
+    // build: untimed, a fresh table every iteration like the reference's AllocAdapter (:26-62)
+    db_ok(dbhip_slab_table_reset(ws.get(), ws_bytes, buckets, pool, nullptr), "dbhip_slab_table_reset");
+    db_ok(dbhip_slab_table_insert_u32(keys.get(), keys.get(), n, ws.get(), ws_bytes, buckets, pool, kSlabA, kSlabB,
+                                      kSlabP, 0, nullptr, nullptr),
+          "dbhip_slab_table_insert_u32");
+    hip_ok(hipStreamSynchronize(nullptr), "sync");
+    auto result = std::make_unique<Result>();
+    const auto host_start = clk::now();
+    hip_ok(hipEventRecord(ev.a, nullptr), "event");
+    db_ok(dbhip_slab_table_lookup_u32(keys.get(), n, ws.get(), buckets, pool, kSlabA, kSlabB, kSlabP, vals.get(),
+                                      found.get(), nullptr),
+          "dbhip_slab_table_lookup_u32");
+    hip_ok(hipEventRecord(ev.b, nullptr), "event");
+    hip_ok(hipStreamSynchronize(nullptr), "sync");
+    const auto host_end = clk::now();
+    result->host_time = host_end - host_start;
+    result->kernel_time = ev.elapsed();
+    bool ok = slab_built(ws.get(), "SlabProbeHip");
+    if (ok && n) {
+      if (inject_fault()) poke_xor(vals.get() + n / 2, 1u);
+      ok = slab_found_own_keys(keys, vals, found, n, false, key_fp, chk);
+    }
+    if (!ok) {
+      std::cerr << "Incorrect results" << std::endl;
+      result->valid = false;
+    }
+    meter.add_result(size_param(n), std::move(result));
+  }
+}
+void SlabProbeHip::run(const RunOptions &opts) {
+  for (auto size : opts.input_size) _run(size, meter());
+}
+void SlabProbeHip::init(const RunOptions &opts) { common_init(*this, opts); }
+
+// SlabJoinHip — join/slab_join.cpp:10-144: unique sorted keys and unique sorted values on both sides (the
+// make_unique_random twin, the seeds of JoinHip), build and probe timed separately (HashJoinResult).  The reference
+// fixes 1024 buckets, a 20000-node heap and the hasher <32, 48, 1031> (:37-39, :72, :100): its heap holds 640,000
+// pairs and it writes past it beyond that, and at 2^24 rows its chains would be about 512 slabs long.  Here the table
+// is sized like SlabHashBuild's (n / 20 buckets, a pool of as many nodes + DBHIP_SLAB_INSERT_GROUPS) with its hasher.  The probe writes per probe row
+// (key, build value, probe value), all 0xFFFFFFFF on a miss (dbhip_ujoin_probe_u32's convention): the reference
+// compacts by key != 0 (:127) and drops a real key 0.  Checked like JoinHip, against seq_join's table.
+SlabJoinHip::SlabJoinHip() : Dwarf("SlabJoinHip") {}
+void SlabJoinHip::_run(const size_t n, Meter &meter) {
+  const RunOptions &opts = meter.opts();
+  banner("SlabJoinHip");
+  if (10ull * n > 0xFFFFFFFFull) fail("SlabJoinHip: keys are drawn from [0, 10*n) and must fit 32 bits");
+  const size_t buckets = slab_buckets(n), pool = slab_pool(n);
+  DevBuf<uint32_t> ak(n), av(n), bk(n), bv(n), ok_(n), o1(n), o2(n);
+  const size_t ws_bytes = dbhip_slab_table_workspace_bytes(buckets, pool);
+  DevBuf<unsigned char> ws(ws_bytes);
+  db_ok(dbhip_gen_unique_sorted_u32(ak.get(), n, 11, 0, nullptr), "gen");
+  db_ok(dbhip_gen_unique_sorted_u32(av.get(), n, 12, 0, nullptr), "gen");
+  db_ok(dbhip_gen_unique_sorted_u32(bk.get(), n, 13, 0, nullptr), "gen");
+  db_ok(dbhip_gen_unique_sorted_u32(bv.get(), n, 14, 0, nullptr), "gen");
+  hip_ok(hipDeviceSynchronize(), "sync");
+  const bool host_check = n <= validate_limit();
+  std::unordered_map<uint32_t, uint32_t> a_payload;
+  std::vector<uint32_t> hbk, hbv;
+  CheckWords chk;
+  if (host_check) {
+    const auto hak = ak.to_host(n), hav = av.to_host(n);
+    hbk = bk.to_host(n);
+    hbv = bv.to_host(n);
+    for (size_t i = 0; i < n; ++i) a_payload.emplace(hak[i], hav[i]);
+  }
+  Events build_ev, probe_ev;
+  for (size_t it = 0; it < opts.iterations; ++it) {
+    db_ok(dbhip_slab_table_reset(ws.get(), ws_bytes, buckets, pool, nullptr), "dbhip_slab_table_reset");
+    hip_ok(hipStreamSynchronize(nullptr), "sync");
+    auto result = std::make_unique<HashJoinResult>();
+    const auto host_start = clk::now();
+    hip_ok(hipEventRecord(build_ev.a, nullptr), "event");
+    db_ok(dbhip_slab_table_insert_u32(ak.get(), av.get(), n, ws.get(), ws_bytes, buckets, pool, kSlabA, kSlabB, kSlabP,
+                                      0, nullptr, nullptr),
+          "dbhip_slab_table_insert_u32");
+    hip_ok(hipEventRecord(build_ev.b, nullptr), "event");
+    hip_ok(hipStreamSynchronize(nullptr), "sync");
+    const auto build_end = clk::now();
+    hip_ok(hipEventRecord(probe_ev.a, nullptr), "event");
+    db_ok(dbhip_slab_table_join_probe_u32(bk.get(), bv.get(), n, ws.get(), buckets, pool, kSlabA, kSlabB, kSlabP,
+                                          ok_.get(), o1.get(), o2.get(), nullptr),
+          "dbhip_slab_table_join_probe_u32");
+    hip_ok(hipEventRecord(probe_ev.b, nullptr), "event");
+    hip_ok(hipStreamSynchronize(nullptr), "sync");
+    const auto host_end = clk::now();
+    result->host_time = host_end - host_start;
+    result->build_time = build_end - host_start;
+    result->probe_time = host_end - build_end;
+    result->kernel_time = build_ev.elapsed() + probe_ev.elapsed();
+    bool ok = slab_built(ws.get(), "SlabJoinHip");
+    if (inject_fault() && n) poke_xor(o1.get() + n / 2, 1u);
+    if (ok && host_check) {
+      const auto hk = ok_.to_host(n), h1 = o1.to_host(n), h2 = o2.to_host(n);
+      for (size_t i = 0; i < n && ok; ++i) {
+        const auto f = a_payload.find(hbk[i]);
+        if (f == a_payload.end())
+          ok = hk[i] == 0xFFFFFFFFu && h1[i] == 0xFFFFFFFFu && h2[i] == 0xFFFFFFFFu;
+        else
+          ok = hk[i] == hbk[i] && h1[i] == f->second && h2[i] == hbv[i];
+      }
+    } else if (ok) {  // the build keys are generated ascending and unique: binary search finds every probe row's partner
+      db_ok(dbhip_check_ujoin_u32(ak.get(), av.get(), n, bk.get(), bv.get(), n, ok_.get(), o1.get(), o2.get(), chk.dev(),
+                                  nullptr),
+            "dbhip_check_ujoin_u32");
+      ok = chk.get()[0] == 0;
+    }
+    if (!ok) {
+      std::cerr << "Incorrect results" << std::endl;
+      result->valid = false;
+    }
+    meter.add_result(size_param(n), std::move(result));
+  }
+}
+void SlabJoinHip::run(const RunOptions &opts) {
+  for (auto size : opts.input_size) _run(size, meter());
+}
+void SlabJoinHip::init(const RunOptions &opts) { common_init(*this, opts); }
+
+// =====================================================================================================
 // PartitionedJoinHip — the radix-partitioned hash join of SURVEY 8(e) behind the Dwarf hook: one process driving
 // `--gpus P` ranks through pjoin::Engine (pjoin_engine.hpp: per-rank compute and exchange streams, counts by
 // ncclAllGather, exchange of R overlapping partition S, exchange of S overlapping build R).  No reference

@@ -37,5 +37,9 @@ DBHIP_DECLARE_DWARF(ReduceHip);               // reduce/reduce.cpp:27-98 (int su
 DBHIP_DECLARE_DWARF(NestedLoopJoinHip);       // join/nested_join.cpp:10-110 (dense cell matrix, small n)
 // the reference's EXPERIMENTAL block: registered by populate_experimental_registry() only
 DBHIP_DECLARE_DWARF(CuckooHashBuildHip);      // hash/cuckoo_hash_build.cpp:8-134 (lock-free cuckoo table, rebuild on failure)
+// the reference's EXPERIMENTAL slab dwarfs: registered by populate_slab_registry() only (the dwarf_bench_slab CLI)
+DBHIP_DECLARE_DWARF(SlabHashBuildHip);        // hash/slab_hash_build.cpp:9-108 (lock-free slab table, insert timed)
+DBHIP_DECLARE_DWARF(SlabProbeHip);            // probe/slab_probe.cpp:9-107 (slab table built untimed, lookups timed)
+DBHIP_DECLARE_DWARF(SlabJoinHip);             // join/slab_join.cpp:10-144 (build and probe timed separately)
 
 #undef DBHIP_DECLARE_DWARF

@@ -4,7 +4,8 @@
 //               [--report_path FILE] [--groups_count G] [--executors E] [--gpus P] [--help]
 // Exit codes as in the reference: 1 for an unknown dwarf, 0 otherwise — also after a caught exception.
 // Built twice: `dwarf_bench`, and with -DEXPERIMENTAL `dwarf_bench_experimental`, which also registers the reference's
-// EXPERIMENTAL dwarfs that have a HIP counterpart (populate_experimental_registry).
+// EXPERIMENTAL dwarfs that have a HIP counterpart (populate_experimental_registry), and with -DEXPERIMENTAL_SLAB
+// `dwarf_bench_slab`, the default set plus the slab dwarfs (populate_slab_registry).
 #include <iostream>
 #include <memory>
 #include <sstream>
@@ -36,6 +37,9 @@ int main(int argc, char *argv[]) {
   populate_registry();
 #ifdef EXPERIMENTAL
   populate_experimental_registry();  // dwarf_bench_experimental
+#endif
+#ifdef EXPERIMENTAL_SLAB
+  populate_slab_registry();  // dwarf_bench_slab
 #endif
   Registry *registry = Registry::instance();
 

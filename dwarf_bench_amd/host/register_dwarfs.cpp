@@ -35,3 +35,14 @@ void populate_experimental_registry() {
   registry->registerd(new CuckooHashBuildHip());  // hash/cuckoo_hash_build.cpp (register_dwarfs.cpp:44 in the reference)
 #endif
 }
+
+// the reference's SlabHashBuild, SlabJoin and SlabProbe (register_dwarfs.cpp:44-46): only the dwarf_bench_slab CLI (main.cpp
+// built with -DEXPERIMENTAL_SLAB) calls this, so the lists of dwarf_bench and dwarf_bench_experimental stay as they are
+void populate_slab_registry() {
+#ifdef HIP_ENABLED
+  Registry *registry = Registry::instance();
+  registry->registerd(new SlabHashBuildHip());  // hash/slab_hash_build.cpp
+  registry->registerd(new SlabJoinHip());       // join/slab_join.cpp
+  registry->registerd(new SlabProbeHip());      // probe/slab_probe.cpp
+#endif
+}

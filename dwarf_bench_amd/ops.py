@@ -544,6 +544,124 @@ def cuckoo_build(keys: torch.Tensor, vals: torch.Tensor, table_size: int | None 
 
 
 # ---------------------------------------------------------------------------------------------
+# slab table (SlabHashTable counterpart, common/dpcpp/slab_hash.hpp)
+# ---------------------------------------------------------------------------------------------
+SLAB_HASHER_BUILD = (242792921, 653019598, 2147483647)  # DefaultHasher of SlabHashBuild / SlabProbe
+SLAB_HASHER_JOIN = (32, 48, 1031)                       # join/slab_join.cpp:72, :100
+SLAB_HASHER_TESTS = (13, 24, 343)                       # tests/slab_tests.cpp
+SLAB_MAX_GROUPS = 1 << 14  # DBHIP_SLAB_INSERT_GROUPS: the most pool nodes one concurrent insert leaves unlinked
+
+
+def slab_buckets(n: int) -> int:
+    """calculate_buckets_count(n, 60) = n / (32 * 0.625) = n // 20 (slab_hash.hpp:30-58), but at least 1: the reference
+    takes % 0 below 20 rows"""
+    return max(1, n // 20)
+
+
+class SlabTable:
+    """Slab hash table: `buckets` chains of 32-slot slabs, nodes [buckets, buckets + pool_nodes) the overflow pool.
+    hasher = (A, B, P): bucket = ((A*k + B) % P) % buckets.  A multimap; insert() is asynchronous, status() / failed()
+    synchronise.  A concurrent insert may leave one pool node per group unlinked: a pool of ceil(rows / 32) +
+    SLAB_MAX_GROUPS nodes holds any input."""
+
+    def __init__(self, buckets: int, pool_nodes: int, hasher=SLAB_HASHER_BUILD, device="cuda"):
+        self.buckets, self.pool = int(buckets), int(pool_nodes)
+        self.hasher = tuple(int(x) for x in hasher)
+        self.ws_bytes = _capi.lib().dbhip_slab_table_workspace_bytes(self.buckets, self.pool)
+        if self.ws_bytes == 0:
+            raise ValueError(f"SlabTable: bad geometry ({buckets} buckets, {pool_nodes} pool nodes)")
+        self.ws = _ws(self.ws_bytes, device)
+        self.reset()
+
+    @property
+    def nodes(self) -> int:
+        return self.buckets + self.pool
+
+    def reset(self) -> None:
+        """empty every slab, unlink every node, clear the pool cursor and the status word"""
+        _capi.check(_capi.lib().dbhip_slab_table_reset(self.ws.data_ptr(), self.ws_bytes, self.buckets, self.pool,
+                                                       _stream()), "slab_table_reset")
+
+    def insert(self, keys: torch.Tensor, vals: torch.Tensor, serial: bool = False, want_results: bool = False):
+        """insert (keys[i], vals[i]); serial: one group in input order (the reference's sequential layout).
+        want_results: returns an int32 tensor, 1 where the row was stored."""
+        _need(keys, torch.int32, "keys")
+        _need(vals, torch.int32, "vals")
+        n = keys.numel()
+        if vals.numel() != n:
+            raise ValueError("keys and vals differ in length")
+        res = torch.empty(max(n, 1), dtype=torch.int32, device=keys.device) if want_results else None
+        a, b, p = self.hasher
+        _capi.check(_capi.lib().dbhip_slab_table_insert_u32(
+            keys.data_ptr(), vals.data_ptr(), n, self.ws.data_ptr(), self.ws_bytes, self.buckets, self.pool, a, b, p,
+            int(serial), res.data_ptr() if want_results else None, _stream()), "slab_table_insert")
+        return res[:n] if want_results else None
+
+    def status(self) -> int:
+        """the device status word since the last reset (synchronises): DEV_TABLE_FULL, DEV_KEY_RANGE, DEV_SPIN_TIMEOUT"""
+        return workspace_status(self.ws)
+
+    def failed(self) -> bool:
+        """True if a row since the last reset was not stored for want of pool nodes"""
+        return bool(self.status() & DEV_TABLE_FULL)
+
+    def lookup(self, keys: torch.Tensor):
+        """(vals, found): the value of the first slot in chain order holding each key (0 when missing) and 1 / 0"""
+        _need(keys, torch.int32, "keys")
+        n = keys.numel()
+        vals = torch.empty(max(n, 1), dtype=torch.int32, device=keys.device)
+        found = torch.empty(max(n, 1), dtype=torch.int32, device=keys.device)
+        a, b, p = self.hasher
+        _capi.check(_capi.lib().dbhip_slab_table_lookup_u32(keys.data_ptr(), n, self.ws.data_ptr(), self.buckets,
+                                                            self.pool, a, b, p, vals.data_ptr(), found.data_ptr(),
+                                                            _stream()), "slab_table_lookup")
+        return vals[:n], found[:n]
+
+    def join_probe(self, keys: torch.Tensor, vals: torch.Tensor):
+        """(key, build value, probe value) per probe row, all -1 (0xFFFFFFFF) on a miss"""
+        _need(keys, torch.int32, "keys")
+        _need(vals, torch.int32, "vals")
+        n = keys.numel()
+        if vals.numel() != n:
+            raise ValueError("keys and vals differ in length")
+        out = torch.empty((3, max(n, 1)), dtype=torch.int32, device=keys.device)
+        a, b, p = self.hasher
+        _capi.check(_capi.lib().dbhip_slab_table_join_probe_u32(
+            keys.data_ptr(), vals.data_ptr(), n, self.ws.data_ptr(), self.buckets, self.pool, a, b, p,
+            out[0].data_ptr(), out[1].data_ptr(), out[2].data_ptr(), _stream()), "slab_table_join_probe")
+        return out[0, :n], out[1, :n], out[2, :n]
+
+    def slabs(self):
+        """(keys [nodes, 32], vals [nodes, 32], next [nodes], pool_used): the layout; an empty slot is (-1, 0), a
+        missing link -1"""
+        dev = self.ws.device
+        keys = torch.empty((self.nodes, 32), dtype=torch.int32, device=dev)
+        vals = torch.empty((self.nodes, 32), dtype=torch.int32, device=dev)
+        nxt = torch.empty(self.nodes, dtype=torch.int32, device=dev)
+        used = torch.empty(1, dtype=torch.int32, device=dev)
+        _capi.check(_capi.lib().dbhip_slab_table_export_u32(self.ws.data_ptr(), self.buckets, self.pool,
+                                                            keys.data_ptr(), vals.data_ptr(), nxt.data_ptr(),
+                                                            used.data_ptr(), _stream()), "slab_table_export")
+        return keys, vals, nxt, int(used.cpu()[0])
+
+
+def slab_join(build_keys: torch.Tensor, build_vals: torch.Tensor, probe_keys: torch.Tensor,
+              probe_vals: torch.Tensor, hasher=SLAB_HASHER_BUILD):
+    """SlabJoin (join/slab_join.cpp:10-144): build a slab table over (build_keys, build_vals), probe it with every probe
+    row, and return (keys, build_vals, probe_vals) of the hit rows in probe-row order.  A probe key that occurs more than
+    once in the build side meets the first of its rows in chain order (find()).  Key 0 is a key like any other; key
+    0xFFFFFFFF (-1) cannot be stored.  Sized by slab_buckets with a pool that holds any input, not the reference's fixed
+    1024 buckets and 20000-node heap."""
+    n = build_keys.numel()
+    table = SlabTable(slab_buckets(n), -(-n // 32) + SLAB_MAX_GROUPS, hasher, device=build_keys.device)
+    table.insert(build_keys, build_vals)
+    _check_status(table.ws, "slab_join build")
+    k, bv, pv = table.join_probe(probe_keys, probe_vals)
+    hit = k != -1
+    return k[hit], bv[hit], pv[hit]
+
+
+# ---------------------------------------------------------------------------------------------
 # exclusive prefix sum (scan/scan.cl:44-66, tests/scan_tests.cpp:14-21, dpl_wrapper.hpp:18-25)
 # ---------------------------------------------------------------------------------------------
 class ExclusiveScan:

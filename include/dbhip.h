@@ -31,6 +31,8 @@
  *                             join/join.cpp:30-38, tests/hash_table_tests.cpp
  *   dbhip_cuckoo_table_*      common/dpcpp/cuckoo_hashtable.hpp (CuckooHashtable) <- hash/cuckoo_hash_build.cpp:8-120,
  *                             tests/cuckoo_hashtable_tests.cpp
+ *   dbhip_slab_table_*        common/dpcpp/slab_hash.hpp (SlabHashTable) <- hash/slab_hash_build.cpp:8-112,
+ *                             probe/slab_probe.cpp, join/slab_join.cpp:10-144, tests/slab_tests.cpp
  *   dbhip_reduce_sum_i32      reduce/reduce.cpp:27-88
  *   dbhip_nested_join_u32     join/nested_join.cpp:52-66
  *   dbhip_pjoin_*             no reference counterpart (multi-GPU radix-partitioned join)
@@ -60,13 +62,15 @@ extern "C" {
 /* device-side status word values (dbhip_workspace_status) */
 #define DBHIP_DEV_OK 0u
 #define DBHIP_DEV_SPIN_TIMEOUT 1u  /* dbhip_copy_if_lt_dense_i32 and the single-launch path of dbhip_exclusive_scan_u32:
-                                      a chunk waited 2 s for its predecessors (never seen); the output is then wrong */
+                                      a chunk waited 2 s for its predecessors (never seen); the output is then wrong;
+                                      the slab table: an insert reached a loop bound (a workspace that was not reset) */
 #define DBHIP_DEV_KEY_RANGE 2u     /* group key >= groups_count, or the 0xFFFFFFFF sentinel as a join build key */
 #define DBHIP_DEV_TABLE_FULL 4u    /* open-addressing table wrapped without finding a slot: the bitmask-claimed table (a
                                       table that really is full: the reference spins forever there) and the small-input
                                       unique-key table; the cuckoo table: an insert's eviction chain reached max_iter
                                       exchanges and the pair it carried was dropped (a normal result: rebuild with other
-                                      seeds).  NOT the LDS-partitioned joins (dbhip_join_build* / _radix_* /
+                                      seeds); the slab table: its overflow pool ran out and the row was not
+                                      stored.  NOT the LDS-partitioned joins (dbhip_join_build* / _radix_* /
                                       dbhip_ujoin_* from 2^16 rows): a partition with more distinct keys than its 3072-slot
                                       LDS sub-table holds is built in a spill table of its own, any keys join (the one
                                       exception: a one-to-many build of exactly 2^31 rows has no spare bit to mark such a
@@ -284,6 +288,52 @@ int dbhip_cuckoo_table_lookup_u32(const uint32_t *keys, size_t n, const void *wo
                                   uint32_t *out_found, dbhip_stream_t stream);
 int dbhip_cuckoo_table_export_u32(const void *workspace, size_t table_size, uint32_t *out_keys,
                                   uint32_t *out_vals, dbhip_stream_t stream);
+
+/* ---- slab table: HIP counterpart of SlabHashTable (common/dpcpp/slab_hash.hpp), the table of the reference's
+ * SlabHashBuild, SlabProbe and SlabJoin dwarfs.  A multimap: bucket = ((A*k + B) % P) % buckets, computed exactly as
+ * DefaultHasher<A, B, P> does in 64 bits (:60-64; A, B <= 2^32 - 1, 1 <= P <= 2^32 - 1); each bucket heads a chain of
+ * slabs of 32 (key, value) slots (SLAB_SIZE, :20-22), node b being bucket b's root slab and nodes
+ * [buckets, buckets + pool_nodes) the overflow pool (the reference's heap, :84-99, with its end checked); buckets >= 1,
+ * buckets + pool_nodes <= 2^32 - 1.  Workspace: header (status word, pool cursor) | vals[nodes][32] | keys[nodes][32] |
+ * 8-byte link words[nodes]; empty = key 0xFFFFFFFF, value 0.
+ *   reset   clears the status word and the pool cursor, empties every slab and unlinks every node.
+ *   insert  lock-free (the reference appends slabs under a spin lock, :209-222): each row goes into the first empty slot
+ *           of the first slab of its chain that has one (:224-262), a duplicate key into a slot of its own; a full
+ *           chain gets a pool node linked at its end with one CAS.  Pool exhausted: the row is NOT stored and
+ *           DBHIP_DEV_TABLE_FULL is ORed into the status word (the reference writes past its heap, :92-97).  Key
+ *           0xFFFFFFFF is not stored (DBHIP_DEV_KEY_RANGE).  Every loop is bounded (a chain walk by buckets + pool_nodes
+ *           steps, a slab by 32 CASes); DBHIP_DEV_SPIN_TIMEOUT: a bound was reached or a link pointed outside the
+ *           table (a workspace that was not reset), the row is not stored.  out_inserted (nullable) gets 1 / 0 per row.
+ *           serial != 0 inserts with ONE group in input order: the slot, slab and chain layout of a sequential run of
+ *           the reference's algorithm.  A concurrent insert may leave one pool node unlinked per row group (a group
+ *           that loses the race to link a node keeps it for its next append; pool_used counts it), at most
+ *           DBHIP_SLAB_INSERT_GROUPS in all.
+ *   lookup  after an insert call has finished: out_vals[i] = the value of the first slot, in chain and slot order,
+ *           that holds keys[i] (find(), :177-196, :264-294), or 0; out_found[i] = 1 / 0.
+ *   join_probe  SlabJoin's probe (join/slab_join.cpp:88-111) in dbhip_ujoin_probe_u32's convention: for probe row i
+ *           out_key[i] = the key, out_build_val[i] = lookup's value, out_probe_val[i] = probe_vals[i] on a hit, and all
+ *           three 0xFFFFFFFF on a miss (the reference marks a miss with key 0 and loses a real key 0, :127).
+ *   export  out_keys / out_vals[node * 32 + slot], out_next[node] (0xFFFFFFFF: none), *out_pool_used = pool nodes
+ *           taken (at most pool_nodes): the layout, for tests and callers.                                          */
+#define DBHIP_SLAB_INSERT_GROUPS 16384 /* most row groups of one concurrent insert call: it leaves at most this many
+                                         pool nodes unlinked, so a pool of (overflow slabs needed) + this never runs out */
+size_t dbhip_slab_table_workspace_bytes(size_t buckets, size_t pool_nodes);
+int dbhip_slab_table_reset(void *workspace, size_t workspace_bytes, size_t buckets, size_t pool_nodes,
+                           dbhip_stream_t stream);
+int dbhip_slab_table_insert_u32(const uint32_t *keys, const uint32_t *vals, size_t n, void *workspace,
+                                size_t workspace_bytes, size_t buckets, size_t pool_nodes, uint64_t hash_a,
+                                uint64_t hash_b, uint64_t hash_p, int serial, uint32_t *out_inserted /* nullable */,
+                                dbhip_stream_t stream);
+int dbhip_slab_table_lookup_u32(const uint32_t *keys, size_t n, const void *workspace, size_t buckets,
+                                size_t pool_nodes, uint64_t hash_a, uint64_t hash_b, uint64_t hash_p,
+                                uint32_t *out_vals, uint32_t *out_found, dbhip_stream_t stream);
+int dbhip_slab_table_join_probe_u32(const uint32_t *probe_keys, const uint32_t *probe_vals, size_t n,
+                                    const void *workspace, size_t buckets, size_t pool_nodes, uint64_t hash_a,
+                                    uint64_t hash_b, uint64_t hash_p, uint32_t *out_key, uint32_t *out_build_val,
+                                    uint32_t *out_probe_val, dbhip_stream_t stream);
+int dbhip_slab_table_export_u32(const void *workspace, size_t buckets, size_t pool_nodes, uint32_t *out_keys,
+                                uint32_t *out_vals, uint32_t *out_next, uint32_t *out_pool_used,
+                                dbhip_stream_t stream);
 
 /* ---- multi-GPU radix-partitioned join: device pieces (no reference counterpart) ---------
  * Partition a local column shard into `parts` (1..1024) destination buckets by a mixed hash of

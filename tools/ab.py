@@ -22,6 +22,10 @@ the contract numbers come from bench.py.
   reduce          2^28-row reduce (median of 15; DBHIP_RED_WGS)
   cuckoo [lg]     cuckoo table (hash_kind 2) at 2^lg unique keys in 4 * 2^lg slots (default lg 24): reset, insert, lookups of present
                   and of absent keys (median of 9), each checked against torch
+  slab [lg]       slab table at 2^lg rows (default lg 24), the dwarfs' n / 20 buckets and n / 20 + 16384 pool nodes: reset, insert of unique keys,
+                  of SlabHashBuild's keys in [1, 10000] and of 2^(lg-8) rows of one key, lookups of present and absent keys
+                  (median of 9), each with the tail hint on and off (DBHIP_SLAB_HINT) and the first CAS at the lowest or at a
+                  spread empty slot (DBHIP_SLAB_SPREAD 0 / default / 1); every build checked
   xscan [lg]      exclusive scan of 2^lg uint32, aligned (one launch) and offset by one element (three launches)
   graph           direct launches vs hipGraph replay of sort and join at 2^14..2^20 rows (host wall clock)
   launch-join [lg] / launch-sort [lg] / launch-all
@@ -595,6 +599,45 @@ def cuckoo(lg):
           f"({n / la / 1e3:6.2f} G/s) | {'ok' if ok else 'WRONG'}", flush=True)
 
 
+def slab(lg):
+    lg = lg or 24
+    n = 1 << lg
+    uniq = ops.gen_unique_sorted_u32(n, 11)
+    absent = bits32(u64(uniq) - u64(uniq) % 10 + (u64(uniq) % 10 + 1) % 10)  # same decade, another digit: never generated
+    ref = ops.gen_uniform_u32(n, 21, 1, 10000)
+    one = torch.full((n >> 8,), 77, dtype=torch.int32, device="cuda")
+    cases = [("unique", uniq, None), ("keys 1..10000", ref, None), ("one key", one, (n >> 8) // 32 + ops.SLAB_MAX_GROUPS)]
+    for hint, spread in (("1", ""), ("0", ""), ("1", "0"), ("1", "1")):
+        os.environ["DBHIP_SLAB_HINT"], os.environ["DBHIP_SLAB_SPREAD"] = hint, spread
+        for name, keys, pool in cases:
+            m = keys.numel()
+            b = ops.slab_buckets(m)
+            t = ops.SlabTable(b, pool if pool is not None else b + ops.SLAB_MAX_GROUPS)
+            r = median(times(t.reset, 9))
+
+            def build():
+                t.reset()
+                t.insert(keys, keys)
+
+            bt = median(times(build, 9))
+            vals, found = t.lookup(keys)
+            ok = t.status() == ops.DEV_OK and bool((found == 1).all()) and torch.equal(vals, keys)
+            line = (f"{TAG:12s} hint={hint} spread={spread} {name:14s} {m:9d} rows: reset {r:8.1f} us, insert {bt - r:9.1f} us "
+                    f"({m / max(bt - r, 1e-3) / 1e3:6.2f} G rows/s)")
+            if keys is uniq:
+                lp = median(times(lambda: t.lookup(uniq), 9))
+                av, af = t.lookup(absent)
+                ok = ok and not bool(af.any()) and not bool(av.any())
+                la = median(times(lambda: t.lookup(absent), 9))
+                line += f" | lookup present {lp:8.1f} us ({m / lp / 1e3:6.2f} G/s), absent {la:8.1f} us ({m / la / 1e3:6.2f} G/s)"
+            elif keys is ref:
+                lr = median(times(lambda: t.lookup(ref), 9))
+                line += f" | lookup {lr:8.1f} us"
+            print(line + f" | {'ok' if ok else 'WRONG'}", flush=True)
+    os.environ.pop("DBHIP_SLAB_HINT")
+    os.environ.pop("DBHIP_SLAB_SPREAD")
+
+
 def xscan(lg):
     lg = lg or 28
     n = 1 << lg
@@ -712,7 +755,7 @@ def launch_all(_):
 
 
 MODES = {"radix": radix, "ramp": ramp, "radix-idle": radix_idle, "radix-stream": radix_stream, "radix-alloc": radix_alloc, "radix-offsets": radix_offsets, "radix-sizes": radix_sizes, "graph": graph, "launch-join": launch_join, "launch-sort": launch_sort, "launch-all": launch_all, "scan": scan, "sort": sort, "sort-only": sort_only, "groupby": groupby, "groupby-shapes": groupby_shapes, "groupby-skew": groupby_skew, "sort-shapes": sort_shapes, "join": join, "join-skew": join_skew, "size-sweep": size_sweep, "partition": partition,
-         "reduce": reduce, "xscan": xscan, "cuckoo": cuckoo}
+         "reduce": reduce, "xscan": xscan, "cuckoo": cuckoo, "slab": slab}
 
 if __name__ == "__main__":
     if len(sys.argv) < 2 or sys.argv[1] not in MODES:
