@@ -34,6 +34,8 @@ SIGNATURES = {
     "dbhip_groupby_sum_u32": (_int, [_vp, _vp, _sz, _u32, _vp, _vp, _sz, _vp]),
     "dbhip_groupby_partial_u32": (_int, [_vp, _vp, _sz, _u32, _u32, _vp, _sz, _vp]),
     "dbhip_groupby_merge_u32": (_int, [_u32, _u32, _vp, _vp, _vp]),
+    "dbhip_groupby_hash_workspace_bytes": (_sz, [_sz, _u32]),
+    "dbhip_groupby_hash_u32": (_int, [_vp, _vp, _sz, _u32, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "dbhip_join_workspace_bytes": (_sz, [_sz]),
     "dbhip_join_build_u32": (_int, [_vp, _sz, _vp, _vp, _sz, _vp]),
     "dbhip_join_build_pairs_u32": (_int, [_vp, _vp, _sz, _vp, _vp, _sz, _vp]),
@@ -77,6 +79,8 @@ SIGNATURES = {
     "dbhip_check_permutation_u32": (_int, [_vp, _sz, _vp, _vp, _sz, _vp]),
     "dbhip_check_join_u32": (_int, [_vp, _sz, _vp, _sz, _vp, _vp, _vp, _vp, _u64, _u32, _u32, _vp, _vp]),
     "dbhip_check_ujoin_u32": (_int, [_vp, _vp, _sz, _vp, _vp, _sz, _vp, _vp, _vp, _vp, _vp]),
+    "dbhip_check_distinct_workspace_bytes": (_sz, [_sz]),
+    "dbhip_check_distinct_u32": (_int, [_vp, _sz, _vp, _vp, _sz, _vp]),
     "dbhip_check_gen_uniform_u32": (_int, [_vp, _vp, _sz, _u64, _u64, _u32, _u32, _vp, _vp]),
 }
 

@@ -18,6 +18,9 @@
 //                                    pseudo-random id carry the key.
 //   dbhip_check_ujoin_u32            per probe row of the unique-key join: (key, build payload, probe payload) or
 //                                    the three sentinels, the build side found by binary search.
+//   dbhip_check_distinct_u32         number of i with s[i] >= s[i+1] over a copy s of the keys sorted by
+//                                    dbhip_radix_sort_u32 (whose own checks watch the sort): 0 iff the keys are distinct
+//                                    (a group-by output with one key emitted twice has it).
 //   dbhip_check_gen_uniform_u32      values[i] == lo + mix64(seed, index_i) % span: a column (or a received
 //                                    (key, row id) pair of the partitioned join) is what the generator produced.
 // All results are uint64 words in DEVICE memory, zeroed by the call itself.
@@ -162,6 +165,17 @@ __global__ __launch_bounds__(kCkThreads) void weighted_sum_kernel(const unsigned
     if (a0) atomicAdd(reinterpret_cast<unsigned *>(result + 0), a0);
     if (a1) atomicAdd(reinterpret_cast<unsigned *>(result + 1), a1);
   }
+}
+
+// ---- distinct keys (group-by output) ------------------------------------------------------------------------------
+// over a sorted column: number of i with key[i] >= key[i+1]
+__global__ __launch_bounds__(kCkThreads) void not_increasing_kernel(const unsigned *__restrict__ keys, size_t n,
+                                                                    unsigned long long *result) {
+  const size_t stride = static_cast<size_t>(gridDim.x) * kCkThreads;
+  unsigned long long bad = 0;
+  for (size_t i = static_cast<size_t>(blockIdx.x) * kCkThreads + threadIdx.x; i + 1 < n; i += stride)
+    bad += keys[i] >= keys[i + 1] ? 1u : 0u;
+  block_add_u64(bad, result);
 }
 
 // ---- permutation ---------------------------------------------------------------------------------------------------
@@ -406,6 +420,34 @@ extern "C" int dbhip_check_ujoin_u32(const uint32_t *sorted_build_keys, const ui
   if (n_probe == 0) return DBHIP_OK;
   hipLaunchKernelGGL(ujoin_check_kernel, dim3(ck_grid(n_probe, dev)), dim3(kCkThreads), 0, s, sorted_build_keys,
                      build_vals, n_build, probe_keys, probe_vals, n_probe, out_key, out_build_val, out_probe_val,
+                     reinterpret_cast<unsigned long long *>(result));
+  return launch_status();
+}
+
+// workspace: sorted copy | ping-pong buffer | the sort's own workspace
+extern "C" size_t dbhip_check_distinct_workspace_bytes(size_t n) {
+  const size_t col = align_up((n ? n : 1) * sizeof(unsigned), kWsAlign);
+  return 2 * col + dbhip_radix_sort_workspace_bytes(n, 8);
+}
+
+extern "C" int dbhip_check_distinct_u32(const uint32_t *keys, size_t n, uint64_t *result, void *workspace,
+                                        size_t workspace_bytes, dbhip_stream_t stream) {
+  if (!result || (n && !keys)) return DBHIP_EINVAL;
+  if (!ws_ok(workspace, workspace_bytes, dbhip_check_distinct_workspace_bytes(n))) return DBHIP_EWORKSPACE;
+  const DeviceInfo &dev = current_device_info();
+  if (!dev.ok) return DBHIP_ENODEVICE;
+  hipStream_t s = as_stream(stream);
+  hipError_t e = fill_async(result, 0, sizeof(uint64_t), s);
+  if (e != hipSuccess) return static_cast<int>(e);
+  if (n < 2) return DBHIP_OK;
+  const size_t col = align_up(n * sizeof(unsigned), kWsAlign);
+  unsigned *copy = static_cast<unsigned *>(workspace);
+  unsigned *tmp = reinterpret_cast<unsigned *>(static_cast<char *>(workspace) + col);
+  e = hipMemcpyAsync(copy, keys, n * sizeof(unsigned), hipMemcpyDeviceToDevice, s);
+  if (e != hipSuccess) return static_cast<int>(e);
+  const int rc = dbhip_radix_sort_u32(copy, tmp, n, 8, static_cast<char *>(workspace) + 2 * col, workspace_bytes - 2 * col, stream);
+  if (rc != 0) return rc;
+  hipLaunchKernelGGL(not_increasing_kernel, dim3(ck_grid(n, dev)), dim3(kCkThreads), 0, s, copy, n,
                      reinterpret_cast<unsigned long long *>(result));
   return launch_status();
 }

@@ -163,6 +163,15 @@ inline JlLayout jl_layout(size_t n, size_t rows_per_part = kJlRowsPerPart) {
   return L;
 }
 
+// The partition step of every join (join_lds.hip), also the group-by's (groupby_hash.hip): the (key, row id) pairs of a
+// column of n rows hash-partitioned into `parts` partitions of the geometry (parts, k1, k2, log2_k2) of jl_layout; level-0
+// output in rows_a, level-1 output (k2 > 1) in rows_b, offsets in `meta` (meta_bytes).  *out_pairs: the partition-major
+// pairs, *out_starts: parts + 1 offsets into them.  row_ids == nullptr: the row index.  Any key, 0xFFFFFFFF included, is
+// carried like any other.
+int jl_partition_side(const unsigned *keys, const unsigned *row_ids, size_t n, unsigned parts, unsigned k1, unsigned k2,
+                      unsigned log2_k2, u32x2 *rows_a, u32x2 *rows_b, unsigned long long *meta, size_t meta_bytes,
+                      hipStream_t s, const DeviceInfo &dev, const unsigned **out_pairs,
+                      const unsigned long long **out_starts);
 int join_lds_build(const unsigned *build_keys, const unsigned *row_ids, size_t n, unsigned *ids, void *workspace,
                    hipStream_t s, const DeviceInfo &dev);
 size_t jl_partition_workspace_bytes(unsigned parts);

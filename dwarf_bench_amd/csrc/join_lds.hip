@@ -2032,6 +2032,7 @@ struct JlPartitioned {
   u32x2 *table;
   unsigned *status;
 };
+}  // namespace
 
 // The one or two scatter levels shared by all joins, for a column of n rows and a partition geometry that may come
 // from ANOTHER column (the radix join partitions the probe side by the build side's geometry): level-0 output in
@@ -2133,6 +2134,7 @@ int jl_partition_side(const unsigned *keys, const unsigned *row_ids, size_t n, u
   return launch_status();
 }
 
+namespace {
 // the build side of the one-to-many / unique-key joins, laid out by jl_layout(n): fills `out`
 int jl_partition_rows(const unsigned *build_keys, const unsigned *row_ids, size_t n, void *workspace, hipStream_t s,
                       const DeviceInfo &dev, const JlLayout &L, JlPartitioned *out) {

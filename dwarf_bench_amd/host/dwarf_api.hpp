@@ -170,6 +170,8 @@ void populate_experimental_registry();
 // the reference's slab dwarfs (register_dwarfs.cpp:44-46, inside its EXPERIMENTAL block): only the dwarf_bench_slab CLI
 // registers them, after populate_registry()
 void populate_slab_registry();
+// GroupByHashHip: only the dwarf_bench_groupby_hash CLI registers it, after populate_registry()
+void populate_groupby_hash_registry();
 
 namespace helpers {
 // $DWARF_BENCH_ROOT or the executable's directory (common/common.cpp:38-41, without Boost.DLL)

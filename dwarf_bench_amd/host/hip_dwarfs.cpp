@@ -1355,3 +1355,72 @@ void PartitionedJoinHip::run(const RunOptions &opts) {
   for (auto size : opts.input_size) _run(size, meter());
 }
 void PartitionedJoinHip::init(const RunOptions &opts) { common_init(*this, opts); }
+
+// =====================================================================================================
+// GroupByHashHip — GROUP BY key SUM(val), COUNT(*) over sparse keys (dbhip_groupby_hash_u32): vals uniform in [1, 10000]
+// as GroupByHip's, keys = the low 32 bits of mix64 of a uniform draw from [0, groups_count) — groups_count values (a few
+// fewer where two draws mix to one word) spread over the whole uint32 range.  max_groups = groups_count.  Result::valid
+// from the device validators: distinct output keys, the weighted sums of (out_keys, out_sums) and of (out_keys,
+// out_counts) equal those of (keys, vals) and of (keys, ones), and the counts sum to n.
+GroupByHashHip::GroupByHashHip() : Dwarf("GroupByHashHip") {}
+void GroupByHashHip::_run(const size_t n, Meter &meter) {
+  const auto &opts = static_cast<const GroupByRunOptions &>(meter.opts());
+  banner("GroupByHashHip");
+  if (n > (static_cast<size_t>(1) << 31)) fail("GroupByHashHip: at most 2^31 rows");
+  const uint32_t groups = static_cast<uint32_t>(opts.groups_count ? opts.groups_count : 1);
+  const size_t cap = std::max<size_t>(std::min<size_t>(groups, n), 1);
+  DevBuf<uint32_t> keys(n), vals(n), ones(n), draw(n), out_keys(cap), out_sums(cap), out_counts(cap);
+  DevBuf<uint64_t> out_groups(1);
+  const size_t ws_bytes = dbhip_groupby_hash_workspace_bytes(n, groups);
+  DevBuf<unsigned char> ws(ws_bytes);
+  const size_t dws_bytes = dbhip_check_distinct_workspace_bytes(cap);
+  DevBuf<unsigned char> dws(dws_bytes);
+  db_ok(dbhip_gen_uniform_u32(vals.get(), n, 43, 0, 1, 10000, nullptr), "gen vals");
+  db_ok(dbhip_gen_uniform_u32(draw.get(), n, 42, 0, 0, groups - 1, nullptr), "gen draw");
+  db_ok(dbhip_gen_uniform_at_u32(keys.get(), draw.get(), n, 44, 0, 0xFFFFFFFFu, nullptr), "gen keys");
+  db_ok(dbhip_gen_uniform_u32(ones.get(), n, 0, 0, 1, 1, nullptr), "gen ones");
+  CheckWords chk;
+  db_ok(dbhip_check_weighted_sum_u32(keys.get(), vals.get(), n, chk.dev(), nullptr), "dbhip_check_weighted_sum_u32");
+  const auto want_sums = chk.get();
+  db_ok(dbhip_check_weighted_sum_u32(keys.get(), ones.get(), n, chk.dev(), nullptr), "dbhip_check_weighted_sum_u32");
+  const auto want_counts = chk.get();
+  Events ev;
+  for (size_t it = 0; it < opts.iterations; ++it) {
+    auto result = std::make_unique<Result>();
+    const auto host_start = clk::now();
+    hip_ok(hipEventRecord(ev.a, nullptr), "event");
+    db_ok(dbhip_groupby_hash_u32(keys.get(), vals.get(), n, groups, out_keys.get(), out_sums.get(), out_counts.get(),
+                                 out_groups.get(), ws.get(), ws_bytes, nullptr),
+          "dbhip_groupby_hash_u32");
+    hip_ok(hipEventRecord(ev.b, nullptr), "event");
+    hip_ok(hipStreamSynchronize(nullptr), "sync");
+    const auto host_end = clk::now();
+    result->host_time = host_end - host_start;
+    result->kernel_time = ev.elapsed();
+    check_status(ws.get(), "GroupByHashHip");
+    const size_t g = static_cast<size_t>(out_groups.to_host(1)[0]);
+    if (inject_fault() && g) poke_xor(out_sums.get() + g / 2, 1u);
+    bool ok = g <= cap;
+    if (ok) {
+      db_ok(dbhip_check_weighted_sum_u32(out_keys.get(), out_sums.get(), g, chk.dev(), nullptr), "dbhip_check_weighted_sum_u32");
+      const auto s = chk.get();
+      db_ok(dbhip_check_weighted_sum_u32(out_keys.get(), out_counts.get(), g, chk.dev(), nullptr), "dbhip_check_weighted_sum_u32");
+      const auto c = chk.get();
+      db_ok(dbhip_check_distinct_u32(out_keys.get(), g, chk.dev(), dws.get(), dws_bytes, nullptr), "dbhip_check_distinct_u32");
+      const auto d = chk.get();
+      uint64_t total = 0;  // the counts sum to n: summed on the host (g words, at most groups_count)
+      for (uint32_t x : out_counts.to_host(g)) total += x;
+      ok = s[0] == want_sums[0] && s[1] == want_sums[1] && c[0] == want_counts[0] && c[1] == want_counts[1] && d[0] == 0 &&
+           total == n;
+    }
+    if (!ok) {
+      std::cerr << "Incorrect results" << std::endl;
+      result->valid = false;
+    }
+    meter.add_result(size_param(n), std::move(result));
+  }
+}
+void GroupByHashHip::run(const RunOptions &opts) {
+  for (auto size : opts.input_size) _run(size, meter());
+}
+void GroupByHashHip::init(const RunOptions &opts) { common_init(*this, opts); }

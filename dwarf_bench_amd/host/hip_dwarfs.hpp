@@ -41,5 +41,8 @@ DBHIP_DECLARE_DWARF(CuckooHashBuildHip);      // hash/cuckoo_hash_build.cpp:8-13
 DBHIP_DECLARE_DWARF(SlabHashBuildHip);        // hash/slab_hash_build.cpp:9-108 (lock-free slab table, insert timed)
 DBHIP_DECLARE_DWARF(SlabProbeHip);            // probe/slab_probe.cpp:9-107 (slab table built untimed, lookups timed)
 DBHIP_DECLARE_DWARF(SlabJoinHip);             // join/slab_join.cpp:10-144 (build and probe timed separately)
+// group-by on arbitrary 32-bit keys (SUM and COUNT): registered by populate_groupby_hash_registry() only (the
+// dwarf_bench_groupby_hash CLI)
+DBHIP_DECLARE_DWARF(GroupByHashHip);          // groupby/groupby.cpp:58-93 (the hash table keyed by the group key)
 
 #undef DBHIP_DECLARE_DWARF

@@ -5,7 +5,8 @@
 // Exit codes as in the reference: 1 for an unknown dwarf, 0 otherwise — also after a caught exception.
 // Built twice: `dwarf_bench`, and with -DEXPERIMENTAL `dwarf_bench_experimental`, which also registers the reference's
 // EXPERIMENTAL dwarfs that have a HIP counterpart (populate_experimental_registry), and with -DEXPERIMENTAL_SLAB
-// `dwarf_bench_slab`, the default set plus the slab dwarfs (populate_slab_registry).
+// `dwarf_bench_slab`, the default set plus the slab dwarfs (populate_slab_registry), and with -DEXPERIMENTAL_GROUPBY_HASH
+// `dwarf_bench_groupby_hash`, the default set plus GroupByHashHip (populate_groupby_hash_registry).
 #include <iostream>
 #include <memory>
 #include <sstream>
@@ -40,6 +41,9 @@ int main(int argc, char *argv[]) {
 #endif
 #ifdef EXPERIMENTAL_SLAB
   populate_slab_registry();  // dwarf_bench_slab
+#endif
+#ifdef EXPERIMENTAL_GROUPBY_HASH
+  populate_groupby_hash_registry();  // dwarf_bench_groupby_hash
 #endif
   Registry *registry = Registry::instance();
 

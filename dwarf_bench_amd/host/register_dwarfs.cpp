@@ -46,3 +46,11 @@ void populate_slab_registry() {
   registry->registerd(new SlabProbeHip());      // probe/slab_probe.cpp
 #endif
 }
+
+// the general group-by (dbhip_groupby_hash_u32): only the dwarf_bench_groupby_hash CLI (main.cpp built with
+// -DEXPERIMENTAL_GROUPBY_HASH) calls this, so the lists of the other three CLIs stay as they are
+void populate_groupby_hash_registry() {
+#ifdef HIP_ENABLED
+  Registry::instance()->registerd(new GroupByHashHip());
+#endif
+}

@@ -212,6 +212,56 @@ def groupby_sum(keys: torch.Tensor, vals: torch.Tensor, groups: int) -> torch.Te
     return plan.result()
 
 
+class GroupByHash:
+    """Reusable plan for GROUP BY key SUM(val), COUNT(*) over arbitrary 32-bit keys (dbhip_groupby_hash_u32): owns the
+    workspace and the three output columns for n rows and a bound on the distinct keys (max_groups, 0 = n)."""
+
+    def __init__(self, n: int, max_groups: int = 0, device="cuda"):
+        if not 0 <= max_groups < 1 << 32:
+            raise ValueError("max_groups must fit 32 bits")
+        self.n, self.max_groups = n, max_groups
+        self.ws_bytes = _capi.lib().dbhip_groupby_hash_workspace_bytes(n, max_groups)
+        if self.ws_bytes == 0:
+            raise ValueError(f"n = {n} is above the group-by's 2^31 rows")
+        self.ws = _ws(self.ws_bytes, device)
+        cap = max(max_groups if max_groups else n, 1)
+        self.keys = torch.empty(cap, dtype=torch.int32, device=device)
+        self.sums = torch.empty(cap, dtype=torch.int32, device=device)
+        self.counts = torch.empty(cap, dtype=torch.int32, device=device)
+        self.groups = torch.zeros(1, dtype=torch.int64, device=device)
+        self._counted = True
+
+    def launch(self, keys: torch.Tensor, vals: torch.Tensor, counts: bool = True) -> None:
+        """Asynchronous on the current stream; nothing is read back (graph-capturable)."""
+        _need(keys, torch.int32, "keys")
+        _need(vals, torch.int32, "vals")
+        _need16(keys, "keys")
+        _need16(vals, "vals")
+        if keys.numel() != self.n or vals.numel() != self.n:
+            raise ValueError("size mismatch")
+        self._counted = counts
+        _capi.check(_capi.lib().dbhip_groupby_hash_u32(keys.data_ptr(), vals.data_ptr(), self.n, self.max_groups,
+                                                       self.keys.data_ptr(), self.sums.data_ptr(),
+                                                       self.counts.data_ptr() if counts else None, self.groups.data_ptr(),
+                                                       self.ws.data_ptr(), self.ws_bytes, _stream()), "groupby_hash_u32")
+
+    def result(self):
+        """-> (keys, sums, counts or None), cut to the number of groups; raises on a device status (more distinct keys
+        than max_groups: DBHIP_DEV_TABLE_FULL)."""
+        _check_status(self.ws, "groupby_hash_u32")
+        g = int(self.groups.item())
+        return self.keys[:g], self.sums[:g], (self.counts[:g] if self._counted else None)
+
+
+def groupby_hash(keys: torch.Tensor, vals: torch.Tensor, max_groups: int | None = None, counts: bool = True):
+    """GROUP BY keys: -> (distinct keys, SUM(vals), COUNT(*) or None), rows in no particular order, int32 tensors holding
+    uint32 bits.  max_groups: a bound on the number of distinct keys (None: n, always correct; a small bound selects the
+    faster LDS path)."""
+    plan = GroupByHash(keys.numel(), max_groups or 0, keys.device)
+    plan.launch(keys, vals, counts=counts)
+    return plan.result()
+
+
 # ---------------------------------------------------------------------------------------------
 # dwarf 4a: one-to-many hash join (JoinOmnisci semantics)
 # ---------------------------------------------------------------------------------------------
@@ -738,6 +788,18 @@ def check_weighted_sum(keys: torch.Tensor | None, vals: torch.Tensor):
     _capi.check(_capi.lib().dbhip_check_weighted_sum_u32(keys.data_ptr() if keys is not None else None, vals.data_ptr(),
                                                          vals.numel(), res.data_ptr(), _stream()), "check_weighted_sum_u32")
     return tuple(_u64(res))
+
+
+def check_distinct(keys: torch.Tensor) -> int:
+    """-> number of i with s[i] >= s[i+1] over a sorted copy s of keys (0 iff the keys are distinct)"""
+    _need(keys, torch.int32, "keys")
+    lib = _capi.lib()
+    ws_bytes = lib.dbhip_check_distinct_workspace_bytes(keys.numel())
+    ws = _ws(ws_bytes, keys.device)
+    res = _result(1, keys.device)
+    _capi.check(lib.dbhip_check_distinct_u32(keys.data_ptr(), keys.numel(), res.data_ptr(), ws.data_ptr(), ws_bytes,
+                                             _stream()), "check_distinct_u32")
+    return _u64(res)[0]
 
 
 def check_permutation(ids: torch.Tensor) -> int:

@@ -27,6 +27,7 @@
  *   dbhip_ujoin_*             join/join.cpp:60-104, common/dpcpp/hashtable.hpp:5-93,
  *                             common/dpcpp/hashfunctions.hpp:64-137 (MurmurHash3_x86_32)
  *   dbhip_groupby_partial/merge_u32  groupby/groupby_local.cpp:52-112 (the two timed phases of GroupByLocal)
+ *   dbhip_groupby_hash_u32    groupby/groupby.cpp:58-93 (GroupBy's open-addressing table keyed by the group key)
  *   dbhip_bitmask_table_*     common/dpcpp/hashtable.hpp:5-93 (SimpleNonOwningHashTable) <- hash/hash_build.cpp:8-98,
  *                             join/join.cpp:30-38, tests/hash_table_tests.cpp
  *   dbhip_cuckoo_table_*      common/dpcpp/cuckoo_hashtable.hpp (CuckooHashtable) <- hash/cuckoo_hash_build.cpp:8-120,
@@ -168,6 +169,30 @@ int dbhip_groupby_partial_u32(const uint32_t *keys, const uint32_t *vals, size_t
                               dbhip_stream_t stream);
 int dbhip_groupby_merge_u32(uint32_t groups, uint32_t max_private_tables, uint32_t *out, const void *workspace,
                             dbhip_stream_t stream);
+
+/* ---- dwarf 3b: group-by on arbitrary 32-bit keys, SUM and COUNT (hash aggregation) -------------------------------
+ * One output row per distinct key k of keys[0..n): out_keys[i] = k, out_sums[i] = the sum of its vals (uint32
+ * wrap-around), out_counts[i] = its number of rows; *out_groups (a DEVICE uint64, like copy_if's out_size) = the number of
+ * rows written.  The order of the rows is unspecified.  out_counts may be NULL: no counting.  Every key value is a key,
+ * 0xFFFFFFFF included (the tables' empty marker: those rows are summed on the side, never lost, never flagged).
+ * max_groups is the caller's bound on the number of distinct keys and the capacity of the three output arrays; 0 = n.
+ * More distinct keys than max_groups: DBHIP_DEV_TABLE_FULL in the workspace status word, nothing written past max_groups
+ * entries, *out_groups = max_groups; every probe loop is bounded (no fault, no hang).  keys and vals must be 16-byte aligned
+ * (DBHIP_EINVAL otherwise); n <= 2^31; NULL pointers (out_counts aside) and n > 2^31 are DBHIP_EINVAL, a small workspace
+ * DBHIP_EWORKSPACE, all before any HIP call.  n = 0 gives *out_groups = 0.  Never synchronises, never allocates; repeated
+ * calls on one workspace give the same multiset of rows whatever the workspace held before.
+ * The path is chosen on the host from max_groups alone (min(max_groups, n) distinct keys at most):
+ *   <= 4096: private LDS tables per workgroup, one global insert per (workgroup, group) at the end;
+ *   more:    the radix join's hash partitioning of the (key, val) pairs, then one workgroup per ~2048-row partition
+ *            aggregates it in LDS and writes its groups out (hot keys: the partition is sliced over many workgroups).
+ * So a caller who knows the number of keys is small should pass it: max_groups = n is always correct, and slower.
+ * Workspace: a global table of 2 * min(max_groups, n) slots (at least 64) of key | sum | count, 24 bytes per group of the
+ * bound, and for the partitioned path 16 bytes per row of pair buffers plus the partition offsets (~1 MiB): at most
+ * 65 bytes per row plus 2 MiB.  DBHIP_GBH_PATH=lds|part|global pins a path (read once; global = every row into the table in HBM).   */
+size_t dbhip_groupby_hash_workspace_bytes(size_t n, uint32_t max_groups);
+int dbhip_groupby_hash_u32(const uint32_t *keys, const uint32_t *vals, size_t n, uint32_t max_groups, uint32_t *out_keys,
+                           uint32_t *out_sums, uint32_t *out_counts, uint64_t *out_groups, void *workspace,
+                           size_t workspace_bytes, dbhip_stream_t stream);
 
 /* ---- dwarf 4a: one-to-many hash join (JoinOmnisci semantics) -----------------------------------
  * Build: hash table over the DISTINCT build keys, per-key match count, exclusive scan -> position,
@@ -401,7 +426,12 @@ int dbhip_exclusive_scan_u32(const uint32_t *src, size_t n, uint32_t init, uint3
  *                       result[0] = probe rows whose (key, build payload, probe payload) triple or sentinels are
  *                       wrong, result[1] = number of hits.
  *   gen_uniform_u32     result[0] = number of i with values[i] != lo + mix64(seed, index_i) % (hi - lo + 1),
- *                       index_i = indices ? indices[i] : first_index + i.                              */
+ *                       index_i = indices ? indices[i] : first_index + i.
+ *   distinct_u32        result[0] = number of i with s[i] >= s[i+1] over a sorted copy s of keys (dbhip_radix_sort_u32 in
+ *                       the workspace): 0 iff the keys are distinct.  A group-by output (dbhip_groupby_hash_u32) is right
+ *                       iff its keys are distinct, weighted_sum over (out_keys, out_sums) equals weighted_sum over
+ *                       (keys, vals), the same holds for (out_keys, out_counts) against a column of ones, and the counts
+ *                       sum to n.                                                                        */
 size_t dbhip_check_fingerprint_workspace_bytes(size_t n);
 int dbhip_check_fingerprint_lt_i32(const int32_t *src, size_t n, int32_t filter_value, uint64_t *result,
                                    void *workspace, size_t workspace_bytes, dbhip_stream_t stream);
@@ -420,6 +450,9 @@ int dbhip_check_ujoin_u32(const uint32_t *sorted_build_keys, const uint32_t *bui
                           const uint32_t *probe_keys, const uint32_t *probe_vals, size_t n_probe,
                           const uint32_t *out_key, const uint32_t *out_build_val, const uint32_t *out_probe_val,
                           uint64_t *result, dbhip_stream_t stream);
+size_t dbhip_check_distinct_workspace_bytes(size_t n);
+int dbhip_check_distinct_u32(const uint32_t *keys, size_t n, uint64_t *result, void *workspace, size_t workspace_bytes,
+                             dbhip_stream_t stream);
 int dbhip_check_gen_uniform_u32(const uint32_t *values, const uint32_t *indices, size_t n, uint64_t seed,
                                 uint64_t first_index, uint32_t lo, uint32_t hi, uint64_t *result,
                                 dbhip_stream_t stream);

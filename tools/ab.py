@@ -11,6 +11,9 @@ the contract numbers come from bench.py.
   groupby-shapes  more than 32768 groups over row counts, group counts and value ranges (median of 5): run it with
                   DBHIP_GB_PACKED=0 beside the default to see what the kernel's choice between its two large-table modes
                   buys and that it costs nothing where the packed table would be slow
+  groupby-hash    dbhip_groupby_hash_u32 at 2^24 and 2^26 rows: 1 .. 2^20 and all-distinct sparse keys, half the rows on one
+                  key, and groupby_sum's BASELINE input (2^16 dense groups), beside groupby_sum on the dense draw and the torch
+                  composition unique(return_inverse, return_counts) + scatter_add (median of 7 / 7 / 3)
   groupby-skew    2^26 rows whose keys crowd into one or a few groups, at 64 .. 2^16 groups (median of 5)
   sort-shapes [lg] 2^lg keys of eight distributions (few distinct values, sorted, reversed, skewed ...; median of 5)
   join [lg]       build / probe / radix join of 2^lg x 2^lg (drop-max-mean of 7); default lg 26
@@ -132,6 +135,46 @@ def groupby(_):
         ok = bool(torch.equal(u64(plan.result()), ref & 0xFFFFFFFF))
         res.append(f"G={groups}: {t:6.1f} us {'ok' if ok else 'WRONG'}")
     print(f"{TAG:16s} " + "  ".join(res), flush=True)
+
+
+def groupby_hash(_):
+    """dbhip_groupby_hash_u32 (max_groups = the number of distinct keys) against groupby_sum on the dense draw the keys
+    come from and against torch.unique(return_inverse, return_counts) + scatter_add (median of 7 / 7 / 3)"""
+    def mixed(u):  # a bijective spread of [0, d) over the uint32 range: sparse keys
+        return bits32((u.to(torch.int64) * 2654435761 + 12345) % 2**32)
+
+    def composed(keys, vals):
+        u, inv, cnt = torch.unique(keys, return_inverse=True, return_counts=True)
+        return u, torch.zeros(len(u), dtype=torch.int64, device="cuda").scatter_add_(0, inv, u64(vals)), cnt
+
+    for lg in (24, 26):
+        n = 1 << lg
+        vals = ops.gen_uniform_u32(n, 43, 1, 10000)
+        cases = [(f"d={d}", d) for d in (1, 64, 4096, 1 << 16, 1 << 20) if d <= n] + [("all-distinct", n), ("hot-half", n)]
+        if lg == 26:
+            cases.append(("dense 2^16 (BASELINE)", 1 << 16))
+        for name, d in cases:
+            u = torch.arange(n, dtype=torch.int32, device="cuda") if d == n else ops.gen_uniform_u32(n, 42, 0, d - 1)
+            keys = u if name.startswith("dense") else mixed(u)
+            if name == "hot-half":
+                keys = keys.clone()
+                keys[ops.gen_uniform_u32(n, 7, 0, 1) == 0] = 777
+            plan = ops.GroupByHash(n, d)
+            t = median(times(lambda: plan.launch(keys, vals), 7))
+            k, sm, c = plan.result()
+            ru, rs, rc = composed(keys, vals)
+            o, r = torch.argsort(u64(k)), torch.argsort(u64(ru))  # (torch.unique orders the int32 bits as signed)
+            ok = (torch.equal(u64(k)[o], u64(ru)[r]) and torch.equal(u64(sm)[o], rs[r] & 0xFFFFFFFF)
+                  and torch.equal(c[o].to(torch.int64), rc[r]))
+            tt = median(times(lambda: composed(keys, vals), 3, warm=1))
+            dense = ""
+            if name != "hot-half" and d <= 1 << 20:  # (above, groupby_sum reads every row once per 32768 groups)
+                gplan = ops.GroupBySum(n, d)
+                td = median(times(lambda: gplan.launch(u, vals), 7))
+                dense = f"  groupby_sum(dense draw) {td:8.1f} us"
+            print(f"{TAG:10s} 2^{lg} {name:22s} groupby_hash {t:8.1f} us {'ok' if ok else 'WRONG'}  torch {tt:9.1f} us{dense}",
+                  flush=True)
+            del plan
 
 
 def groupby_shapes(_):
@@ -755,7 +798,8 @@ def launch_all(_):
 
 
 MODES = {"radix": radix, "ramp": ramp, "radix-idle": radix_idle, "radix-stream": radix_stream, "radix-alloc": radix_alloc, "radix-offsets": radix_offsets, "radix-sizes": radix_sizes, "graph": graph, "launch-join": launch_join, "launch-sort": launch_sort, "launch-all": launch_all, "scan": scan, "sort": sort, "sort-only": sort_only, "groupby": groupby, "groupby-shapes": groupby_shapes, "groupby-skew": groupby_skew, "sort-shapes": sort_shapes, "join": join, "join-skew": join_skew, "size-sweep": size_sweep, "partition": partition,
-         "reduce": reduce, "xscan": xscan, "cuckoo": cuckoo, "slab": slab}
+         "reduce": reduce, "xscan": xscan, "cuckoo": cuckoo, "slab": slab,
+         "groupby-hash": groupby_hash}
 
 if __name__ == "__main__":
     if len(sys.argv) < 2 or sys.argv[1] not in MODES:
