@@ -171,3 +171,115 @@ def test_fuzz_partition_and_reduce():
         assert np.all(np.diff(d[r2]) >= 0)  # bucket-major
         src = keys.view(np.int32)
         assert int(ops.reduce_sum(_dev(src)).cpu()[0]) == po.reduce_sum(src), n
+
+
+def _gbh_keys(rng, n, kind):
+    """_keys' distributions plus kind 8: keys on one path-b sub-table home (tests/groupby_hash_testlib.py)"""
+    if kind == 8:
+        from tests.groupby_hash_testlib import SUB_LG, keys_on_home
+        pool = keys_on_home(rng, int(rng.integers(65, 5000)), SUB_LG, int(rng.integers(0, 1 << SUB_LG)))
+        return pool[rng.integers(0, pool.size, n)]
+    return _keys(rng, n, kind)
+
+
+def test_fuzz_groupby_hash():
+    """the hash group-by on seeded sizes and key distributions, bound at, above, below the true distinct count and
+    none, counts on and off: exact keys, sums and counts; below the bound only the status and the bound"""
+    from dwarf_bench_amd import ops
+    from tests.groupby_hash_testlib import expect
+    rng = np.random.default_rng(107)
+    for n in _sizes(rng, 24, 21):
+        keys = _gbh_keys(rng, n, int(rng.integers(0, 9)))
+        vals = po.gen_uniform_u32(n, int(rng.integers(1, 1 << 30)), 0, int(rng.choice([1, 10000, 2**32 - 1])))
+        want = expect(keys, vals)
+        d = want[0].size
+        which = int(rng.integers(0, 4))
+        bound = [d, d + int(rng.integers(1, 5000)), max(1, d - int(rng.integers(1, max(2, d)))), 0][which]
+        counts = bool(rng.integers(0, 2))
+        plan = ops.GroupByHash(n, bound)
+        plan.launch(_dev(keys), _dev(vals), counts=counts)
+        st = ops.workspace_status(plan.ws)
+        if bound and bound < d:
+            assert st & ops.DEV_TABLE_FULL and int(plan.groups.item()) == bound, (n, d, bound)
+            continue
+        assert st == ops.DEV_OK, (n, d, bound, st)
+        k, s, c = plan.result()
+        k = k.cpu().numpy().view(np.uint32)
+        o = np.argsort(k, kind="stable")
+        assert np.array_equal(k[o], want[0]) and np.array_equal(s.cpu().numpy().view(np.uint32)[o], want[1]), (n, d, bound)
+        if counts:
+            assert np.array_equal(c.cpu().numpy().view(np.uint32)[o], want[2]), (n, d, bound)
+
+
+def test_fuzz_cuckoo():
+    """the cuckoo table (hash_kind 2) built through ops.cuckoo_build at load 0.1-0.45 from shuffled full-range unique
+    keys, a second insert into the non-empty table, lookups of present and absent keys against the inserted pairs; duplicate keys
+    against the documented rule (the h1 slot wins)"""
+    from dwarf_bench_amd import ops
+    from tests.cuckoo_model import positions_np
+    rng = np.random.default_rng(108)
+    for n in _sizes(rng, 12, 20)[::2]:
+        size = max(8, int(n / rng.uniform(0.1, 0.45)))
+        keys = rng.choice(2**32 - 1, size=n, replace=False).astype(np.uint32)  # 0xFFFFFFFF is the empty key
+        vals = rng.integers(0, 2**32, size=n, dtype=np.uint64).astype(np.uint32)
+        half = n // 2
+        table, _ = ops.cuckoo_build(_dev(keys[:half]), _dev(vals[:half]), table_size=size, seed=int(rng.integers(0, 1000)))
+        table.insert(_dev(keys[half:]), _dev(vals[half:]))
+        if table.status() != ops.DEV_OK:  # a second insert may fail legitimately: rebuild the whole set instead
+            assert table.status() == ops.DEV_TABLE_FULL
+            table, _ = ops.cuckoo_build(_dev(keys), _dev(vals), table_size=size)
+        q = np.concatenate([keys, rng.integers(0, 2**32 - 1, size=n + 7, dtype=np.uint64).astype(np.uint32)])
+        q = q[rng.permutation(q.size)]
+        gv, gf = (t.cpu().numpy().view(np.uint32) for t in table.lookup(_dev(q)))
+        order = np.argsort(keys)
+        at = np.minimum(np.searchsorted(keys[order], q), n - 1)
+        wf = (keys[order][at] == q).astype(np.uint32)
+        wv = np.where(wf == 1, vals[order][at], 0).astype(np.uint32)
+        assert np.array_equal(gf, wf) and np.array_equal(gv, wv), (n, size)
+    # duplicates: every row stored (distinct positions), a lookup answers from h1 when h1 holds the key, else from h2.
+    # A key has two slots, so twice at most, and few of them: two duplicated keys in one component of the cuckoo graph
+    # cannot both be placed, whatever the seeds
+    for n in (1000, 50000):
+        uniq = rng.choice(2**32 - 1, size=n, replace=False).astype(np.uint32)
+        keys = rng.permutation(np.concatenate([uniq, uniq[:8]]))
+        vals = np.arange(keys.size, dtype=np.uint32)
+        table, _ = ops.cuckoo_build(_dev(keys), _dev(vals), table_size=16 * keys.size)
+        sk, sv = (t.cpu().numpy().view(np.uint32) for t in table.slots())
+        assert np.array_equal(np.sort(sv[sk != 0xFFFFFFFF]), vals) and np.array_equal(keys[sv[sk != 0xFFFFFFFF]], sk[sk != 0xFFFFFFFF])
+        p1 = positions_np(uniq, 2, table.seeds[0], table.size)
+        p2 = positions_np(uniq, 2, table.seeds[1], table.size)
+        at = np.where(sk[p1] == uniq, p1, p2)
+        assert (sk[at] == uniq).all()
+        gv, gf = (t.cpu().numpy().view(np.uint32) for t in table.lookup(_dev(uniq)))
+        assert gf.all() and np.array_equal(gv, sv[at]), n
+
+
+def test_fuzz_slab():
+    """the slab table on random multiplicities (many distinct keys in few buckets: concurrent groups grow one chain):
+    every stored row found once, none lost; join_probe against a numpy join"""
+    from dwarf_bench_amd import ops
+    rng = np.random.default_rng(109)
+    for n in _sizes(rng, 10, 19)[::3]:
+        distinct = max(1, int(n / rng.choice([1, 2, 10, 300])))
+        keys = rng.choice(2**32 - 1, size=distinct, replace=False).astype(np.uint32)[rng.integers(0, distinct, n)]
+        uniq = np.unique(keys)  # the keys stored
+        buckets = max(int(rng.choice([1, 3, 64, max(1, n // 20)])), n // 4096)  # chains of up to 128 slabs
+        t = ops.SlabTable(buckets, -(-n // 32) + buckets + ops.SLAB_MAX_GROUPS)
+        res = t.insert(_dev(keys), _dev(np.arange(n, dtype=np.uint32)), want_results=True).cpu().numpy()
+        assert (res == 1).all() and t.status() == ops.DEV_OK, (n, buckets)
+        K, V, _, _ = t.slabs()
+        K, V = K.cpu().numpy().view(np.uint32), V.cpu().numpy().view(np.uint32)
+        full = K != 0xFFFFFFFF
+        assert np.array_equal(np.sort(V[full]), np.arange(n, dtype=np.uint32)), (n, buckets)  # each row once
+        assert np.array_equal(keys[V[full]], K[full])
+        gv, gf = (x.cpu().numpy().view(np.uint32) for x in t.lookup(_dev(uniq)))
+        assert gf.all() and np.array_equal(keys[gv], uniq), (n, buckets)
+        # join_probe: a hit carries (key, some build row's value of that key, the probe value), a miss three -1
+        probe = np.concatenate([uniq[rng.integers(0, uniq.size, n // 2 + 1)],
+                                rng.integers(0, 2**32 - 1, n // 2 + 1, dtype=np.uint64).astype(np.uint32)])
+        pv = rng.integers(0, 2**32, probe.size, dtype=np.uint64).astype(np.uint32)
+        ok, ob, op_ = (x.cpu().numpy().view(np.uint32) for x in t.join_probe(_dev(probe), _dev(pv)))
+        hit = np.isin(probe, uniq)
+        assert np.array_equal(ok, np.where(hit, probe, np.uint32(0xFFFFFFFF))), (n, buckets)
+        assert np.array_equal(op_, np.where(hit, pv, np.uint32(0xFFFFFFFF)))
+        assert (ob[~hit] == 0xFFFFFFFF).all() and np.array_equal(keys[ob[hit]], probe[hit])

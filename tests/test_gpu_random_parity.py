@@ -1,6 +1,6 @@
 """A short randomized parity run (tools/fuzz_gpu.py; beside the seeded oracle sweep of test_gpu_fuzz.py): sizes, alignments and value distributions outside the fixed lists
 of the other test files — both scan entry points, both digit widths of the sort, group-by, exclusive scan, reduce and
-both join forms against numpy."""
+both join forms, the hash group-by, the cuckoo and the slab tables against numpy."""
 import subprocess
 import sys
 from pathlib import Path

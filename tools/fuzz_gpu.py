@@ -10,7 +10,8 @@ budget = float(sys.argv[1]) if len(sys.argv) > 1 else 60.0
 seed = int(sys.argv[2]) if len(sys.argv) > 2 else 1
 rng = np.random.default_rng(seed)
 t_end = time.time() + budget
-done = {"scan": 0, "dense": 0, "sort": 0, "groupby": 0, "xscan": 0, "reduce": 0, "join": 0, "radix_join": 0, "crowded": 0, "ujoin": 0}
+done = {"scan": 0, "dense": 0, "sort": 0, "groupby": 0, "xscan": 0, "reduce": 0, "join": 0, "radix_join": 0, "crowded": 0, "ujoin": 0,
+        "groupby_hash": 0, "cuckoo": 0, "slab": 0}
 
 
 def rand_n():
@@ -180,6 +181,66 @@ while time.time() < t_end:
         assert np.array_equal(ob, np.where(hit, uv[srt][at], miss)), ("ujoin build vals", uk.size, m)
         assert np.array_equal(op_, np.where(hit, qv, miss)), ("ujoin probe vals", uk.size, m)
         done["ujoin"] += 1
+    # ---- hash group-by: any keys (a crowd on one partition every third round), a bound at, above or below the answer
+    ng = min(rand_n(), 4_000_000)
+    if ng:
+        if it % 3 == 0:
+            pool = crowd(int(rng.integers(100, 6000)))[0]
+            gk = pool[rng.integers(0, pool.size, ng)]
+        else:
+            gk = rand_values(ng, np.uint32)
+        gv = rand_values(ng, np.uint32)
+        uk, inv = np.unique(gk, return_inverse=True)
+        d = uk.size
+        bound = int(rng.choice([d, d + int(rng.integers(1, 100)), max(1, d - 1), 0]))
+        counts = bool(rng.integers(0, 2))
+        plan = ops.GroupByHash(ng, bound)
+        plan.launch(torch.from_numpy(gk.view(np.int32)).cuda(), torch.from_numpy(gv.view(np.int32)).cuda(), counts=counts)
+        st = ops.workspace_status(plan.ws)
+        if bound and bound < d:
+            assert st & ops.DEV_TABLE_FULL and int(plan.groups.item()) == bound, ("groupby_hash bound", ng, d, bound)
+        else:
+            k, s, c = plan.result()
+            k = k.cpu().numpy().view(np.uint32)
+            o = np.argsort(k)
+            sums = np.zeros(d, dtype=np.uint64)
+            np.add.at(sums, inv, gv.astype(np.uint64))
+            assert np.array_equal(k[o], uk), ("groupby_hash keys", ng, d, bound)
+            assert np.array_equal(s.cpu().numpy().view(np.uint32)[o], (sums & 0xFFFFFFFF).astype(np.uint32)), ("groupby_hash sums", ng, d)
+            if counts:
+                assert np.array_equal(c.cpu().numpy().view(np.uint32)[o], np.bincount(inv).astype(np.uint32)), ("groupby_hash counts", ng, d)
+        done["groupby_hash"] += 1
+    # ---- cuckoo table (hash kind 2): unique keys at load 0.1-0.45, lookups of present and absent keys
+    nc = min(rand_n(), 2_000_000)
+    if nc:
+        ck = rng.choice(2**32 - 1, size=nc, replace=False).astype(np.uint32)
+        cv = rand_values(nc, np.uint32)
+        table, _ = ops.cuckoo_build(torch.from_numpy(ck.view(np.int32)).cuda(), torch.from_numpy(cv.view(np.int32)).cuda(),
+                                    table_size=max(8, int(nc / rng.uniform(0.1, 0.45))), seed=it)
+        q = np.concatenate([ck, rng.integers(0, 2**32 - 1, nc, dtype=np.uint64).astype(np.uint32)])
+        gv_, gf_ = (t.cpu().numpy().view(np.uint32) for t in table.lookup(torch.from_numpy(q.view(np.int32)).cuda()))
+        srt = np.argsort(ck)
+        at = np.minimum(np.searchsorted(ck[srt], q), nc - 1)
+        hit = ck[srt][at] == q
+        assert np.array_equal(gf_, hit.astype(np.uint32)) and np.array_equal(gv_, np.where(hit, cv[srt][at], 0)), ("cuckoo", nc)
+        done["cuckoo"] += 1
+    # ---- slab table: random multiplicities in few or many buckets, every row stored once and found
+    ns = min(rand_n(), 1_000_000)
+    if ns:
+        sk = rand_values(ns, np.uint32) % np.uint32(max(1, ns // int(rng.choice([1, 3, 50]))))
+        sk[sk == 0xFFFFFFFF] = 0
+        buckets = max(int(rng.choice([1, 7, max(1, ns // 20)])), ns // 4096)
+        st_ = ops.SlabTable(buckets, -(-ns // 32) + buckets + ops.SLAB_MAX_GROUPS)
+        st_.insert(torch.from_numpy(sk.view(np.int32)).cuda(), torch.arange(ns, dtype=torch.int32, device="cuda"))
+        assert st_.status() == ops.DEV_OK, ("slab status", ns, buckets)
+        K, V, _, _ = st_.slabs()
+        K, V = K.cpu().numpy().view(np.uint32), V.cpu().numpy().view(np.uint32)
+        full = K != 0xFFFFFFFF
+        assert np.array_equal(np.sort(V[full]), np.arange(ns, dtype=np.uint32)) and np.array_equal(sk[V[full]], K[full]), ("slab rows", ns, buckets)
+        uq = np.unique(sk)
+        lv, lf = (t.cpu().numpy().view(np.uint32) for t in st_.lookup(torch.from_numpy(uq.view(np.int32)).cuda()))
+        assert lf.all() and np.array_equal(sk[lv], uq), ("slab lookup", ns, buckets)
+        done["slab"] += 1
     if it % 10 == 0:
         print(f"{it} iterations {done}", flush=True)
 print("fuzz ok", it, done)
