@@ -1,7 +1,9 @@
 // CPU check of the join's partition geometry (dwarf_bench_amd/csrc/join_common.hpp): every row count must give a
 // geometry the kernels can run — at most 1024 level-0 buckets, a power-of-two level-1 fan-out of at most 1024,
 // partitions that hold their expected rows, giant lists that fit the kernels' LDS list.  Built with hipcc (the header
-// pulls in the HIP runtime header), runs without a GPU.
+// pulls in the HIP runtime header), runs without a GPU.  With row counts as arguments it prints the geometry of each
+// instead, one line "n rows parts k1 k2" per count and rows per partition (the build's, then the radix join's), for the
+// tests' restatement of jl_layout to be compared with.
 #include <cstdio>
 #include <cstdlib>
 
@@ -31,8 +33,18 @@ static void check(size_t n, size_t rows) {
   CHECK(L.total >= L.giant_off + jl_giant_bytes(L.max_giants) && L.giant_off >= L.meta_off + L.meta_bytes);
 }
 
-int main() {
+int main(int argc, char **argv) {
   const size_t rows_options[2] = {kJlRowsPerPart, kJrRowsPerPart};
+  if (argc > 1) {
+    for (int i = 1; i < argc; ++i) {
+      const size_t n = std::strtoull(argv[i], nullptr, 10);
+      for (size_t rows : rows_options) {
+        const JlLayout L = jl_layout(n, rows);
+        std::printf("%zu %zu %u %u %u\n", n, rows, L.parts, L.k1, L.k2);
+      }
+    }
+    return 0;
+  }
   for (size_t rows : rows_options) {
     for (size_t n = 0; n < 70000; n += 17) check(n, rows);
     for (unsigned lg = 10; lg <= 31; ++lg)

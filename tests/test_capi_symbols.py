@@ -56,16 +56,78 @@ def test_product_has_no_oracle_import():
         assert "pyoracle" not in src and "import oracle" not in src and "from oracle" not in src, py
 
 
-def test_join_partition_geometry_for_every_row_count(tmp_path):
+@pytest.fixture(scope="module")
+def layout_tool(tmp_path_factory):
+    """tests/cpp/join_layout_check.cpp built with hipcc against join_common.hpp (runs without a GPU)"""
+    import subprocess
+    exe = tmp_path_factory.mktemp("layout") / "join_layout_check"
+    subprocess.run(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O1", "-std=c++17", "-w", "-I", str(ROOT / "dwarf_bench_amd" / "csrc"),
+                    str(ROOT / "tests" / "cpp" / "join_layout_check.cpp"), "-o", str(exe)], check=True, timeout=600)
+    return exe
+
+
+def test_join_partition_geometry_for_every_row_count(layout_tool):
     """join_common.hpp jl_layout over row counts up to 2^31, for the build's and the radix join's rows per partition:
     at most 1024 level-0 buckets, a power-of-two level-1 fan-out, partitions that hold their rows (tests/cpp/
     join_layout_check.cpp; a geometry with 1171 level-0 buckets at 2^30 rows once made that join take a minute)"""
     import subprocess
-    exe = tmp_path / "join_layout_check"
-    subprocess.run(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O1", "-std=c++17", "-w", "-I", str(ROOT / "dwarf_bench_amd" / "csrc"),
-                    str(ROOT / "tests" / "cpp" / "join_layout_check.cpp"), "-o", str(exe)], check=True, timeout=600)
-    r = subprocess.run([str(exe)], capture_output=True, text=True, timeout=300)
+    r = subprocess.run([str(layout_tool)], capture_output=True, text=True, timeout=300)
     assert r.returncode == 0 and "join layout ok" in r.stdout, r.stdout[-2000:]
+
+
+def test_side_plan_restates_the_compiled_geometry(layout_tool):
+    """tests/join_testlib.side_plan's (parts, k1, k2) against jl_layout as compiled, at every size the layout tests use
+    and +-3 rows around the partition counts where the histogram variant changes (8192: fused, 32768: fused16, 81920:
+    the digit column), for both rows per partition; and the variants and tile shapes the layout tests rely on"""
+    import subprocess
+    from tests import join_testlib as jt
+    per_part = (jt.JL_ROWS_PER_PART, jt.JR_ROWS_PER_PART)
+    sizes = set(jt.layout_sizes())
+    for parts in (8192, 32768, 81920):
+        for rows in per_part:
+            sizes.update(parts * rows + d for d in range(-3, 4))
+    r = subprocess.run([str(layout_tool)] + [str(n) for n in sorted(sizes)], capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
+    lines = r.stdout.split("\n")[:-1]
+    assert len(lines) == 2 * len(sizes)
+    for line in lines:
+        n, rows, parts, k1, k2 = map(int, line.split())
+        assert (rows in per_part) and jt.side_plan(n, n, rows)[:3] == (parts, k1, k2), line
+    # the variant changes exactly there (parts is a multiple of k2 = 64 below 2^26 rows: 8128 partitions, then 8192)
+    for rows in per_part:
+        for last, below, above in ((8128, "plain", "fused"), (32768, "fused", "fused16"), (81920, "fused16", "digits")):
+            got = [jt.side_plan(n, n, rows)[3] for n in (last * rows, last * rows + 1)]
+            assert got == [below, above], (rows, last, got)
+    for n, radix, hashed in jt.LAYOUT_TABLE:
+        assert jt.side_plan(n, n, jt.JR_ROWS_PER_PART) == radix and jt.side_plan(n, n, jt.JL_ROWS_PER_PART) == hashed
+        large, small = jt.radix_probe_sizes(n)
+        parts = radix[0]
+        assert large >= 128 * parts and jt.side_plan(large, n, jt.JR_ROWS_PER_PART)[3] == radix[3]
+        want_small = "plain" if radix[3] in ("fused", "fused16") else radix[3]
+        assert jt.side_plan(small, n, jt.JR_ROWS_PER_PART)[3] == want_small
+        assert jt.side_plan(128 * parts - 1, n, jt.JR_ROWS_PER_PART)[3] == want_small  # one row short of the scratch
+    hb = jt.HEADLINE_BUILD
+    assert (jt.side_plan(hb, hb, jt.JR_ROWS_PER_PART), jt.side_plan(hb, hb, jt.JL_ROWS_PER_PART)) == jt.HEADLINE_PLANS
+    assert jt.side_plan(jt.HEADLINE_PROBE, hb, jt.JR_ROWS_PER_PART)[3:] == ("digits", 2, 1)
+    assert [jt.side_plan(1 << 20, 1 << 20, 1792, t0, t1)[4:] for t0, t1 in ((0, 2), (1, 0), (None, 1))] == [(0, 1), (1, 0), (2, 1)]
+
+
+def test_guarded_columns_start_where_they_say():
+    """join_testlib.guarded on the host: the view starts offset words past a 16-byte boundary, the guards around it
+    are checked by assert_guards, and a write into one is caught"""
+    import torch
+    from tests import join_testlib as jt
+    for off in range(6):
+        base, view = jt.guarded(37, off, 0x5A5A5A5A, device="cpu")
+        assert view.numel() == 37 and (view.data_ptr() - base.data_ptr()) // 4 == jt.GUARD_WORDS + off
+        view.fill_(7)
+        jt.assert_guards(base, view, 0x5A5A5A5A)
+        for at in (jt.GUARD_WORDS + off - 1, jt.GUARD_WORDS + off + 37):
+            base[at] = 1
+            with pytest.raises(AssertionError):
+                jt.assert_guards(base, view, 0x5A5A5A5A)
+            base[at] = 0x5A5A5A5A
+    assert torch.equal(view, torch.full((37,), 7, dtype=torch.int32))
 
 
 def test_radix_join_refuses_probe_sides_its_32_bit_row_indices_cannot_walk():

@@ -8,6 +8,7 @@ import pytest
 import torch
 
 from oracle import pyoracle as po
+from tests import join_testlib as jt
 
 pytestmark = pytest.mark.gpu
 
@@ -164,19 +165,39 @@ def test_ranks_sharing_one_gpu_with_a_hot_key():
     assert max(o[4].size for o in outs) > n // 2  # the hot key's rows all went to one rank
 
 
-@pytest.mark.parametrize("n,direct", [(1000, False), (1000, True), (300007, False), (1 << 22, True), (1 << 22, False)])
-def test_native_engine_single_rank(n, direct):
+_ENGINE_CASES = [(1000, False, None), (1000, True, None), (300007, False, None), (1 << 22, True, None), (1 << 22, False, None),
+                 ((1 << 25) + 7, False, None), ((1 << 26) + 7, False, 4)]
+
+
+@pytest.mark.parametrize("n,direct,sub_joins", _ENGINE_CASES,
+                         ids=[f"{n}-{d}" + (f"-{h}-sub-joins" if h else "") for n, d, h in _ENGINE_CASES])
+def test_native_engine_single_rank(n, direct, sub_joins, monkeypatch):
     """the C++ engine (pjoin_engine.cpp) through its C entry points, one rank: the pipelined path with a self
-    exchange, and the direct local join; its device-side checks and the match count against the oracle"""
+    exchange, and the direct local join; its device-side checks and the match count against the oracle.  From 2^25
+    rows the sub-joins (two by default, four through DWARF_BENCH_PJOIN_SUBJOINS, read at creation) are in the fused
+    histograms' range, and every sub-join after the first starts at the rows of those before it: its keys, row ids and
+    output columns at an arbitrary 4-byte offset"""
     from dwarf_bench_amd import pjoin_native
+    from tests.pjoin_testlib import dest_of
+    if sub_joins is not None:
+        monkeypatch.setenv("DWARF_BENCH_PJOIN_SUBJOINS", str(sub_joins))
+    build = po.gen_uniform_u32(n, 42, 0, n - 1)
+    probe = po.gen_uniform_u32(n, 43, 0, n - 1)
+    if n > 1 << 22:
+        h = sub_joins or 2
+        # one rank: the rank-level partition's bucket (jl_rank_of over h buckets) is the sub-join
+        rows_b, rows_p = (np.bincount(dest_of(side, h), minlength=h) for side in (build, probe))
+        for rows in (rows_b, rows_p):
+            assert (np.cumsum(rows)[:-1] % 4).any(), rows  # some sub-join's columns start off a 16-byte boundary
+            assert h != 2 or rows[0] % 4, rows  # with two, the second one's
+        for nb, np_ in zip(rows_b, rows_p):  # every sub-join's sides through the fused histograms
+            assert jt.side_plan(nb, nb, jt.JR_ROWS_PER_PART)[3] == jt.side_plan(np_, nb, jt.JR_ROWS_PER_PART)[3] == "fused"
     eng = pjoin_native.NativePartitionedJoin(n, rank=0, world=1, device=0, direct_single=direct)
     for _ in range(2):
         t = eng.step()
         assert t["total_us"] > 0 and t["build_us"] > 0 and t["probe_us"] > 0
     chk = eng.check()
     eng.close()
-    build = po.gen_uniform_u32(n, 42, 0, n - 1)
-    probe = po.gen_uniform_u32(n, 43, 0, n - 1)
     assert chk["bad_pairs"] == chk["bad_route"] == chk["bad_rows"] == 0 and chk["conserved"]
     assert chk["recv_build"] == n and chk["recv_probe"] == n
     assert chk["matches"] == int(po.join_counts_fast(build, probe).astype(np.uint64).sum())
