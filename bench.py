@@ -1,23 +1,25 @@
 #!/usr/bin/env python3
 """bench.py — headline benchmark of the MI355X dwarf backend.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--dwarf scan|sort|groupby|join|all] [--no-cpu] [--no-pjoin] [--no-sweep]
-                  [--dump-outputs DIR]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
+                  [--full [--dwarf scan|sort|groupby|join|all] [--no-cpu] [--no-pjoin] [--no-sweep]]
 
 One "step" = one pass of the hot path over one batch of synthetic input already resident in HBM.
-N = 1 (default): the configuration BASELINE.json's metric is quoted on — TwoPassScan (stream compaction
-x < 5 over int32 uniform in [1, 10000]) at 2^28 rows, with a cold-source control (`value_cold`: the same steps over
-five 1 GiB copies in rotation).  The other single-GPU configurations of BASELINE.json (radix sort 2^24, group-by 2^26
-rows / 2^16 groups, hash join 2^26 x 2^26 — row-ordered probe and radix join) and the 2^30 x 2^30 join on one GPU
-(`pjoin_p1`, the P = 1 point of the partitioned join) are measured in the same run with a few steps each and reported
-under "dwarfs" (they are not the headline value).
+The headline: the configuration BASELINE.json's metric is quoted on — TwoPassScan (stream compaction x < 5 over int32
+uniform in [1, 10000]) at 2^28 rows.  A plain run measures only that: it sets up, warms up, times the K steps, writes
+--dump-outputs and prints the contract line.  Everything else below is measured with --full only (off by default).
+N = 1 with --full: a cold-source control (`value_cold`: the same steps over five 1 GiB copies in rotation), the
+roofline of the headline from HIP events in a loop of its own, a result check against the oracle, the CPU baselines,
+and the other single-GPU configurations of BASELINE.json (radix sort 2^24, group-by 2^26 rows / 2^16 groups, hash join
+2^26 x 2^26 — row-ordered probe and radix join) and the 2^30 x 2^30 join on one GPU (`pjoin_p1`, the P = 1 point of
+the partitioned join), measured with a few steps each and reported under "dwarfs" (they are not the headline value).
 N > 1, one rank per GPU — either under torch.distributed.run (RANK / WORLD_SIZE in the environment) or as plain
 `python bench.py --gpus N`, which then starts its own N rank processes before it imports torch or touches a GPU
 (self_launch; a WORLD_SIZE that differs from --gpus, or a rank without a GPU of its own, ends non-zero instead of
 printing a line with another n_gpus): the headline stays the same metric — scan does not
 shard ("replicas only"), so every rank runs the 2^28 scan on its own GPU and `value` is the aggregate (weak
-scaling) — and the one part of the path that does shard, the radix-partitioned hash join 2^30 x 2^30 with its
-RCCL all-to-all, is measured in the same run (strong scaling) and reported under "pjoin": on the C++ engine of the
+scaling) — and with --full the one part of the path that does shard, the radix-partitioned hash join 2^30 x 2^30 with
+its RCCL all-to-all, is measured in the same run (strong scaling) and reported under "pjoin": on the C++ engine of the
 PartitionedJoinHip dwarf (libdbench.so, one rank per process, RCCL called from C++; device-side checks of the
 exchange and of the result in the warm-up) and, under "pjoin.torch_distributed_host", on the torch.distributed host —
 each with its single-GPU time taken in this run on rank 0, i.e. the speed-up over one GPU is in the line itself.  The
@@ -27,10 +29,11 @@ fault aborts the process) costs `pjoin` an `error` entry, never the contract lin
 Rehearsal knobs (not for reported numbers): DBENCH_BACKEND=gloo lets several ranks share one GPU (the C++ RCCL leg
 is skipped), DBENCH_PJOIN_LOG2 shrinks the partitioned join.
 
-Prints ONE JSON line on rank 0 with the contract fields plus "roofline" and "cpu_baseline"; `ms_per_step` is the wall
-clock of one of the --steps timed scan steps.  --dump-outputs DIR also writes what the last timed step computed (the
-compacted column and its count, dump_outputs) as .npy files; the inputs are seeded, so two builds can be compared.
-The oracle (oracle/) is used ONLY for the cpu_baseline leg and a one-off result check; the timed path is
+Prints ONE JSON line on rank 0 with the contract fields (with --full also "roofline", "cpu_baseline" and the sections
+above); `ms_per_step` is the wall clock of one of the --steps timed scan steps.  --dump-outputs DIR also writes what
+the last timed step computed (the compacted column and its count, dump_outputs) as .npy files; the inputs are seeded,
+so two builds can be compared.
+The oracle (oracle/) is used ONLY for the cpu_baseline leg and a one-off result check (both --full); the timed path is
 libdbhip.so through the C ABI.
 """
 from __future__ import annotations
@@ -126,7 +129,9 @@ def _peak_source():
 # ---------------------------------------------------------------------------------------------------
 # single-GPU dwarfs
 # ---------------------------------------------------------------------------------------------------
-def bench_scan(steps, warmup, log2n=28, filt=5, cold=False, keep_output=False):
+def bench_scan(steps, warmup, log2n=28, filt=5, full=False, cold=False, keep_output=False):
+    """the headline: `warmup` untimed and `steps` timed steps; full: also the HIP-event times of every call (a loop of
+    its own, for the roofline) and, with cold, the cold-source control"""
     import torch
     from dwarf_bench_amd import ops
     n = 1 << log2n
@@ -143,8 +148,13 @@ def bench_scan(steps, warmup, log2n=28, filt=5, cold=False, keep_output=False):
     wall_ms = (time.perf_counter() - t0) * 1e3 / steps
     # what the last timed step handed its caller, read back before any other launch reuses the plan's buffers
     output = plan.result().cpu() if keep_output else None
-    ev = _event_times_us(run, steps)
     matches = plan.result().numel()
+    res = {"rows": n, "ms_per_step": wall_ms, "mrows_per_s": n / (wall_ms * 1e3), "matches": matches,
+           "workload": f"TwoPassScan copy_if(x<{filt}) 2^{log2n} int32 uniform[1,10000]",
+           "src": src, "plan": plan, "output": output}
+    if not full:
+        return res
+    ev = _event_times_us(run, steps)
     alg_bytes = 4 * n + 4 * matches  # 4*N*(1+s)
     avg_us = sum(ev) / len(ev)
     # cold-buffer control: the timed loop above scans the SAME 1 GiB every step; here the steps rotate over five
@@ -161,14 +171,9 @@ def bench_scan(steps, warmup, log2n=28, filt=5, cold=False, keep_output=False):
         torch.cuda.synchronize()
         cold_ms = (time.perf_counter() - t0) * 1e3 / steps
         del copies
-    return {
-        "cold_ms_per_step": cold_ms,
-        "rows": n, "ms_per_step": wall_ms, "kernel_us_avg": avg_us, "kernel_us_dropmax_mean": _drop_max_mean(ev),
-        "kernel_us_min": min(ev), "mrows_per_s": n / (wall_ms * 1e3), "matches": matches,
-        "algorithmic_bytes": alg_bytes, "achieved_gbs": alg_bytes / avg_us / 1e3,
-        "workload": f"TwoPassScan copy_if(x<{filt}) 2^{log2n} int32 uniform[1,10000]",
-        "src": src, "plan": plan, "output": output,
-    }
+    res.update({"cold_ms_per_step": cold_ms, "kernel_us_avg": avg_us, "kernel_us_dropmax_mean": _drop_max_mean(ev),
+                "kernel_us_min": min(ev), "algorithmic_bytes": alg_bytes, "achieved_gbs": alg_bytes / avg_us / 1e3})
+    return res
 
 
 DUMP_LIMIT_BYTES = 64 << 20
@@ -860,104 +865,19 @@ def self_launch(n, argv):
     return 0
 
 
-def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=20)
-    ap.add_argument("--warmup", type=int, default=3)
-    ap.add_argument("--dwarf", default="all", choices=["all", "scan", "sort", "groupby", "join"])
-    ap.add_argument("--no-cpu", action="store_true", help="skip the cpu_baseline leg")
-    ap.add_argument("--no-pjoin", action="store_true", help="skip the single-GPU 2^30 x 2^30 join (profiling passes)")
-    ap.add_argument("--no-sweep", action="store_true", help="skip the scan selectivity sweep and the reference-range "
-                    "sorts (counter passes: keeps every scan / sort dispatch at the BASELINE configuration)")
-    ap.add_argument("--dump-outputs", metavar="DIR", help="write the headline scan's output of its last timed step "
-                    "to DIR/<name>.npy (rank 0)")
-    ap.add_argument("--pjoin-child", action="store_true", help=argparse.SUPPRESS)  # see run_pjoin_children
-    args = ap.parse_args()
-
-    if args.gpus < 1:
-        raise SystemExit("bench.py: --gpus must be >= 1")
-    if args.steps < 1 or args.warmup < 0:
-        raise SystemExit("bench.py: --steps must be >= 1 and --warmup >= 0")
-    if args.gpus > 1 and not ("WORLD_SIZE" in os.environ and "RANK" in os.environ) and not args.pjoin_child:
-        # no launcher around this process: be the launcher (before torch is imported or the GPU touched)
-        raise SystemExit(self_launch(args.gpus, sys.argv[1:]))
-    rank, world, local = _dist_env()
-    if world != args.gpus:
-        # a line that says n_gpus = WORLD_SIZE under a command that says --gpus N would be a silent wrong measurement
-        raise SystemExit(f"bench.py: --gpus {args.gpus} but WORLD_SIZE = {world}: start it as `python bench.py --gpus N` "
-                         f"(it starts its own ranks) or under torch.distributed.run with --nproc-per-node N")
-    # the host driver of this pool only supports dmabuf IPC: without this RCCL's buffer sharing between the ranks
-    # fails with hipIpcGetMemHandle: invalid argument (already exported on the boxes; kept for any other launcher)
-    os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
-    if os.environ.get("DBENCH_FAULT_DUMP"):  # debugging aid: dump every thread's stack after N seconds and exit
-        import faulthandler
-        faulthandler.dump_traceback_later(int(os.environ["DBENCH_FAULT_DUMP"]), exit=True)
+def full_sections(args, scan, out, dist, rank, world, local, barrier):
+    """--full: everything the line carries besides the headline (a plain run measures none of it), filled into
+    `out` after the headline's timed steps"""
     import torch
-    if not torch.cuda.is_available():
-        raise SystemExit("bench.py needs a GPU (the product has no CPU path)")
-    if os.environ.get("DBENCH_BACKEND", "nccl") != "nccl":  # rehearsal: ranks may share a GPU
-        local %= torch.cuda.device_count()
-    elif local >= torch.cuda.device_count():
-        raise SystemExit(f"bench.py: rank {rank} has no GPU of its own ({torch.cuda.device_count()} visible, --gpus "
-                         f"{args.gpus}): RCCL needs one device per rank (DBENCH_BACKEND=gloo rehearses with shared GPUs)")
-    torch.cuda.set_device(local)
-    dist = None
-    if world > 1:
-        import torch.distributed as dist
-        backend = os.environ.get("DBENCH_BACKEND", "nccl")
-        if backend == "nccl":
-            dist.init_process_group("nccl", device_id=torch.device("cuda", local))
-        else:
-            dist.init_process_group(backend)
-    n_gpus = max(world, 1)
-
-    def barrier():
-        if dist is not None:
-            dist.barrier()
-        torch.cuda.synchronize()
-
-    if args.pjoin_child:  # the partitioned-join section only; rank 0 prints {"pjoin": section}
-        child_out = {}
-        print(f"[bench] child of rank {rank}: process group up", file=sys.stderr, flush=True)
-        pjoin_section(args, dist, rank, world, local, barrier, child_out)
-        if rank == 0:
-            print(json.dumps(child_out), flush=True)
-        if dist is not None:
-            dist.barrier()
-            dist.destroy_process_group()
-        return
-
-    # ---- headline: scan 2^28 (BASELINE.json's metric configuration)
-    barrier()
-    scan = bench_scan(args.steps, args.warmup, cold=(n_gpus == 1 and not args.no_sweep),
-                      keep_output=bool(args.dump_outputs) and rank == 0)
-    barrier()
-    if scan["output"] is not None:
-        dump_outputs(args.dump_outputs, scan)
-    ms = scan["ms_per_step"]
-    if dist is not None:
-        t = torch.tensor([ms], dtype=torch.float64, device="cuda")
-        dist.all_reduce(t, op=dist.ReduceOp.MAX)
-        ms = float(t.item())
-    value = n_gpus * scan["rows"] / (ms * 1e3)  # Mrows/s over all GPUs
-
-    out = {
-        "metric": "Mrows/s per dwarf at 2^28 int32; achieved HBM GB/s vs peak",
-        "value": value, "unit": "Mrows/s", "n_gpus": n_gpus, "steps": args.steps, "warmup": args.warmup,
-        "ms_per_step": ms, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-        "dtype": "int32", "data": "synthetic",
-        "config": {"workload": scan["workload"], "rows": scan["rows"], "selectivity": scan["matches"] / scan["rows"],
-                   "parallelism": "single GPU" if n_gpus == 1 else f"{n_gpus} independent replicas (scan does not shard)"},
-        "roofline": {"bound": "hbm", "achieved": scan["achieved_gbs"], "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                     "frac": scan["achieved_gbs"] / HBM_PEAK_GBS, "traffic": _traffic_for("scan"),
-                     "traffic_source": _traffic_source(),
-                     "kernel": "scan_chunk_kernel (+ scan_move_kernel in the same event bracket)",
-                     "kernel_us_avg": scan["kernel_us_avg"], "algorithmic_bytes": scan["algorithmic_bytes"],
-                     "kernel_us_avg_note": "HIP events around every call in a second loop of `steps` calls (event "
-                                           "records between the calls); ms_per_step is the wall clock of the "
-                                           "back-to-back loop — two loops, so the two figures differ by ~1 %"},
-    }
+    n_gpus = out["n_gpus"]
+    out["roofline"] = {"bound": "hbm", "achieved": scan["achieved_gbs"], "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                       "frac": scan["achieved_gbs"] / HBM_PEAK_GBS, "traffic": _traffic_for("scan"),
+                       "traffic_source": _traffic_source(),
+                       "kernel": "scan_chunk_kernel (+ scan_move_kernel in the same event bracket)",
+                       "kernel_us_avg": scan["kernel_us_avg"], "algorithmic_bytes": scan["algorithmic_bytes"],
+                       "kernel_us_avg_note": "HIP events around every call in a second loop of `steps` calls (event "
+                                             "records between the calls); ms_per_step is the wall clock of the "
+                                             "back-to-back loop — two loops, so the two figures differ by ~1 %"}
     if scan["cold_ms_per_step"] is not None:
         # the same scan with NO step finding its input in the Infinity Cache (five 1 GiB copies in rotation)
         out["value_cold"] = n_gpus * scan["rows"] / (scan["cold_ms_per_step"] * 1e3)
@@ -1035,6 +955,104 @@ def main():
             if rank == 0:
                 out["pjoin"] = section
             barrier()
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--gpus", type=int, default=1)
+    ap.add_argument("--steps", type=int, default=20)
+    ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--full", action="store_true", help="also measure and check everything beyond the headline: "
+                    "roofline, cold-source control, oracle check, CPU baselines, the other dwarfs, the partitioned join")
+    ap.add_argument("--dwarf", default="all", choices=["all", "scan", "sort", "groupby", "join"],
+                    help="with --full: the dwarfs measured besides the headline scan")
+    ap.add_argument("--no-cpu", action="store_true", help="with --full: skip the cpu_baseline legs")
+    ap.add_argument("--no-pjoin", action="store_true", help="with --full: skip the single-GPU 2^30 x 2^30 join "
+                    "(profiling passes)")
+    ap.add_argument("--no-sweep", action="store_true", help="with --full: skip the scan selectivity sweep and the "
+                    "reference-range sorts (counter passes: keeps every scan / sort dispatch at the BASELINE configuration)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the headline scan's output of its last timed step "
+                    "to DIR/<name>.npy (rank 0)")
+    ap.add_argument("--pjoin-child", action="store_true", help=argparse.SUPPRESS)  # see run_pjoin_children
+    args = ap.parse_args()
+
+    if args.gpus < 1:
+        raise SystemExit("bench.py: --gpus must be >= 1")
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("bench.py: --steps must be >= 1 and --warmup >= 0")
+    if args.gpus > 1 and not ("WORLD_SIZE" in os.environ and "RANK" in os.environ) and not args.pjoin_child:
+        # no launcher around this process: be the launcher (before torch is imported or the GPU touched)
+        raise SystemExit(self_launch(args.gpus, sys.argv[1:]))
+    rank, world, local = _dist_env()
+    if world != args.gpus:
+        # a line that says n_gpus = WORLD_SIZE under a command that says --gpus N would be a silent wrong measurement
+        raise SystemExit(f"bench.py: --gpus {args.gpus} but WORLD_SIZE = {world}: start it as `python bench.py --gpus N` "
+                         f"(it starts its own ranks) or under torch.distributed.run with --nproc-per-node N")
+    # the host driver of this pool only supports dmabuf IPC: without this RCCL's buffer sharing between the ranks
+    # fails with hipIpcGetMemHandle: invalid argument (already exported on the boxes; kept for any other launcher)
+    os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
+    if os.environ.get("DBENCH_FAULT_DUMP"):  # debugging aid: dump every thread's stack after N seconds and exit
+        import faulthandler
+        faulthandler.dump_traceback_later(int(os.environ["DBENCH_FAULT_DUMP"]), exit=True)
+    import torch
+    if not torch.cuda.is_available():
+        raise SystemExit("bench.py needs a GPU (the product has no CPU path)")
+    if os.environ.get("DBENCH_BACKEND", "nccl") != "nccl":  # rehearsal: ranks may share a GPU
+        local %= torch.cuda.device_count()
+    elif local >= torch.cuda.device_count():
+        raise SystemExit(f"bench.py: rank {rank} has no GPU of its own ({torch.cuda.device_count()} visible, --gpus "
+                         f"{args.gpus}): RCCL needs one device per rank (DBENCH_BACKEND=gloo rehearses with shared GPUs)")
+    torch.cuda.set_device(local)
+    dist = None
+    if world > 1:
+        import torch.distributed as dist
+        backend = os.environ.get("DBENCH_BACKEND", "nccl")
+        if backend == "nccl":
+            dist.init_process_group("nccl", device_id=torch.device("cuda", local))
+        else:
+            dist.init_process_group(backend)
+    n_gpus = max(world, 1)
+
+    def barrier():
+        if dist is not None:
+            dist.barrier()
+        torch.cuda.synchronize()
+
+    if args.pjoin_child:  # the partitioned-join section only; rank 0 prints {"pjoin": section}
+        child_out = {}
+        print(f"[bench] child of rank {rank}: process group up", file=sys.stderr, flush=True)
+        pjoin_section(args, dist, rank, world, local, barrier, child_out)
+        if rank == 0:
+            print(json.dumps(child_out), flush=True)
+        if dist is not None:
+            dist.barrier()
+            dist.destroy_process_group()
+        return
+
+    # ---- headline: scan 2^28 (BASELINE.json's metric configuration)
+    barrier()
+    scan = bench_scan(args.steps, args.warmup, full=args.full, cold=(args.full and n_gpus == 1 and not args.no_sweep),
+                      keep_output=bool(args.dump_outputs) and rank == 0)
+    barrier()
+    if scan["output"] is not None:
+        dump_outputs(args.dump_outputs, scan)
+    ms = scan["ms_per_step"]
+    if dist is not None:
+        t = torch.tensor([ms], dtype=torch.float64, device="cuda")
+        dist.all_reduce(t, op=dist.ReduceOp.MAX)
+        ms = float(t.item())
+    value = n_gpus * scan["rows"] / (ms * 1e3)  # Mrows/s over all GPUs
+
+    out = {
+        "metric": "Mrows/s per dwarf at 2^28 int32; achieved HBM GB/s vs peak",
+        "value": value, "unit": "Mrows/s", "n_gpus": n_gpus, "steps": args.steps, "warmup": args.warmup,
+        "ms_per_step": ms, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+        "dtype": "int32", "data": "synthetic",
+        "config": {"workload": scan["workload"], "rows": scan["rows"], "selectivity": scan["matches"] / scan["rows"],
+                   "parallelism": "single GPU" if n_gpus == 1 else f"{n_gpus} independent replicas (scan does not shard)"},
+    }
+    if args.full:
+        full_sections(args, scan, out, dist, rank, world, local, barrier)
 
     if rank == 0:
         print(json.dumps(out), flush=True)

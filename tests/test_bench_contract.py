@@ -65,7 +65,7 @@ def test_headline_profile_recomputes_the_roofline_fractions():
 def test_bench_defaults_and_help():
     r = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--help"], capture_output=True, text=True, timeout=120)
     assert r.returncode == 0
-    for flag in ("--gpus", "--steps", "--warmup", "--dump-outputs"):
+    for flag in ("--gpus", "--steps", "--warmup", "--dump-outputs", "--full"):
         assert flag in r.stdout
     src = (ROOT / "bench.py").read_text()
     assert 'add_argument("--gpus", type=int, default=1)' in src

@@ -18,7 +18,8 @@ def _launch(port, extra_env):
     env = {**os.environ, "DBENCH_BACKEND": "gloo", "DBENCH_PJOIN_LOG2": "20", "DBENCH_PJOIN_DEADLINE_S": "60", **extra_env}
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
                         "--master-addr", "127.0.0.1", "--master-port", str(port), str(ROOT / "bench.py"), "--gpus", "2",
-                        "--steps", "2", "--warmup", "1"], capture_output=True, text=True, timeout=600, env=env, cwd=str(ROOT))
+                        "--steps", "2", "--warmup", "1", "--full"], capture_output=True, text=True, timeout=600, env=env,
+                       cwd=str(ROOT))
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
     return r, lines
 
@@ -60,7 +61,7 @@ def test_gpus_2_without_any_launcher_starts_its_own_ranks():
     and carries the partitioned-join section; a world that does not match --gpus is refused"""
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT", "MASTER_ADDR")}
     env.update({"DBENCH_BACKEND": "gloo", "DBENCH_PJOIN_LOG2": "20", "DBENCH_PJOIN_DEADLINE_S": "60"})
-    r = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1"],
+    r = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--full"],
                        capture_output=True, text=True, timeout=600, env=env, cwd=str(ROOT))
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Condense the raw rocprofv3 output of tools/profile_round.sh into the small files kept under profiles/:
 
-  profiles/<tag>_bench_kernel_stats.csv   the --kernel-trace --stats table of `bench.py --no-sweep --no-cpu` (verbatim)
+  profiles/<tag>_bench_kernel_stats.csv   the --kernel-trace --stats table of `bench.py --full --no-sweep --no-cpu` (verbatim)
   profiles/<tag>_headline.json            the same trace split per BASELINE configuration: for every kernel of a
                                           configuration its dispatches, mean and min duration, and per call the span
                                           from the first kernel's start to the last kernel's end — with the algorithmic
@@ -159,8 +159,8 @@ def main():
                  f"WRITE_SIZE: {bool(write)}) — profiles/ left untouched")
     shutil.copy(stats[0], prof / f"{tag}_bench_kernel_stats.csv")
     (prof / f"{tag}_headline.json").write_text(json.dumps({
-        "_comment": "rocprofv3 --kernel-trace of `python3 bench.py --steps 20 --warmup 3 --no-cpu --no-sweep` split per "
-                    "BASELINE configuration (tools/profile_summary.py); durations in us; span = first kernel start -> "
+        "_comment": "rocprofv3 --kernel-trace of `python3 bench.py --steps 20 --warmup 3 --full --no-cpu --no-sweep` split "
+                    "per BASELINE configuration (tools/profile_summary.py); durations in us; span = first kernel start -> "
                     "last kernel end of one call; fractions against 8.0 TB/s",
         "git_head": git_head, "kernel_tree_sha256": kernel_tree_sha256(), "configurations": headline(raw)}, indent=1))
     per_kernel = {}
@@ -172,13 +172,13 @@ def main():
                          "FETCH_SIZE_KiB_mean": sum(f) / len(f) if f else None, "FETCH_SIZE_KiB_max": max(f) if f else None,
                          "WRITE_SIZE_KiB_mean": sum(w) / len(w) if w else None, "WRITE_SIZE_KiB_max": max(w) if w else None}
     (prof / f"{tag}_pmc.json").write_text(json.dumps({
-        "command": "rocprofv3 --pmc FETCH_SIZE -- python3 bench.py --steps 10 --warmup 2 --no-cpu --no-pjoin --no-sweep ; same with "
-                   "--pmc WRITE_SIZE (separate passes, tools/profile_round.sh)", "git_head": git_head, "kernels": per_kernel}, indent=1))
+        "command": "rocprofv3 --pmc FETCH_SIZE -- python3 bench.py --steps 10 --warmup 2 --full --no-cpu --no-pjoin --no-sweep ; "
+                   "same with --pmc WRITE_SIZE (separate passes, tools/profile_round.sh)", "git_head": git_head, "kernels": per_kernel}, indent=1))
 
     traffic = {"_source": {"tool": "tools/profile_round.sh -> tools/profile_summary.py", "round_tag": tag, "git_head": git_head,
                            "kernel_tree_sha256": kernel_tree_sha256(),
                            "command": "rocprofv3 --pmc FETCH_SIZE|WRITE_SIZE -- python3 bench.py --steps 10 --warmup 2 "
-                                      "--no-cpu --no-pjoin --no-sweep (one counter per pass)"},
+                                      "--full --no-cpu --no-pjoin --no-sweep (one counter per pass)"},
                "_comment": "HBM bytes per call from rocprofv3 --pmc passes (profiles/%s_pmc.json); counters are KiB; "
                            "FETCH_SIZE doubled for the 16-B/lane streaming reads on gfx950 (MI355X_MICROARCH.md, HBM "
                            "section); WRITE_SIZE exact; per call = sum over the dwarf's kernels / calls" % tag}
