@@ -1,8 +1,8 @@
 // hip_dwarfs.cpp — host side of the `...Hip` dwarfs (see hip_dwarfs.hpp).
 //
-// Every _run follows the reference's shape: generate the inputs once per size, then per iteration
-// time the device work between steady_clock stamps (host_time: launch + sync, the reference's
-// figure) and between hipEvents (kernel_time), validate, meter.add_result({{"buf_size", n}}, result).
+// Every _run follows the reference's shape: generate the inputs once per size, then per iteration time the device
+// work between steady_clock stamps (host_time: launch + sync, the reference's figure) and between hipEvents
+// (kernel_time; time_launch, time_build_probe), validate, record() -> meter.add_result({{"buf_size", n}}, result).
 // Differences, all deliberate:
 //   * inputs are generated ON the device by the counter-based generators of libdbhip (deterministic
 //     seeds instead of std::random_device, common/common.hpp:34-35) and stay resident: host_time does
@@ -33,19 +33,13 @@
 #include <unordered_map>
 
 #include "../../include/dbhip.h"
-#include "bench.hpp"
+#include "errors.hpp"
+
+using namespace dbench_errors;
 
 namespace {
 
 using clk = std::chrono::steady_clock;
-
-[[noreturn]] void fail(const std::string &what) { throw DwarfBench::DwarfBenchException(what); }
-void hip_ok(hipError_t e, const char *what) {
-  if (e != hipSuccess) fail(std::string(what) + ": " + hipGetErrorString(e));
-}
-void db_ok(int rc, const char *what) {
-  if (rc != 0) fail(std::string(what) + " failed with status " + std::to_string(rc));
-}
 
 // device buffer with the 256-byte alignment the C ABI asks for (hipMalloc gives more)
 template <class T>
@@ -157,7 +151,7 @@ void check_status(const void *ws, const char *what) {
   if (st != DBHIP_DEV_OK) fail(std::string(what) + ": device status " + std::to_string(st));
 }
 
-void banner(const char *dwarf) {
+void banner(const std::string &dwarf) {
   char name[64] = {0};
   int cus = 0, wave = 0;
   int dev = 0;
@@ -166,17 +160,83 @@ void banner(const char *dwarf) {
   std::cout << "Selected device: " << name << " (" << cus << " CUs, wave" << wave << ") for " << dwarf << "\n";
 }
 
-void common_init(Dwarf &d, const RunOptions &opts) {
-  d.meter().set_opts(opts);
-  d.meter().set_params({{"device_type", to_string(opts.device_ty)}});
+DwarfParams size_param(size_t n) { return DwarfParams{{"buf_size", std::to_string(n)}}; }
+
+// the end of every iteration: a failed check prints `message` (if any) on stderr and makes the Result invalid
+void record(Meter &meter, size_t n, std::unique_ptr<Result> result, bool ok, const char *message) {
+  if (!ok) {
+    if (message) std::cerr << message << std::endl;
+    result->valid = false;
+  }
+  meter.add_result(size_param(n), std::move(result));
 }
 
-DwarfParams size_param(size_t n) { return DwarfParams{{"buf_size", std::to_string(n)}}; }
+// the timed region of one launch: host_time = launch + sync between steady_clock stamps, kernel_time = the event pair
+template <class Launch>
+void time_launch(Result &result, const Events &ev, Launch &&launch) {
+  const auto host_start = clk::now();
+  hip_ok(hipEventRecord(ev.a, nullptr), "event");
+  launch();
+  hip_ok(hipEventRecord(ev.b, nullptr), "event");
+  hip_ok(hipStreamSynchronize(nullptr), "sync");
+  const auto host_end = clk::now();
+  result.host_time = host_end - host_start;
+  result.kernel_time = ev.elapsed();
+}
+
+// the timed region of a join: build, sync, probe, sync, each launch between its own event pair; build_time ends at the
+// build's sync, probe_time is the rest
+template <class Build, class Probe>
+void time_build_probe(HashJoinResult &result, const Events &build_ev, const Events &probe_ev, Build &&build,
+                      Probe &&probe) {
+  const auto host_start = clk::now();
+  hip_ok(hipEventRecord(build_ev.a, nullptr), "event");
+  build();
+  hip_ok(hipEventRecord(build_ev.b, nullptr), "event");
+  hip_ok(hipStreamSynchronize(nullptr), "sync");
+  const auto build_end = clk::now();
+  hip_ok(hipEventRecord(probe_ev.a, nullptr), "event");
+  probe();
+  hip_ok(hipEventRecord(probe_ev.b, nullptr), "event");
+  hip_ok(hipStreamSynchronize(nullptr), "sync");
+  const auto host_end = clk::now();
+  result.host_time = host_end - host_start;
+  result.build_time = build_end - host_start;
+  result.probe_time = host_end - build_end;
+  result.kernel_time = build_ev.elapsed() + probe_ev.elapsed();
+}
+
+// dbhip_gen_unique_sorted_u32 draws n unique keys from [0, 10n)
+void require_unique_keys_fit(size_t n, const std::string &who) {
+  if (10ull * n > 0xFFFFFFFFull) fail(who + ": keys are drawn from [0, 10*n) and must fit 32 bits");
+}
+
+constexpr uint64_t kSlabUniformSeed = 21;  // SlabHashBuildHip's keys: uniform in [1, 10000] from this seed
+
+// every key found (found = n ones) with value == key: vals against the generator itself (uniform keys) or against the
+// sorted keys' fingerprint (unique sorted keys); host comparison up to DWARF_BENCH_VALIDATE_MAX
+bool found_own_keys(const DevBuf<uint32_t> &keys, const DevBuf<uint32_t> &vals, const DevBuf<uint32_t> &found, size_t n,
+                    bool uniform_keys, const std::array<uint64_t, 4> &key_fp, CheckWords &chk) {
+  if (n <= validate_limit()) {
+    const auto hf = found.to_host(n);
+    return std::all_of(hf.begin(), hf.end(), [](uint32_t f) { return f == 1u; }) && vals.to_host(n) == keys.to_host(n);
+  }
+  db_ok(dbhip_check_sorted_u32(found.get(), n, 0, chk.dev(), nullptr), "dbhip_check_sorted_u32");
+  const auto g = chk.get();
+  bool ok = g[0] == 0 && g[2] == n;  // non-decreasing 0/1 entries summing to n: all ones
+  if (uniform_keys) {
+    db_ok(dbhip_check_gen_uniform_u32(vals.get(), nullptr, n, kSlabUniformSeed, 0, 1, 10000, chk.dev(), nullptr),
+          "dbhip_check_gen_uniform_u32");
+    return ok && chk.get()[0] == 0;
+  }
+  db_ok(dbhip_check_sorted_u32(vals.get(), n, 0, chk.dev(), nullptr), "dbhip_check_sorted_u32");
+  const auto v = chk.get();
+  return ok && v[0] == 0 && v[1] == key_fp[1] && v[2] == key_fp[2];
+}
 
 // ---- scan: shared by TwoPassScanHip and DPLScanHip -------------------------------------------------
 void run_scan(const char *who, size_t n, Meter &meter) {
   const RunOptions &opts = meter.opts();
-  banner(who);
   // scan/scan.cpp:73, scan/dplscan.cpp:43 hard-code 5 (selectivity 4e-4 on keys 1..10000); DWARF_BENCH_SCAN_FILTER
   // overrides it for the selectivity sweep of SURVEY 8(d)
   const char *filter_env = std::getenv("DWARF_BENCH_SCAN_FILTER");
@@ -248,36 +308,30 @@ void run_scan(const char *who, size_t n, Meter &meter) {
       const auto g = got.get();
       ok = count == want_fp[1] && g[1] == want_fp[1] && g[0] == want_fp[0];
     }
-    if (!ok) {
-      std::cerr << "incorrect results" << std::endl;
-      result->valid = false;
-    }
-    meter.add_result(size_param(n), std::move(result));
+    record(meter, n, std::move(result), ok, "incorrect results");  // scan/scan.cpp:162
   }
 }
 
 }  // namespace
 
+void HipDwarf::run(const RunOptions &opts) {
+  for (auto size : opts.input_size) {
+    banner(name());
+    _run(size, meter());
+  }
+}
+void HipDwarf::init(const RunOptions &opts) {
+  meter().set_opts(opts);
+  meter().set_params({{"device_type", to_string(opts.device_ty)}});
+}
+
 // =====================================================================================================
-TwoPassScanHip::TwoPassScanHip() : Dwarf("TwoPassScanHip") {}
 void TwoPassScanHip::_run(const size_t n, Meter &meter) { run_scan("TwoPassScanHip", n, meter); }
-void TwoPassScanHip::run(const RunOptions &opts) {
-  for (auto size : opts.input_size) _run(size, meter());
-}
-void TwoPassScanHip::init(const RunOptions &opts) { common_init(*this, opts); }
-
-DPLScanHip::DPLScanHip() : Dwarf("DPLScanHip") {}
 void DPLScanHip::_run(const size_t n, Meter &meter) { run_scan("DPLScanHip", n, meter); }
-void DPLScanHip::run(const RunOptions &opts) {
-  for (auto size : opts.input_size) _run(size, meter());
-}
-void DPLScanHip::init(const RunOptions &opts) { common_init(*this, opts); }
 
 // =====================================================================================================
-RadixHip::RadixHip() : Dwarf("RadixHip") {}
 void RadixHip::_run(const size_t n, Meter &meter) {
   const RunOptions &opts = meter.opts();
-  banner("RadixHip");
   const int bits = [] {
     const char *e = std::getenv("DWARF_BENCH_RADIX_BITS");
     return (e && std::atoi(e) == 4) ? 4 : 8;
@@ -304,14 +358,9 @@ void RadixHip::_run(const size_t n, Meter &meter) {
     // sort/radix.cpp:31); the refresh copy is not timed
     hip_ok(hipMemcpy(keys.get(), src.get(), n * sizeof(int32_t), hipMemcpyDeviceToDevice), "refresh");
     auto result = std::make_unique<Result>();
-    const auto host_start = clk::now();
-    hip_ok(hipEventRecord(ev.a, nullptr), "event");
-    db_ok(dbhip_radix_sort_i32(keys.get(), tmp.get(), n, bits, ws.get(), ws_bytes, nullptr), "dbhip_radix_sort_i32");
-    hip_ok(hipEventRecord(ev.b, nullptr), "event");
-    hip_ok(hipStreamSynchronize(nullptr), "sync");
-    const auto host_end = clk::now();
-    result->host_time = host_end - host_start;
-    result->kernel_time = ev.elapsed();
+    time_launch(*result, ev, [&] {
+      db_ok(dbhip_radix_sort_i32(keys.get(), tmp.get(), n, bits, ws.get(), ws_bytes, nullptr), "dbhip_radix_sort_i32");
+    });
     if (n) check_status(ws.get(), "RadixHip");
     if (inject_fault() && n) poke_xor(keys.get() + n / 2, 0x100u);
     bool ok;
@@ -322,87 +371,79 @@ void RadixHip::_run(const size_t n, Meter &meter) {
       const auto g = chk.get();
       ok = g[0] == 0 && g[1] == want[1] && g[2] == want[2];
     }
-    if (!ok) {
-      std::cerr << "incorrect results" << std::endl;
-      result->valid = false;
-    }
-    meter.add_result(size_param(n), std::move(result));
+    record(meter, n, std::move(result), ok, "incorrect results");  // sort/radix.cpp:61
   }
 }
-void RadixHip::run(const RunOptions &opts) {
-  for (auto size : opts.input_size) _run(size, meter());
-}
 void RadixHip::init(const RunOptions &opts) {
-  common_init(*this, opts);
+  HipDwarf::init(opts);
   // optional calibration, outside every timed region: pins the sort's ranking to what the device-side self-test of
   // the lane order saw (the sorts themselves never synchronise; every tile checks the order invariant regardless)
   (void)dbhip_radix_sort_prepare(nullptr);
 }
 
 // =====================================================================================================
-GroupByHip::GroupByHip() : Dwarf("GroupByHip") {}
+// ---- group-by: the buffers and the check shared by GroupByHip and GroupByLocalHip ----------------
+namespace {
+class GroupByBuffers {
+ public:
+  GroupByBuffers(size_t n, uint32_t groups)
+      : keys(n), vals(n), out(groups), ws_bytes(dbhip_groupby_sum_u32_workspace_bytes(n, groups)), ws(ws_bytes),
+        host_check_(n <= validate_limit()), expected_(groups, 0) {
+    db_ok(dbhip_gen_uniform_u32(vals.get(), n, 43, 0, 1, 10000, nullptr), "gen vals");        // groupby.cpp:29-30
+    db_ok(dbhip_gen_uniform_u32(keys.get(), n, 42, 0, 0, groups - 1, nullptr), "gen keys");  // groupby.cpp:31-32
+    hip_ok(hipDeviceSynchronize(), "sync");
+    if (host_check_) {  // groupby/groupby.cpp:8-19 expected_GroupBy with f = +
+      const auto hk = keys.to_host(n);
+      const auto hv = vals.to_host(n);
+      for (size_t i = 0; i < n; ++i) expected_[hk[i]] = expected_[hk[i]] + hv[i];
+    } else {  // sum of val * w(key) mod 2^32 for two weight functions, over the rows
+      db_ok(dbhip_check_weighted_sum_u32(keys.get(), vals.get(), n, chk_.dev(), nullptr), "dbhip_check_weighted_sum_u32");
+      want_ = chk_.get();
+    }
+  }
+  // the sums in `out` after a run
+  bool check() {
+    if (host_check_) return out.to_host(out.size()) == expected_;
+    // ... and over (g, out[g]): equal iff every row's value reached its own group (mod 2^32, as the sums)
+    db_ok(dbhip_check_weighted_sum_u32(nullptr, out.get(), out.size(), chk_.dev(), nullptr), "dbhip_check_weighted_sum_u32");
+    const auto g = chk_.get();
+    return g[0] == want_[0] && g[1] == want_[1];
+  }
+
+  DevBuf<uint32_t> keys, vals, out;
+  const size_t ws_bytes;
+  DevBuf<unsigned char> ws;
+
+ private:
+  const bool host_check_;
+  std::vector<uint32_t> expected_;
+  CheckWords chk_;
+  std::array<uint64_t, 4> want_{};
+};
+}  // namespace
+
 void GroupByHip::_run(const size_t n, Meter &meter) {
   // callers hand a GroupByRunOptions to GroupBy-family dwarfs (main.cpp:87-92, bench.cpp:80)
   const auto &opts = static_cast<const GroupByRunOptions &>(meter.opts());
-  banner("GroupByHip");
   const uint32_t groups = static_cast<uint32_t>(opts.groups_count ? opts.groups_count : 1);
-  DevBuf<uint32_t> keys(n), vals(n), out(groups);
-  const size_t ws_bytes = dbhip_groupby_sum_u32_workspace_bytes(n, groups);
-  DevBuf<unsigned char> ws(ws_bytes);
-  db_ok(dbhip_gen_uniform_u32(vals.get(), n, 43, 0, 1, 10000, nullptr), "gen vals");        // groupby.cpp:29-30
-  db_ok(dbhip_gen_uniform_u32(keys.get(), n, 42, 0, 0, groups - 1, nullptr), "gen keys");  // groupby.cpp:31-32
-  hip_ok(hipDeviceSynchronize(), "sync");
-  const bool host_check = n <= validate_limit();
-  std::vector<uint32_t> expected(groups, 0);
-  CheckWords chk;
-  std::array<uint64_t, 4> want{};
-  if (host_check) {  // groupby/groupby.cpp:8-19 expected_GroupBy with f = +
-    const auto hk = keys.to_host(n);
-    const auto hv = vals.to_host(n);
-    for (size_t i = 0; i < n; ++i) expected[hk[i]] = expected[hk[i]] + hv[i];
-  } else {  // sum of val * w(key) mod 2^32 for two weight functions, over the rows
-    db_ok(dbhip_check_weighted_sum_u32(keys.get(), vals.get(), n, chk.dev(), nullptr), "dbhip_check_weighted_sum_u32");
-    want = chk.get();
-  }
+  GroupByBuffers buf(n, groups);
   Events ev;
   for (size_t it = 0; it < opts.iterations; ++it) {
     auto result = std::make_unique<Result>();
-    const auto host_start = clk::now();
-    hip_ok(hipEventRecord(ev.a, nullptr), "event");
-    db_ok(dbhip_groupby_sum_u32(keys.get(), vals.get(), n, groups, out.get(), ws.get(), ws_bytes, nullptr),
-          "dbhip_groupby_sum_u32");
-    hip_ok(hipEventRecord(ev.b, nullptr), "event");
-    hip_ok(hipStreamSynchronize(nullptr), "sync");
-    const auto host_end = clk::now();
-    result->host_time = host_end - host_start;
-    result->kernel_time = ev.elapsed();
-    check_status(ws.get(), "GroupByHip");
-    if (inject_fault()) poke_xor(out.get() + groups / 2, 1u);
-    bool ok;
-    if (host_check) {
-      ok = out.to_host(groups) == expected;
-    } else {  // ... and over (g, out[g]): equal iff every row's value reached its own group (mod 2^32, as the sums)
-      db_ok(dbhip_check_weighted_sum_u32(nullptr, out.get(), groups, chk.dev(), nullptr), "dbhip_check_weighted_sum_u32");
-      const auto g = chk.get();
-      ok = g[0] == want[0] && g[1] == want[1];
-    }
-    if (!ok) {
-      std::cerr << "Incorrect results" << std::endl;
-      result->valid = false;
-    }
-    meter.add_result(size_param(n), std::move(result));
+    time_launch(*result, ev, [&] {
+      db_ok(dbhip_groupby_sum_u32(buf.keys.get(), buf.vals.get(), n, groups, buf.out.get(), buf.ws.get(), buf.ws_bytes,
+                                  nullptr),
+            "dbhip_groupby_sum_u32");
+    });
+    check_status(buf.ws.get(), "GroupByHip");
+    if (inject_fault()) poke_xor(buf.out.get() + groups / 2, 1u);
+    record(meter, n, std::move(result), buf.check(), "Incorrect results");
   }
 }
-void GroupByHip::run(const RunOptions &opts) {
-  for (auto size : opts.input_size) _run(size, meter());
-}
-void GroupByHip::init(const RunOptions &opts) { common_init(*this, opts); }
 
 // =====================================================================================================
-JoinOmnisciHip::JoinOmnisciHip() : Dwarf("JoinOmnisciHip") {}
 void JoinOmnisciHip::_run(const size_t n, Meter &meter) {
   const RunOptions &opts = meter.opts();
-  banner("JoinOmnisciHip");
   DevBuf<uint32_t> a(n), b(n), ids(n), pos(n), cnt(n);
   const size_t ws_bytes = dbhip_join_workspace_bytes(n);
   DevBuf<unsigned char> ws(ws_bytes);
@@ -432,21 +473,10 @@ void JoinOmnisciHip::_run(const size_t n, Meter &meter) {
   Events build_ev, probe_ev;
   for (size_t it = 0; it < opts.iterations; ++it) {
     auto result = std::make_unique<HashJoinResult>();
-    const auto host_start = clk::now();
-    hip_ok(hipEventRecord(build_ev.a, nullptr), "event");
-    db_ok(dbhip_join_build_u32(a.get(), n, ids.get(), ws.get(), ws_bytes, nullptr), "dbhip_join_build_u32");
-    hip_ok(hipEventRecord(build_ev.b, nullptr), "event");
-    hip_ok(hipStreamSynchronize(nullptr), "sync");
-    const auto build_end = clk::now();
-    hip_ok(hipEventRecord(probe_ev.a, nullptr), "event");
-    db_ok(dbhip_join_probe_u32(b.get(), n, ws.get(), n, pos.get(), cnt.get(), nullptr), "dbhip_join_probe_u32");
-    hip_ok(hipEventRecord(probe_ev.b, nullptr), "event");
-    hip_ok(hipStreamSynchronize(nullptr), "sync");
-    const auto host_end = clk::now();
-    result->host_time = host_end - host_start;
-    result->build_time = build_end - host_start;
-    result->probe_time = host_end - build_end;
-    result->kernel_time = build_ev.elapsed() + probe_ev.elapsed();
+    time_build_probe(
+        *result, build_ev, probe_ev,
+        [&] { db_ok(dbhip_join_build_u32(a.get(), n, ids.get(), ws.get(), ws_bytes, nullptr), "dbhip_join_build_u32"); },
+        [&] { db_ok(dbhip_join_probe_u32(b.get(), n, ws.get(), n, pos.get(), cnt.get(), nullptr), "dbhip_join_probe_u32"); });
     check_status(ws.get(), "JoinOmnisciHip");
     if (inject_fault() && n) poke_xor(cnt.get() + n / 2, 1u);
     bool ok = true;
@@ -477,131 +507,113 @@ void JoinOmnisciHip::_run(const size_t n, Meter &meter) {
             "dbhip_check_permutation_u32");
       ok = g[0] == 0 && chk.get()[0] == 0;
     }
-    if (!ok) {
-      std::cerr << "Incorrect results" << std::endl;
-      result->valid = false;
-    }
-    meter.add_result(size_param(n), std::move(result));
+    record(meter, n, std::move(result), ok, "Incorrect results");
   }
 }
-void JoinOmnisciHip::run(const RunOptions &opts) {
-  for (auto size : opts.input_size) _run(size, meter());
-}
-void JoinOmnisciHip::init(const RunOptions &opts) { common_init(*this, opts); }
 
 // =====================================================================================================
-JoinHip::JoinHip() : Dwarf("JoinHip") {}
+// ---- unique-key join: the buffers and the check shared by JoinHip and SlabJoinHip -----------------
+namespace {
+class UniqueJoinBuffers {
+ public:
+  UniqueJoinBuffers(size_t n, size_t ws_bytes)
+      : ak(n), av(n), bk(n), bv(n), ok_(n), o1(n), o2(n), ws_bytes(ws_bytes), ws(ws_bytes), n_(n),
+        host_check_(n <= validate_limit()) {
+    // unique, ascending keys in [0, 10n) like helpers::make_unique_random (common/common.cpp:7-20)
+    db_ok(dbhip_gen_unique_sorted_u32(ak.get(), n, 11, 0, nullptr), "gen");
+    db_ok(dbhip_gen_unique_sorted_u32(av.get(), n, 12, 0, nullptr), "gen");
+    db_ok(dbhip_gen_unique_sorted_u32(bk.get(), n, 13, 0, nullptr), "gen");
+    db_ok(dbhip_gen_unique_sorted_u32(bv.get(), n, 14, 0, nullptr), "gen");
+    hip_ok(hipDeviceSynchronize(), "sync");
+    if (host_check_) {
+      const auto hak = ak.to_host(n), hav = av.to_host(n);
+      hbk_ = bk.to_host(n);
+      hbv_ = bv.to_host(n);
+      for (size_t i = 0; i < n; ++i) a_payload_.emplace(hak[i], hav[i]);
+    }
+  }
+  // the probe's (ok_, o1, o2) after a run: per probe row (key, build value, probe value), all 0xFFFFFFFF on a miss
+  bool check() {
+    bool ok = true;
+    if (host_check_) {
+      // same table as seq_join would produce (join.cpp:27-28, :133): unique keys -> per probe row
+      const auto hk = ok_.to_host(n_), h1 = o1.to_host(n_), h2 = o2.to_host(n_);
+      for (size_t i = 0; i < n_ && ok; ++i) {
+        const auto f = a_payload_.find(hbk_[i]);
+        if (f == a_payload_.end())
+          ok = hk[i] == 0xFFFFFFFFu && h1[i] == 0xFFFFFFFFu && h2[i] == 0xFFFFFFFFu;
+        else
+          ok = hk[i] == hbk_[i] && h1[i] == f->second && h2[i] == hbv_[i];
+      }
+    } else {  // the build keys are generated ascending and unique: binary search finds every probe row's partner
+      db_ok(dbhip_check_ujoin_u32(ak.get(), av.get(), n_, bk.get(), bv.get(), n_, ok_.get(), o1.get(), o2.get(), chk_.dev(),
+                                  nullptr),
+            "dbhip_check_ujoin_u32");
+      ok = chk_.get()[0] == 0;
+    }
+    return ok;
+  }
+
+  DevBuf<uint32_t> ak, av, bk, bv, ok_, o1, o2;
+  const size_t ws_bytes;  // the join's table
+  DevBuf<unsigned char> ws;
+
+ private:
+  const size_t n_;
+  const bool host_check_;
+  std::unordered_map<uint32_t, uint32_t> a_payload_;
+  std::vector<uint32_t> hbk_, hbv_;
+  CheckWords chk_;
+};
+}  // namespace
+
 void JoinHip::_run(const size_t n, Meter &meter) {
   const RunOptions &opts = meter.opts();
-  banner("JoinHip");
-  if (10ull * n > 0xFFFFFFFFull) fail("JoinHip: keys are drawn from [0, 10*n) and must fit 32 bits");
-  DevBuf<uint32_t> ak(n), av(n), bk(n), bv(n), ok_(n), o1(n), o2(n);
-  const size_t ws_bytes = dbhip_ujoin_workspace_bytes(n);
-  DevBuf<unsigned char> ws(ws_bytes);
-  // unique, ascending keys in [0, 10n) like helpers::make_unique_random (common/common.cpp:7-20)
-  db_ok(dbhip_gen_unique_sorted_u32(ak.get(), n, 11, 0, nullptr), "gen");
-  db_ok(dbhip_gen_unique_sorted_u32(av.get(), n, 12, 0, nullptr), "gen");
-  db_ok(dbhip_gen_unique_sorted_u32(bk.get(), n, 13, 0, nullptr), "gen");
-  db_ok(dbhip_gen_unique_sorted_u32(bv.get(), n, 14, 0, nullptr), "gen");
-  hip_ok(hipDeviceSynchronize(), "sync");
-  const bool host_check = n <= validate_limit();
-  std::unordered_map<uint32_t, uint32_t> a_payload;
-  std::vector<uint32_t> hbk, hbv;
-  CheckWords chk;
-  if (host_check) {
-    const auto hak = ak.to_host(n), hav = av.to_host(n);
-    hbk = bk.to_host(n);
-    hbv = bv.to_host(n);
-    for (size_t i = 0; i < n; ++i) a_payload.emplace(hak[i], hav[i]);
-  }
+  require_unique_keys_fit(n, name());
+  UniqueJoinBuffers buf(n, dbhip_ujoin_workspace_bytes(n));
   Events build_ev, probe_ev;
   for (size_t it = 0; it < opts.iterations; ++it) {
     auto result = std::make_unique<HashJoinResult>();
-    const auto host_start = clk::now();
-    hip_ok(hipEventRecord(build_ev.a, nullptr), "event");
-    db_ok(dbhip_ujoin_build_u32(ak.get(), av.get(), n, ws.get(), ws_bytes, nullptr), "dbhip_ujoin_build_u32");
-    hip_ok(hipEventRecord(build_ev.b, nullptr), "event");
-    hip_ok(hipStreamSynchronize(nullptr), "sync");
-    const auto build_end = clk::now();
-    hip_ok(hipEventRecord(probe_ev.a, nullptr), "event");
-    db_ok(dbhip_ujoin_probe_u32(bk.get(), bv.get(), n, ws.get(), n, ok_.get(), o1.get(), o2.get(), nullptr),
-          "dbhip_ujoin_probe_u32");
-    hip_ok(hipEventRecord(probe_ev.b, nullptr), "event");
-    hip_ok(hipStreamSynchronize(nullptr), "sync");
-    const auto host_end = clk::now();
-    result->host_time = host_end - host_start;
-    result->build_time = build_end - host_start;
-    result->probe_time = host_end - build_end;
-    result->kernel_time = build_ev.elapsed() + probe_ev.elapsed();
-    check_status(ws.get(), "JoinHip");
-    if (inject_fault() && n) poke_xor(o1.get() + n / 2, 1u);
-    bool ok = true;
-    if (host_check) {
-      // same table as seq_join would produce (join.cpp:27-28, :133): unique keys -> per probe row
-      const auto hk = ok_.to_host(n), h1 = o1.to_host(n), h2 = o2.to_host(n);
-      for (size_t i = 0; i < n && ok; ++i) {
-        const auto f = a_payload.find(hbk[i]);
-        if (f == a_payload.end())
-          ok = hk[i] == 0xFFFFFFFFu && h1[i] == 0xFFFFFFFFu && h2[i] == 0xFFFFFFFFu;
-        else
-          ok = hk[i] == hbk[i] && h1[i] == f->second && h2[i] == hbv[i];
-      }
-    } else {  // the build keys are generated ascending and unique: binary search finds every probe row's partner
-      db_ok(dbhip_check_ujoin_u32(ak.get(), av.get(), n, bk.get(), bv.get(), n, ok_.get(), o1.get(), o2.get(), chk.dev(),
-                                  nullptr),
-            "dbhip_check_ujoin_u32");
-      ok = chk.get()[0] == 0;
-    }
-    if (!ok) {
-      std::cerr << "Incorrect results" << std::endl;
-      result->valid = false;
-    }
-    meter.add_result(size_param(n), std::move(result));
+    time_build_probe(
+        *result, build_ev, probe_ev,
+        [&] {
+          db_ok(dbhip_ujoin_build_u32(buf.ak.get(), buf.av.get(), n, buf.ws.get(), buf.ws_bytes, nullptr),
+                "dbhip_ujoin_build_u32");
+        },
+        [&] {
+          db_ok(dbhip_ujoin_probe_u32(buf.bk.get(), buf.bv.get(), n, buf.ws.get(), n, buf.ok_.get(), buf.o1.get(),
+                                      buf.o2.get(), nullptr),
+                "dbhip_ujoin_probe_u32");
+        });
+    check_status(buf.ws.get(), "JoinHip");
+    if (inject_fault() && n) poke_xor(buf.o1.get() + n / 2, 1u);
+    record(meter, n, std::move(result), buf.check(), "Incorrect results");
   }
 }
-void JoinHip::run(const RunOptions &opts) {
-  for (auto size : opts.input_size) _run(size, meter());
-}
-void JoinHip::init(const RunOptions &opts) { common_init(*this, opts); }
 
 // =====================================================================================================
 // GroupByLocalHip — the reference's privatised group-by as its own dwarf (groupby/groupby_local.cpp:24-142):
 // GroupByAggResult with the two phases timed separately and the CSV header
 // "total_time,group_by_time,reduction_time"; --executors caps the number of private tables.
-GroupByLocalHip::GroupByLocalHip() : Dwarf("GroupByLocalHip") {}
+GroupByLocalHip::GroupByLocalHip() : HipDwarf("GroupByLocalHip") {
+  reporting_header_ = "total_time,group_by_time,reduction_time";  // groupby_local.cpp:138
+}
 void GroupByLocalHip::_run(const size_t n, Meter &meter) {
   const auto &opts = static_cast<const GroupByRunOptions &>(meter.opts());
-  banner("GroupByLocalHip");
   const uint32_t groups = static_cast<uint32_t>(opts.groups_count ? opts.groups_count : 1);
   const uint32_t executors = static_cast<uint32_t>(opts.executors);
-  DevBuf<uint32_t> keys(n), vals(n), out(groups);
-  const size_t ws_bytes = dbhip_groupby_sum_u32_workspace_bytes(n, groups);
-  DevBuf<unsigned char> ws(ws_bytes);
-  db_ok(dbhip_gen_uniform_u32(vals.get(), n, 43, 0, 1, 10000, nullptr), "gen vals");
-  db_ok(dbhip_gen_uniform_u32(keys.get(), n, 42, 0, 0, groups - 1, nullptr), "gen keys");
-  hip_ok(hipDeviceSynchronize(), "sync");
-  const bool host_check = n <= validate_limit();
-  std::vector<uint32_t> expected(groups, 0);
-  CheckWords chk;
-  std::array<uint64_t, 4> want{};
-  if (host_check) {
-    const auto hk = keys.to_host(n);
-    const auto hv = vals.to_host(n);
-    for (size_t i = 0; i < n; ++i) expected[hk[i]] = expected[hk[i]] + hv[i];
-  } else {  // sum of val * w(key) mod 2^32 for two weight functions, over the rows
-    db_ok(dbhip_check_weighted_sum_u32(keys.get(), vals.get(), n, chk.dev(), nullptr), "dbhip_check_weighted_sum_u32");
-    want = chk.get();
-  }
+  GroupByBuffers buf(n, groups);
   Events ev;
   for (size_t it = 0; it < opts.iterations; ++it) {
     auto result = std::make_unique<GroupByAggResult>();
     const auto host_start = clk::now();
     hip_ok(hipEventRecord(ev.a, nullptr), "event");
-    db_ok(dbhip_groupby_partial_u32(keys.get(), vals.get(), n, groups, executors, ws.get(), ws_bytes, nullptr),
+    db_ok(dbhip_groupby_partial_u32(buf.keys.get(), buf.vals.get(), n, groups, executors, buf.ws.get(), buf.ws_bytes,
+                                    nullptr),
           "dbhip_groupby_partial_u32");
     hip_ok(hipStreamSynchronize(nullptr), "sync");  // the reference waits between the two kernels (:83, :112)
     const auto group_by_end = clk::now();
-    db_ok(dbhip_groupby_merge_u32(groups, executors, out.get(), ws.get(), nullptr), "dbhip_groupby_merge_u32");
+    db_ok(dbhip_groupby_merge_u32(groups, executors, buf.out.get(), buf.ws.get(), nullptr), "dbhip_groupby_merge_u32");
     hip_ok(hipEventRecord(ev.b, nullptr), "event");
     hip_ok(hipStreamSynchronize(nullptr), "sync");
     const auto host_end = clk::now();
@@ -609,38 +621,17 @@ void GroupByLocalHip::_run(const size_t n, Meter &meter) {
     result->group_by_time = group_by_end - host_start;
     result->reduction_time = host_end - group_by_end;
     result->kernel_time = ev.elapsed();
-    check_status(ws.get(), "GroupByLocalHip");
-    if (inject_fault()) poke_xor(out.get() + groups / 2, 1u);
-    bool ok;
-    if (host_check) {
-      ok = out.to_host(groups) == expected;
-    } else {  // ... and over (g, out[g]): equal iff every row's value reached its own group (mod 2^32, as the sums)
-      db_ok(dbhip_check_weighted_sum_u32(nullptr, out.get(), groups, chk.dev(), nullptr), "dbhip_check_weighted_sum_u32");
-      const auto g = chk.get();
-      ok = g[0] == want[0] && g[1] == want[1];
-    }
-    if (!ok) {
-      std::cerr << "Incorrect results" << std::endl;
-      result->valid = false;
-    }
-    meter.add_result(size_param(n), std::move(result));
+    check_status(buf.ws.get(), "GroupByLocalHip");
+    if (inject_fault()) poke_xor(buf.out.get() + groups / 2, 1u);
+    record(meter, n, std::move(result), buf.check(), "Incorrect results");
   }
-}
-void GroupByLocalHip::run(const RunOptions &opts) {
-  for (auto size : opts.input_size) _run(size, meter());
-}
-void GroupByLocalHip::init(const RunOptions &opts) {
-  reporting_header_ = "total_time,group_by_time,reduction_time";  // groupby_local.cpp:138
-  common_init(*this, opts);
 }
 
 // =====================================================================================================
 // HashBuildHip — build-only timing of the bitmask-claimed table (hash/hash_build.cpp:8-98): every row
 // inserts (key, key) into a table of 2n slots, Murmur3 hash; afterwards every key must be found.
-HashBuildHip::HashBuildHip() : Dwarf("HashBuildHip") {}
 void HashBuildHip::_run(const size_t n, Meter &meter) {
   const RunOptions &opts = meter.opts();
-  banner("HashBuildHip");
   const size_t ht_size = n ? n * 2 : 1;  // hash_build.cpp:19
   const uint32_t seed = 421;             // the reference draws it at random (helpers::make_random)
   DevBuf<uint32_t> src(n), found(n);
@@ -652,39 +643,25 @@ void HashBuildHip::_run(const size_t n, Meter &meter) {
     db_ok(dbhip_bitmask_table_reset(ws.get(), ws_bytes, ht_size, nullptr), "reset");  // fresh table, untimed (:23-26)
     hip_ok(hipStreamSynchronize(nullptr), "sync");
     auto result = std::make_unique<Result>();
-    const auto host_start = clk::now();
-    hip_ok(hipEventRecord(ev.a, nullptr), "event");
-    db_ok(dbhip_bitmask_table_insert_u32(src.get(), src.get(), n, ws.get(), ws_bytes, ht_size, 1, seed, 0, nullptr),
-          "dbhip_bitmask_table_insert_u32");
-    hip_ok(hipEventRecord(ev.b, nullptr), "event");
-    hip_ok(hipStreamSynchronize(nullptr), "sync");
-    const auto host_end = clk::now();
-    result->host_time = host_end - host_start;
-    result->kernel_time = ev.elapsed();
+    time_launch(*result, ev, [&] {
+      db_ok(dbhip_bitmask_table_insert_u32(src.get(), src.get(), n, ws.get(), ws_bytes, ht_size, 1, seed, 0, nullptr),
+            "dbhip_bitmask_table_insert_u32");
+    });
     check_status(ws.get(), "HashBuildHip");
     // hash_build.cpp:60-83: has(key) must be 1 for every inserted key
     db_ok(dbhip_bitmask_table_lookup_u32(src.get(), n, ws.get(), ht_size, 1, seed, nullptr, found.get(), nullptr),
           "dbhip_bitmask_table_lookup_u32");
     const auto h = found.to_host(n);
-    if (!std::all_of(h.begin(), h.end(), [](uint32_t f) { return f == 1u; })) {
-      std::cerr << "Incorrect results" << std::endl;
-      result->valid = false;
-    }
-    meter.add_result(size_param(n), std::move(result));
+    record(meter, n, std::move(result), std::all_of(h.begin(), h.end(), [](uint32_t f) { return f == 1u; }),
+           "Incorrect results");
   }
 }
-void HashBuildHip::run(const RunOptions &opts) {
-  for (auto size : opts.input_size) _run(size, meter());
-}
-void HashBuildHip::init(const RunOptions &opts) { common_init(*this, opts); }
 
 // =====================================================================================================
 // HashBuildNonBitmaskHip — build-only timing of the CAS-claimed table (hash/hash_build_non_bitmask.cpp:7-91):
 // distinct keys claim slots with atomicCAS, duplicates land on the same slot; every key must be found.
-HashBuildNonBitmaskHip::HashBuildNonBitmaskHip() : Dwarf("HashBuildNonBitmaskHip") {}
 void HashBuildNonBitmaskHip::_run(const size_t n, Meter &meter) {
   const RunOptions &opts = meter.opts();
-  banner("HashBuildNonBitmaskHip");
   DevBuf<uint32_t> src(n), ok_(n), o1(n), o2(n);
   const size_t ws_bytes = dbhip_ujoin_workspace_bytes(n);
   DevBuf<unsigned char> ws(ws_bytes);
@@ -693,28 +670,16 @@ void HashBuildNonBitmaskHip::_run(const size_t n, Meter &meter) {
   Events ev;
   for (size_t it = 0; it < opts.iterations; ++it) {
     auto result = std::make_unique<Result>();
-    const auto host_start = clk::now();
-    hip_ok(hipEventRecord(ev.a, nullptr), "event");
-    db_ok(dbhip_ujoin_build_u32(src.get(), src.get(), n, ws.get(), ws_bytes, nullptr), "dbhip_ujoin_build_u32");
-    hip_ok(hipEventRecord(ev.b, nullptr), "event");
-    hip_ok(hipStreamSynchronize(nullptr), "sync");
-    const auto host_end = clk::now();
-    result->host_time = host_end - host_start;
-    result->kernel_time = ev.elapsed();
+    time_launch(*result, ev, [&] {
+      db_ok(dbhip_ujoin_build_u32(src.get(), src.get(), n, ws.get(), ws_bytes, nullptr), "dbhip_ujoin_build_u32");
+    });
     check_status(ws.get(), "HashBuildNonBitmaskHip");
     db_ok(dbhip_ujoin_probe_u32(src.get(), src.get(), n, ws.get(), n, ok_.get(), o1.get(), o2.get(), nullptr), "probe");
     const auto hk = ok_.to_host(n), hs = src.to_host(n);
-    if (hk != hs) {  // every key found (a miss would leave the 0xFFFFFFFF sentinel)
-      std::cerr << "Incorrect results" << std::endl;
-      result->valid = false;
-    }
-    meter.add_result(size_param(n), std::move(result));
+    // every key found (a miss would leave the 0xFFFFFFFF sentinel)
+    record(meter, n, std::move(result), hk == hs, "Incorrect results");
   }
 }
-void HashBuildNonBitmaskHip::run(const RunOptions &opts) {
-  for (auto size : opts.input_size) _run(size, meter());
-}
-void HashBuildNonBitmaskHip::init(const RunOptions &opts) { common_init(*this, opts); }
 
 // =====================================================================================================
 // ProbeHip — probe-only timing (probe/slab_probe.cpp:9-107: the table is built untimed, :38-62, the timed region is the
@@ -722,11 +687,9 @@ void HashBuildNonBitmaskHip::init(const RunOptions &opts) { common_init(*this, o
 // Table = the LDS-partitioned one-to-many table of dwarf 4a (DWARF_BENCH_PROBE_TABLE=bitmask: the bitmask-claimed
 // SimpleNonOwningHashTable instead); keys from the make_unique_random twin.  Isolates the probe's share of the join:
 // algorithmic bytes 4n (keys) + 8n (position, count).
-ProbeHip::ProbeHip() : Dwarf("ProbeHip") {}
 void ProbeHip::_run(const size_t n, Meter &meter) {
   const RunOptions &opts = meter.opts();
-  banner("ProbeHip");
-  if (10ull * n > 0xFFFFFFFFull) fail("ProbeHip: keys are drawn from [0, 10*n) and must fit 32 bits");
+  require_unique_keys_fit(n, name());
   const char *table_env = std::getenv("DWARF_BENCH_PROBE_TABLE");
   const bool bitmask = table_env && std::string(table_env) == "bitmask";
   DevBuf<uint32_t> keys(n), ids(n), pos(n), cnt(n);
@@ -748,18 +711,13 @@ void ProbeHip::_run(const size_t n, Meter &meter) {
     }
     hip_ok(hipStreamSynchronize(nullptr), "sync");
     auto result = std::make_unique<Result>();
-    const auto host_start = clk::now();
-    hip_ok(hipEventRecord(ev.a, nullptr), "event");
-    if (bitmask)
-      db_ok(dbhip_bitmask_table_lookup_u32(keys.get(), n, ws.get(), ht_size, 1, seed, pos.get(), cnt.get(), nullptr),
-            "dbhip_bitmask_table_lookup_u32");
-    else
-      db_ok(dbhip_join_probe_u32(keys.get(), n, ws.get(), n, pos.get(), cnt.get(), nullptr), "dbhip_join_probe_u32");
-    hip_ok(hipEventRecord(ev.b, nullptr), "event");
-    hip_ok(hipStreamSynchronize(nullptr), "sync");
-    const auto host_end = clk::now();
-    result->host_time = host_end - host_start;
-    result->kernel_time = ev.elapsed();
+    time_launch(*result, ev, [&] {
+      if (bitmask)
+        db_ok(dbhip_bitmask_table_lookup_u32(keys.get(), n, ws.get(), ht_size, 1, seed, pos.get(), cnt.get(), nullptr),
+              "dbhip_bitmask_table_lookup_u32");
+      else
+        db_ok(dbhip_join_probe_u32(keys.get(), n, ws.get(), n, pos.get(), cnt.get(), nullptr), "dbhip_join_probe_u32");
+    });
     result->bytes = 12 * n;
     if (n) check_status(ws.get(), "ProbeHip");
     if (inject_fault() && n) poke_xor(cnt.get() + n / 2, 1u);
@@ -788,24 +746,14 @@ void ProbeHip::_run(const size_t n, Meter &meter) {
         ok = g[0] == 0 && g[1] == n;
       }
     }
-    if (!ok) {
-      std::cerr << "Incorrect results" << std::endl;
-      result->valid = false;
-    }
-    meter.add_result(size_param(n), std::move(result));
+    record(meter, n, std::move(result), ok, "Incorrect results");
   }
 }
-void ProbeHip::run(const RunOptions &opts) {
-  for (auto size : opts.input_size) _run(size, meter());
-}
-void ProbeHip::init(const RunOptions &opts) { common_init(*this, opts); }
 
 // =====================================================================================================
 // ReduceHip — int sum of a column (reduce/reduce.cpp:27-98); expected = std::accumulate(..., 0) (:21).
-ReduceHip::ReduceHip() : Dwarf("ReduceHip") {}
 void ReduceHip::_run(const size_t n, Meter &meter) {
   const RunOptions &opts = meter.opts();
-  banner("ReduceHip");
   DevBuf<int32_t> src(n), out(1);
   db_ok(dbhip_gen_uniform_u32(reinterpret_cast<uint32_t *>(src.get()), n, 42, 0, 1, 10000, nullptr), "gen");
   hip_ok(hipDeviceSynchronize(), "sync");
@@ -835,25 +783,15 @@ void ReduceHip::_run(const size_t n, Meter &meter) {
     result->kernel_time = ev.elapsed();
     result->bytes = n * sizeof(int32_t);
     if (inject_fault()) host_out ^= 1;
-    if (host_out != expected) {
-      std::cerr << "Incorrect results" << std::endl;
-      result->valid = false;
-    }
-    meter.add_result(size_param(n), std::move(result));
+    record(meter, n, std::move(result), host_out == expected, "Incorrect results");
   }
 }
-void ReduceHip::run(const RunOptions &opts) {
-  for (auto size : opts.input_size) _run(size, meter());
-}
-void ReduceHip::init(const RunOptions &opts) { common_init(*this, opts); }
 
 // =====================================================================================================
 // NestedLoopJoinHip — join/nested_join.cpp:10-110: n x n cell matrix on the device, compacted on the host in
 // cell order (:81-90), compared with the a-major/b-minor nested loop of join_helpers::seq_join.
-NestedLoopJoinHip::NestedLoopJoinHip() : Dwarf("NestedLoopJoinHip") {}
 void NestedLoopJoinHip::_run(const size_t n, Meter &meter) {
   const RunOptions &opts = meter.opts();
-  banner("NestedLoopJoinHip");
   if (n > (static_cast<size_t>(1) << 15)) fail("NestedLoopJoinHip: the n x n cell matrix is limited to n <= 32768");
   const size_t cells = n * n;
   DevBuf<uint32_t> ak(n), av(n), bk(n), bv(n), ok_(cells), o1(cells), o2(cells);
@@ -874,33 +812,22 @@ void NestedLoopJoinHip::_run(const size_t n, Meter &meter) {
   Events ev;
   for (size_t it = 0; it < opts.iterations; ++it) {
     auto result = std::make_unique<Result>();
-    const auto host_start = clk::now();
-    hip_ok(hipEventRecord(ev.a, nullptr), "event");
-    db_ok(dbhip_nested_join_u32(ak.get(), av.get(), bk.get(), bv.get(), n, n, ok_.get(), o1.get(), o2.get(), nullptr),
-          "dbhip_nested_join_u32");
-    hip_ok(hipEventRecord(ev.b, nullptr), "event");
-    hip_ok(hipStreamSynchronize(nullptr), "sync");
-    const auto host_end = clk::now();
-    result->host_time = host_end - host_start;
-    result->kernel_time = ev.elapsed();
+    time_launch(*result, ev, [&] {
+      db_ok(dbhip_nested_join_u32(ak.get(), av.get(), bk.get(), bv.get(), n, n, ok_.get(), o1.get(), o2.get(), nullptr),
+            "dbhip_nested_join_u32");
+    });
     result->bytes = 12 * cells;
+    bool ok = true;
     if (validate) {
       const auto hk = ok_.to_host(cells), h1 = o1.to_host(cells), h2 = o2.to_host(cells);
       std::vector<Row> got;
       for (size_t c = 0; c < cells; ++c)
         if (hk[c] != 0u) got.push_back({hk[c], h1[c], h2[c]});
-      if (got != expected) {
-        std::cerr << "Incorrect results" << std::endl;
-        result->valid = false;
-      }
+      ok = got == expected;
     }
-    meter.add_result(size_param(n), std::move(result));
+    record(meter, n, std::move(result), ok, "Incorrect results");
   }
 }
-void NestedLoopJoinHip::run(const RunOptions &opts) {
-  for (auto size : opts.input_size) _run(size, meter());
-}
-void NestedLoopJoinHip::init(const RunOptions &opts) { common_init(*this, opts); }
 
 // =====================================================================================================
 // CuckooHashBuildHip — build timing of the cuckoo table (hash/cuckoo_hash_build.cpp:8-134): unique keys from the
@@ -931,20 +858,17 @@ void cuckoo_seed_pair(uint64_t seed, uint64_t attempt, uint32_t *s1, uint32_t *s
 }
 }  // namespace
 
-CuckooHashBuildHip::CuckooHashBuildHip() : Dwarf("CuckooHashBuildHip") {}
 void CuckooHashBuildHip::_run(const size_t n, Meter &meter) {
   const RunOptions &opts = meter.opts();
-  banner("CuckooHashBuildHip");
-  if (10ull * n > 0xFFFFFFFFull) fail("CuckooHashBuildHip: keys are drawn from [0, 10*n) and must fit 32 bits");
+  require_unique_keys_fit(n, name());
   const size_t ht_size = n ? 4 * n : 1;  // cuckoo_hash_build.cpp:14
   DevBuf<uint32_t> keys(n), vals(n), found(n);
   db_ok(dbhip_gen_unique_sorted_u32(keys.get(), n, 11, 0, nullptr), "gen");  // make_unique_random (:12)
   const size_t ws_bytes = dbhip_cuckoo_table_workspace_bytes(ht_size);
   DevBuf<unsigned char> ws(ws_bytes);
-  const bool host_check = n <= validate_limit();
   CheckWords chk;
   std::array<uint64_t, 4> key_fp{};
-  if (!host_check) {  // sortedness + multiset fingerprint of the keys: what the looked-up values must reproduce
+  if (n > validate_limit()) {  // sortedness + multiset fingerprint of the keys: what the looked-up values must reproduce
     db_ok(dbhip_check_sorted_u32(keys.get(), n, 0, chk.dev(), nullptr), "dbhip_check_sorted_u32");
     key_fp = chk.get();
   }
@@ -984,29 +908,11 @@ void CuckooHashBuildHip::_run(const size_t n, Meter &meter) {
             "dbhip_cuckoo_table_lookup_u32");
       hip_ok(hipStreamSynchronize(nullptr), "sync");
       if (inject_fault()) poke_xor(vals.get() + n / 2, 1u);
-      if (host_check) {
-        const auto hf = found.to_host(n);
-        ok = std::all_of(hf.begin(), hf.end(), [](uint32_t f) { return f == 1u; }) && vals.to_host(n) == keys.to_host(n);
-      } else {  // found: n ones; vals: ascending with the keys' multiset fingerprint, i.e. equal to the sorted keys
-        db_ok(dbhip_check_sorted_u32(found.get(), n, 0, chk.dev(), nullptr), "dbhip_check_sorted_u32");
-        const auto g = chk.get();
-        ok = g[0] == 0 && g[2] == n;
-        db_ok(dbhip_check_sorted_u32(vals.get(), n, 0, chk.dev(), nullptr), "dbhip_check_sorted_u32");
-        const auto v = chk.get();
-        ok = ok && v[0] == 0 && v[1] == key_fp[1] && v[2] == key_fp[2];
-      }
+      ok = found_own_keys(keys, vals, found, n, false, key_fp, chk);
     }
-    if (!ok) {
-      std::cerr << "Incorrect results" << std::endl;
-      result->valid = false;
-    }
-    meter.add_result(size_param(n), std::move(result));
+    record(meter, n, std::move(result), ok, "Incorrect results");
   }
 }
-void CuckooHashBuildHip::run(const RunOptions &opts) {
-  for (auto size : opts.input_size) _run(size, meter());
-}
-void CuckooHashBuildHip::init(const RunOptions &opts) { common_init(*this, opts); }
 
 // =====================================================================================================
 // The slab dwarfs (hash/slab_hash_build.cpp, probe/slab_probe.cpp, join/slab_join.cpp) over the lock-free slab table
@@ -1019,7 +925,6 @@ void CuckooHashBuildHip::init(const RunOptions &opts) { common_init(*this, opts)
 // host_start, untimed.  A build that reports DBHIP_DEV_TABLE_FULL is "Incorrect results".
 namespace {
 constexpr uint64_t kSlabA = 242792921, kSlabB = 653019598, kSlabP = 2147483647;
-constexpr uint64_t kSlabUniformSeed = 21;
 size_t slab_buckets(size_t n) { return std::max<size_t>(1, n / 20); }
 size_t slab_pool(size_t n) { return slab_buckets(n) + DBHIP_SLAB_INSERT_GROUPS; }
 
@@ -1031,37 +936,14 @@ bool slab_built(const void *ws, const char *who) {
   if (st == DBHIP_DEV_TABLE_FULL) std::cerr << who << ": the slab pool ran out, rows were not stored\n";
   return st == DBHIP_DEV_OK;
 }
-
-// every key found (found = n ones) with value == key: vals against the generator itself (uniform keys) or against the
-// sorted keys' fingerprint (unique sorted keys); host comparison up to DWARF_BENCH_VALIDATE_MAX
-bool slab_found_own_keys(const DevBuf<uint32_t> &keys, const DevBuf<uint32_t> &vals, const DevBuf<uint32_t> &found,
-                         size_t n, bool uniform_keys, const std::array<uint64_t, 4> &key_fp, CheckWords &chk) {
-  if (n <= validate_limit()) {
-    const auto hf = found.to_host(n);
-    return std::all_of(hf.begin(), hf.end(), [](uint32_t f) { return f == 1u; }) && vals.to_host(n) == keys.to_host(n);
-  }
-  db_ok(dbhip_check_sorted_u32(found.get(), n, 0, chk.dev(), nullptr), "dbhip_check_sorted_u32");
-  const auto g = chk.get();
-  bool ok = g[0] == 0 && g[2] == n;  // non-decreasing 0/1 entries summing to n: all ones
-  if (uniform_keys) {
-    db_ok(dbhip_check_gen_uniform_u32(vals.get(), nullptr, n, kSlabUniformSeed, 0, 1, 10000, chk.dev(), nullptr),
-          "dbhip_check_gen_uniform_u32");
-    return ok && chk.get()[0] == 0;
-  }
-  db_ok(dbhip_check_sorted_u32(vals.get(), n, 0, chk.dev(), nullptr), "dbhip_check_sorted_u32");
-  const auto v = chk.get();
-  return ok && v[0] == 0 && v[1] == key_fp[1] && v[2] == key_fp[2];
-}
 }  // namespace
 
 // SlabHashBuildHip — hash/slab_hash_build.cpp:9-108: keys = make_random (uniform in [1, 10000], the
 // dbhip_gen_uniform_u32 twin), vals = keys, so every key repeats about n / 10000 times and about 10,000 chains grow
 // n / 320000 slabs long.  Timed: the insert alone (:41-64).  Then every key must be found (:66-99), here also with its
 // own value.
-SlabHashBuildHip::SlabHashBuildHip() : Dwarf("SlabHashBuildHip") {}
 void SlabHashBuildHip::_run(const size_t n, Meter &meter) {
   const RunOptions &opts = meter.opts();
-  banner("SlabHashBuildHip");
   const size_t buckets = slab_buckets(n), pool = slab_pool(n);
   if (buckets + pool > 0xFFFFFFFFull) fail("SlabHashBuildHip: too many rows for 32-bit node ids");
   DevBuf<uint32_t> keys(n), vals(n), found(n);
@@ -1074,16 +956,11 @@ void SlabHashBuildHip::_run(const size_t n, Meter &meter) {
     db_ok(dbhip_slab_table_reset(ws.get(), ws_bytes, buckets, pool, nullptr), "dbhip_slab_table_reset");
     hip_ok(hipStreamSynchronize(nullptr), "sync");
     auto result = std::make_unique<Result>();
-    const auto host_start = clk::now();
-    hip_ok(hipEventRecord(ev.a, nullptr), "event");
-    db_ok(dbhip_slab_table_insert_u32(keys.get(), keys.get(), n, ws.get(), ws_bytes, buckets, pool, kSlabA, kSlabB,
-                                      kSlabP, 0, nullptr, nullptr),
-          "dbhip_slab_table_insert_u32");
-    hip_ok(hipEventRecord(ev.b, nullptr), "event");
-    hip_ok(hipStreamSynchronize(nullptr), "sync");
-    const auto host_end = clk::now();
-    result->host_time = host_end - host_start;
-    result->kernel_time = ev.elapsed();
+    time_launch(*result, ev, [&] {
+      db_ok(dbhip_slab_table_insert_u32(keys.get(), keys.get(), n, ws.get(), ws_bytes, buckets, pool, kSlabA, kSlabB,
+                                        kSlabP, 0, nullptr, nullptr),
+            "dbhip_slab_table_insert_u32");
+    });
     bool ok = slab_built(ws.get(), "SlabHashBuildHip");
     if (ok && n) {
       db_ok(dbhip_slab_table_lookup_u32(keys.get(), n, ws.get(), buckets, pool, kSlabA, kSlabB, kSlabP, vals.get(),
@@ -1091,27 +968,17 @@ void SlabHashBuildHip::_run(const size_t n, Meter &meter) {
             "dbhip_slab_table_lookup_u32");
       hip_ok(hipStreamSynchronize(nullptr), "sync");
       if (inject_fault()) poke_xor(vals.get() + n / 2, 1u);
-      ok = slab_found_own_keys(keys, vals, found, n, true, {}, chk);
+      ok = found_own_keys(keys, vals, found, n, true, {}, chk);
     }
-    if (!ok) {
-      std::cerr << "Incorrect results" << std::endl;
-      result->valid = false;
-    }
-    meter.add_result(size_param(n), std::move(result));
+    record(meter, n, std::move(result), ok, "Incorrect results");
   }
 }
-void SlabHashBuildHip::run(const RunOptions &opts) {
-  for (auto size : opts.input_size) _run(size, meter());
-}
-void SlabHashBuildHip::init(const RunOptions &opts) { common_init(*this, opts); }
 
 // SlabProbeHip — probe/slab_probe.cpp:9-107: unique keys (make_unique_random twin), vals = keys, built untimed; timed:
 // the lookups of the same keys, every one of which must be found (:100-103), here also with its own value.
-SlabProbeHip::SlabProbeHip() : Dwarf("SlabProbeHip") {}
 void SlabProbeHip::_run(const size_t n, Meter &meter) {
   const RunOptions &opts = meter.opts();
-  banner("SlabProbeHip");
-  if (10ull * n > 0xFFFFFFFFull) fail("SlabProbeHip: keys are drawn from [0, 10*n) and must fit 32 bits");
+  require_unique_keys_fit(n, name());
   const size_t buckets = slab_buckets(n), pool = slab_pool(n);
   DevBuf<uint32_t> keys(n), vals(n), found(n);
   db_ok(dbhip_gen_unique_sorted_u32(keys.get(), n, 11, 0, nullptr), "gen");  // slab_probe.cpp:17
@@ -1132,32 +999,19 @@ void SlabProbeHip::_run(const size_t n, Meter &meter) {
           "dbhip_slab_table_insert_u32");
     hip_ok(hipStreamSynchronize(nullptr), "sync");
     auto result = std::make_unique<Result>();
-    const auto host_start = clk::now();
-    hip_ok(hipEventRecord(ev.a, nullptr), "event");
-    db_ok(dbhip_slab_table_lookup_u32(keys.get(), n, ws.get(), buckets, pool, kSlabA, kSlabB, kSlabP, vals.get(),
-                                      found.get(), nullptr),
-          "dbhip_slab_table_lookup_u32");
-    hip_ok(hipEventRecord(ev.b, nullptr), "event");
-    hip_ok(hipStreamSynchronize(nullptr), "sync");
-    const auto host_end = clk::now();
-    result->host_time = host_end - host_start;
-    result->kernel_time = ev.elapsed();
+    time_launch(*result, ev, [&] {
+      db_ok(dbhip_slab_table_lookup_u32(keys.get(), n, ws.get(), buckets, pool, kSlabA, kSlabB, kSlabP, vals.get(),
+                                        found.get(), nullptr),
+            "dbhip_slab_table_lookup_u32");
+    });
     bool ok = slab_built(ws.get(), "SlabProbeHip");
     if (ok && n) {
       if (inject_fault()) poke_xor(vals.get() + n / 2, 1u);
-      ok = slab_found_own_keys(keys, vals, found, n, false, key_fp, chk);
+      ok = found_own_keys(keys, vals, found, n, false, key_fp, chk);
     }
-    if (!ok) {
-      std::cerr << "Incorrect results" << std::endl;
-      result->valid = false;
-    }
-    meter.add_result(size_param(n), std::move(result));
+    record(meter, n, std::move(result), ok, "Incorrect results");
   }
 }
-void SlabProbeHip::run(const RunOptions &opts) {
-  for (auto size : opts.input_size) _run(size, meter());
-}
-void SlabProbeHip::init(const RunOptions &opts) { common_init(*this, opts); }
 
 // SlabJoinHip — join/slab_join.cpp:10-144: unique sorted keys and unique sorted values on both sides (the
 // make_unique_random twin, the seeds of JoinHip), build and probe timed separately (HashJoinResult).  The reference
@@ -1166,82 +1020,33 @@ void SlabProbeHip::init(const RunOptions &opts) { common_init(*this, opts); }
 // is sized like SlabHashBuild's (n / 20 buckets, a pool of as many nodes + DBHIP_SLAB_INSERT_GROUPS) with its hasher.  The probe writes per probe row
 // (key, build value, probe value), all 0xFFFFFFFF on a miss (dbhip_ujoin_probe_u32's convention): the reference
 // compacts by key != 0 (:127) and drops a real key 0.  Checked like JoinHip, against seq_join's table.
-SlabJoinHip::SlabJoinHip() : Dwarf("SlabJoinHip") {}
 void SlabJoinHip::_run(const size_t n, Meter &meter) {
   const RunOptions &opts = meter.opts();
-  banner("SlabJoinHip");
-  if (10ull * n > 0xFFFFFFFFull) fail("SlabJoinHip: keys are drawn from [0, 10*n) and must fit 32 bits");
+  require_unique_keys_fit(n, name());
   const size_t buckets = slab_buckets(n), pool = slab_pool(n);
-  DevBuf<uint32_t> ak(n), av(n), bk(n), bv(n), ok_(n), o1(n), o2(n);
-  const size_t ws_bytes = dbhip_slab_table_workspace_bytes(buckets, pool);
-  DevBuf<unsigned char> ws(ws_bytes);
-  db_ok(dbhip_gen_unique_sorted_u32(ak.get(), n, 11, 0, nullptr), "gen");
-  db_ok(dbhip_gen_unique_sorted_u32(av.get(), n, 12, 0, nullptr), "gen");
-  db_ok(dbhip_gen_unique_sorted_u32(bk.get(), n, 13, 0, nullptr), "gen");
-  db_ok(dbhip_gen_unique_sorted_u32(bv.get(), n, 14, 0, nullptr), "gen");
-  hip_ok(hipDeviceSynchronize(), "sync");
-  const bool host_check = n <= validate_limit();
-  std::unordered_map<uint32_t, uint32_t> a_payload;
-  std::vector<uint32_t> hbk, hbv;
-  CheckWords chk;
-  if (host_check) {
-    const auto hak = ak.to_host(n), hav = av.to_host(n);
-    hbk = bk.to_host(n);
-    hbv = bv.to_host(n);
-    for (size_t i = 0; i < n; ++i) a_payload.emplace(hak[i], hav[i]);
-  }
+  UniqueJoinBuffers buf(n, dbhip_slab_table_workspace_bytes(buckets, pool));
   Events build_ev, probe_ev;
   for (size_t it = 0; it < opts.iterations; ++it) {
-    db_ok(dbhip_slab_table_reset(ws.get(), ws_bytes, buckets, pool, nullptr), "dbhip_slab_table_reset");
+    db_ok(dbhip_slab_table_reset(buf.ws.get(), buf.ws_bytes, buckets, pool, nullptr), "dbhip_slab_table_reset");
     hip_ok(hipStreamSynchronize(nullptr), "sync");
     auto result = std::make_unique<HashJoinResult>();
-    const auto host_start = clk::now();
-    hip_ok(hipEventRecord(build_ev.a, nullptr), "event");
-    db_ok(dbhip_slab_table_insert_u32(ak.get(), av.get(), n, ws.get(), ws_bytes, buckets, pool, kSlabA, kSlabB, kSlabP,
-                                      0, nullptr, nullptr),
-          "dbhip_slab_table_insert_u32");
-    hip_ok(hipEventRecord(build_ev.b, nullptr), "event");
-    hip_ok(hipStreamSynchronize(nullptr), "sync");
-    const auto build_end = clk::now();
-    hip_ok(hipEventRecord(probe_ev.a, nullptr), "event");
-    db_ok(dbhip_slab_table_join_probe_u32(bk.get(), bv.get(), n, ws.get(), buckets, pool, kSlabA, kSlabB, kSlabP,
-                                          ok_.get(), o1.get(), o2.get(), nullptr),
-          "dbhip_slab_table_join_probe_u32");
-    hip_ok(hipEventRecord(probe_ev.b, nullptr), "event");
-    hip_ok(hipStreamSynchronize(nullptr), "sync");
-    const auto host_end = clk::now();
-    result->host_time = host_end - host_start;
-    result->build_time = build_end - host_start;
-    result->probe_time = host_end - build_end;
-    result->kernel_time = build_ev.elapsed() + probe_ev.elapsed();
-    bool ok = slab_built(ws.get(), "SlabJoinHip");
-    if (inject_fault() && n) poke_xor(o1.get() + n / 2, 1u);
-    if (ok && host_check) {
-      const auto hk = ok_.to_host(n), h1 = o1.to_host(n), h2 = o2.to_host(n);
-      for (size_t i = 0; i < n && ok; ++i) {
-        const auto f = a_payload.find(hbk[i]);
-        if (f == a_payload.end())
-          ok = hk[i] == 0xFFFFFFFFu && h1[i] == 0xFFFFFFFFu && h2[i] == 0xFFFFFFFFu;
-        else
-          ok = hk[i] == hbk[i] && h1[i] == f->second && h2[i] == hbv[i];
-      }
-    } else if (ok) {  // the build keys are generated ascending and unique: binary search finds every probe row's partner
-      db_ok(dbhip_check_ujoin_u32(ak.get(), av.get(), n, bk.get(), bv.get(), n, ok_.get(), o1.get(), o2.get(), chk.dev(),
-                                  nullptr),
-            "dbhip_check_ujoin_u32");
-      ok = chk.get()[0] == 0;
-    }
-    if (!ok) {
-      std::cerr << "Incorrect results" << std::endl;
-      result->valid = false;
-    }
-    meter.add_result(size_param(n), std::move(result));
+    time_build_probe(
+        *result, build_ev, probe_ev,
+        [&] {
+          db_ok(dbhip_slab_table_insert_u32(buf.ak.get(), buf.av.get(), n, buf.ws.get(), buf.ws_bytes, buckets, pool,
+                                            kSlabA, kSlabB, kSlabP, 0, nullptr, nullptr),
+                "dbhip_slab_table_insert_u32");
+        },
+        [&] {
+          db_ok(dbhip_slab_table_join_probe_u32(buf.bk.get(), buf.bv.get(), n, buf.ws.get(), buckets, pool, kSlabA,
+                                                kSlabB, kSlabP, buf.ok_.get(), buf.o1.get(), buf.o2.get(), nullptr),
+                "dbhip_slab_table_join_probe_u32");
+        });
+    bool ok = slab_built(buf.ws.get(), "SlabJoinHip");
+    if (inject_fault() && n) poke_xor(buf.o1.get() + n / 2, 1u);
+    record(meter, n, std::move(result), ok && buf.check(), "Incorrect results");
   }
 }
-void SlabJoinHip::run(const RunOptions &opts) {
-  for (auto size : opts.input_size) _run(size, meter());
-}
-void SlabJoinHip::init(const RunOptions &opts) { common_init(*this, opts); }
 
 // =====================================================================================================
 // PartitionedJoinHip — the radix-partitioned hash join of SURVEY 8(e) behind the Dwarf hook: one process driving
@@ -1253,7 +1058,7 @@ void SlabJoinHip::init(const RunOptions &opts) { common_init(*this, opts); }
 // (rehearsal on one GPU; DWARF_BENCH_PJOIN_EXCHANGE=copy forces it) share devices and push with hipMemcpyPeerAsync.
 // DWARF_BENCH_PJOIN_DIRECT=1 with --gpus 1: the plain local join (the P = 1 point of a scaling curve).
 // The local join of every rank is the radix join (dbhip_join_radix_*: received pairs partitioned once more, fused LDS
-// build + probe, no table in HBM); DWARF_BENCH_PJOIN_LOCAL=probe selects build + row-ordered probe instead.
+// build + probe, no table in HBM).
 // HashJoinResult: build_time = start -> every rank's build done, probe_time = the rest; the phase lines printed per
 // iteration are device-event spans (max over ranks) and overlap by design.
 // Checks, every iteration and at every size, on the device: the exchange conserves the four columns (wrap-around
@@ -1263,17 +1068,13 @@ void SlabJoinHip::init(const RunOptions &opts) { common_init(*this, opts); }
 // of the whole build column (all rows of a key must have met on ONE rank).
 #include "pjoin_engine.hpp"
 
-PartitionedJoinHip::PartitionedJoinHip() : Dwarf("PartitionedJoinHip") {}
 void PartitionedJoinHip::_run(const size_t n, Meter &meter) {
   const RunOptions &opts = meter.opts();
-  banner("PartitionedJoinHip");
   pjoin::Options po;
   po.world = static_cast<unsigned>(opts.devices ? opts.devices : 1);
   const char *force = std::getenv("DWARF_BENCH_PJOIN_EXCHANGE");
   po.force_copy = force && std::string(force) == "copy";
   po.direct_single = env_flag("DWARF_BENCH_PJOIN_DIRECT");
-  const char *local = std::getenv("DWARF_BENCH_PJOIN_LOCAL");  // "probe": build + row-ordered probe instead of the radix join
-  po.radix_local = !(local && std::string(local) == "probe");
   int ndev = 0;
   hip_ok(hipGetDeviceCount(&ndev), "hipGetDeviceCount");
   pjoin::Engine engine(n, po);
@@ -1347,14 +1148,9 @@ void PartitionedJoinHip::_run(const size_t n, Meter &meter) {
         ok = false;
       }
     }
-    if (!ok) result->valid = false;
-    meter.add_result(size_param(n), std::move(result));
+    record(meter, n, std::move(result), ok, nullptr);  // the lines above said what failed
   }
 }
-void PartitionedJoinHip::run(const RunOptions &opts) {
-  for (auto size : opts.input_size) _run(size, meter());
-}
-void PartitionedJoinHip::init(const RunOptions &opts) { common_init(*this, opts); }
 
 // =====================================================================================================
 // GroupByHashHip — GROUP BY key SUM(val), COUNT(*) over sparse keys (dbhip_groupby_hash_u32): vals uniform in [1, 10000]
@@ -1362,10 +1158,8 @@ void PartitionedJoinHip::init(const RunOptions &opts) { common_init(*this, opts)
 // fewer where two draws mix to one word) spread over the whole uint32 range.  max_groups = groups_count.  Result::valid
 // from the device validators: distinct output keys, the weighted sums of (out_keys, out_sums) and of (out_keys,
 // out_counts) equal those of (keys, vals) and of (keys, ones), and the counts sum to n.
-GroupByHashHip::GroupByHashHip() : Dwarf("GroupByHashHip") {}
 void GroupByHashHip::_run(const size_t n, Meter &meter) {
   const auto &opts = static_cast<const GroupByRunOptions &>(meter.opts());
-  banner("GroupByHashHip");
   if (n > (static_cast<size_t>(1) << 31)) fail("GroupByHashHip: at most 2^31 rows");
   const uint32_t groups = static_cast<uint32_t>(opts.groups_count ? opts.groups_count : 1);
   const size_t cap = std::max<size_t>(std::min<size_t>(groups, n), 1);
@@ -1387,16 +1181,11 @@ void GroupByHashHip::_run(const size_t n, Meter &meter) {
   Events ev;
   for (size_t it = 0; it < opts.iterations; ++it) {
     auto result = std::make_unique<Result>();
-    const auto host_start = clk::now();
-    hip_ok(hipEventRecord(ev.a, nullptr), "event");
-    db_ok(dbhip_groupby_hash_u32(keys.get(), vals.get(), n, groups, out_keys.get(), out_sums.get(), out_counts.get(),
-                                 out_groups.get(), ws.get(), ws_bytes, nullptr),
-          "dbhip_groupby_hash_u32");
-    hip_ok(hipEventRecord(ev.b, nullptr), "event");
-    hip_ok(hipStreamSynchronize(nullptr), "sync");
-    const auto host_end = clk::now();
-    result->host_time = host_end - host_start;
-    result->kernel_time = ev.elapsed();
+    time_launch(*result, ev, [&] {
+      db_ok(dbhip_groupby_hash_u32(keys.get(), vals.get(), n, groups, out_keys.get(), out_sums.get(), out_counts.get(),
+                                   out_groups.get(), ws.get(), ws_bytes, nullptr),
+            "dbhip_groupby_hash_u32");
+    });
     check_status(ws.get(), "GroupByHashHip");
     const size_t g = static_cast<size_t>(out_groups.to_host(1)[0]);
     if (inject_fault() && g) poke_xor(out_sums.get() + g / 2, 1u);
@@ -1413,14 +1202,6 @@ void GroupByHashHip::_run(const size_t n, Meter &meter) {
       ok = s[0] == want_sums[0] && s[1] == want_sums[1] && c[0] == want_counts[0] && c[1] == want_counts[1] && d[0] == 0 &&
            total == n;
     }
-    if (!ok) {
-      std::cerr << "Incorrect results" << std::endl;
-      result->valid = false;
-    }
-    meter.add_result(size_param(n), std::move(result));
+    record(meter, n, std::move(result), ok, "Incorrect results");
   }
 }
-void GroupByHashHip::run(const RunOptions &opts) {
-  for (auto size : opts.input_size) _run(size, meter());
-}
-void GroupByHashHip::init(const RunOptions &opts) { common_init(*this, opts); }

@@ -10,39 +10,93 @@
 #pragma once
 #include "dwarf_api.hpp"
 
-#define DBHIP_DECLARE_DWARF(cls)                 \
-  class cls : public Dwarf {                     \
-   public:                                       \
-    cls();                                       \
-    void run(const RunOptions &opts) override;   \
-    void init(const RunOptions &opts) override;  \
-                                                 \
-   private:                                      \
-    void _run(const size_t buf_size, Meter &meter); \
-  }
+// The frame of every `...Hip` dwarf: run() prints the device banner and calls _run once per input size, init() hands
+// the options to the meter and records the device type.  A dwarf supplies its name and _run.
+class HipDwarf : public Dwarf {
+ public:
+  explicit HipDwarf(const std::string &name) : Dwarf(name) {}
+  void run(const RunOptions &opts) override;
+  void init(const RunOptions &opts) override;
 
-DBHIP_DECLARE_DWARF(TwoPassScanHip);
-DBHIP_DECLARE_DWARF(DPLScanHip);
-DBHIP_DECLARE_DWARF(RadixHip);
-DBHIP_DECLARE_DWARF(GroupByHip);
-DBHIP_DECLARE_DWARF(JoinOmnisciHip);
-DBHIP_DECLARE_DWARF(JoinHip);
-DBHIP_DECLARE_DWARF(PartitionedJoinHip);      // radix-partitioned join over --gpus ranks, RCCL exchange
+ private:
+  virtual void _run(size_t buf_size, Meter &meter) = 0;
+};
+
+struct TwoPassScanHip : HipDwarf {
+  TwoPassScanHip() : HipDwarf("TwoPassScanHip") {}
+  void _run(size_t buf_size, Meter &meter) override;
+};
+struct DPLScanHip : HipDwarf {
+  DPLScanHip() : HipDwarf("DPLScanHip") {}
+  void _run(size_t buf_size, Meter &meter) override;
+};
+struct RadixHip : HipDwarf {
+  RadixHip() : HipDwarf("RadixHip") {}
+  void init(const RunOptions &opts) override;  // HipDwarf::init, then dbhip_radix_sort_prepare
+  void _run(size_t buf_size, Meter &meter) override;
+};
+struct GroupByHip : HipDwarf {
+  GroupByHip() : HipDwarf("GroupByHip") {}
+  void _run(size_t buf_size, Meter &meter) override;
+};
+struct JoinOmnisciHip : HipDwarf {
+  JoinOmnisciHip() : HipDwarf("JoinOmnisciHip") {}
+  void _run(size_t buf_size, Meter &meter) override;
+};
+struct JoinHip : HipDwarf {
+  JoinHip() : HipDwarf("JoinHip") {}
+  void _run(size_t buf_size, Meter &meter) override;
+};
+struct PartitionedJoinHip : HipDwarf {  // radix-partitioned join over --gpus ranks, RCCL exchange
+  PartitionedJoinHip() : HipDwarf("PartitionedJoinHip") {}
+  void _run(size_t buf_size, Meter &meter) override;
+};
 // SURVEY 8(f) "next" rows
-DBHIP_DECLARE_DWARF(GroupByLocalHip);         // groupby/groupby_local.cpp:24-142 (two-phase timings, --executors)
-DBHIP_DECLARE_DWARF(HashBuildHip);            // hash/hash_build.cpp:8-98 (bitmask-claimed table, build only)
-DBHIP_DECLARE_DWARF(HashBuildNonBitmaskHip);  // hash/hash_build_non_bitmask.cpp:7-91 (CAS table, build only)
-DBHIP_DECLARE_DWARF(ProbeHip);                // probe/slab_probe.cpp:9-107 (table built untimed, lookups timed)
-DBHIP_DECLARE_DWARF(ReduceHip);               // reduce/reduce.cpp:27-98 (int sum)
-DBHIP_DECLARE_DWARF(NestedLoopJoinHip);       // join/nested_join.cpp:10-110 (dense cell matrix, small n)
+struct GroupByLocalHip : HipDwarf {  // groupby/groupby_local.cpp:24-142 (two-phase timings, --executors)
+  GroupByLocalHip();
+  void _run(size_t buf_size, Meter &meter) override;
+};
+struct HashBuildHip : HipDwarf {  // hash/hash_build.cpp:8-98 (bitmask-claimed table, build only)
+  HashBuildHip() : HipDwarf("HashBuildHip") {}
+  void _run(size_t buf_size, Meter &meter) override;
+};
+struct HashBuildNonBitmaskHip : HipDwarf {  // hash/hash_build_non_bitmask.cpp:7-91 (CAS table, build only)
+  HashBuildNonBitmaskHip() : HipDwarf("HashBuildNonBitmaskHip") {}
+  void _run(size_t buf_size, Meter &meter) override;
+};
+struct ProbeHip : HipDwarf {  // probe/slab_probe.cpp:9-107 (table built untimed, lookups timed)
+  ProbeHip() : HipDwarf("ProbeHip") {}
+  void _run(size_t buf_size, Meter &meter) override;
+};
+struct ReduceHip : HipDwarf {  // reduce/reduce.cpp:27-98 (int sum)
+  ReduceHip() : HipDwarf("ReduceHip") {}
+  void _run(size_t buf_size, Meter &meter) override;
+};
+struct NestedLoopJoinHip : HipDwarf {  // join/nested_join.cpp:10-110 (dense cell matrix, small n)
+  NestedLoopJoinHip() : HipDwarf("NestedLoopJoinHip") {}
+  void _run(size_t buf_size, Meter &meter) override;
+};
 // the reference's EXPERIMENTAL block: registered by populate_experimental_registry() only
-DBHIP_DECLARE_DWARF(CuckooHashBuildHip);      // hash/cuckoo_hash_build.cpp:8-134 (lock-free cuckoo table, rebuild on failure)
+struct CuckooHashBuildHip : HipDwarf {  // hash/cuckoo_hash_build.cpp:8-134 (lock-free cuckoo table, rebuild on failure)
+  CuckooHashBuildHip() : HipDwarf("CuckooHashBuildHip") {}
+  void _run(size_t buf_size, Meter &meter) override;
+};
 // the reference's EXPERIMENTAL slab dwarfs: registered by populate_slab_registry() only (the dwarf_bench_slab CLI)
-DBHIP_DECLARE_DWARF(SlabHashBuildHip);        // hash/slab_hash_build.cpp:9-108 (lock-free slab table, insert timed)
-DBHIP_DECLARE_DWARF(SlabProbeHip);            // probe/slab_probe.cpp:9-107 (slab table built untimed, lookups timed)
-DBHIP_DECLARE_DWARF(SlabJoinHip);             // join/slab_join.cpp:10-144 (build and probe timed separately)
+struct SlabHashBuildHip : HipDwarf {  // hash/slab_hash_build.cpp:9-108 (lock-free slab table, insert timed)
+  SlabHashBuildHip() : HipDwarf("SlabHashBuildHip") {}
+  void _run(size_t buf_size, Meter &meter) override;
+};
+struct SlabProbeHip : HipDwarf {  // probe/slab_probe.cpp:9-107 (slab table built untimed, lookups timed)
+  SlabProbeHip() : HipDwarf("SlabProbeHip") {}
+  void _run(size_t buf_size, Meter &meter) override;
+};
+struct SlabJoinHip : HipDwarf {  // join/slab_join.cpp:10-144 (build and probe timed separately)
+  SlabJoinHip() : HipDwarf("SlabJoinHip") {}
+  void _run(size_t buf_size, Meter &meter) override;
+};
 // group-by on arbitrary 32-bit keys (SUM and COUNT): registered by populate_groupby_hash_registry() only (the
 // dwarf_bench_groupby_hash CLI)
-DBHIP_DECLARE_DWARF(GroupByHashHip);          // groupby/groupby.cpp:58-93 (the hash table keyed by the group key)
-
-#undef DBHIP_DECLARE_DWARF
+struct GroupByHashHip : HipDwarf {  // groupby/groupby.cpp:58-93 (the hash table keyed by the group key)
+  GroupByHashHip() : HipDwarf("GroupByHashHip") {}
+  void _run(size_t buf_size, Meter &meter) override;
+};

@@ -12,20 +12,14 @@
 #include <stdexcept>
 
 #include "../../include/dbhip.h"
-#include "bench.hpp"
+#include "errors.hpp"
 
 namespace pjoin {
+using namespace dbench_errors;
 namespace {
 
 using clk = std::chrono::steady_clock;
 
-[[noreturn]] void fail(const std::string &what) { throw DwarfBench::DwarfBenchException(what); }
-void hip_ok(hipError_t e, const char *what) {
-  if (e != hipSuccess) fail(std::string(what) + ": " + hipGetErrorString(e));
-}
-void db_ok(int rc, const char *what) {
-  if (rc != 0) fail(std::string(what) + " failed with status " + std::to_string(rc));
-}
 void nccl_ok(ncclResult_t r, const char *what) {
   if (r != ncclSuccess) fail(std::string(what) + ": " + ncclGetErrorString(r));
 }
@@ -96,7 +90,7 @@ struct Rank {
   size_t part_ws_bytes = 0;
   DevMem rk, rr, sk, sr;            // received pairs
   DevMem join_ws, ids, pos, cnt;
-  DevMem out_rid;                   // radix local join: probe row ids in result order (results are not in received order)
+  DevMem out_rid;                   // probe row ids in result order (the radix join's results are not in received order)
   size_t recv_r = 0, recv_s = 0;    // all sub-joins together
   size_t sub_r[kMaxSub] = {}, sub_s[kMaxSub] = {};  // rows received per sub-join; its rows start at off_r / off_s
   size_t off_r[kMaxSub + 1] = {}, off_s[kMaxSub + 1] = {};
@@ -263,7 +257,7 @@ struct Engine::Impl {
         // radix join: the build side's regions of the workspace depend on the build size alone; the probe side's size is
         // only known after S's counts (plan() has put the planning pass's sizes into sub_s), so the workspace is
         // re-checked then (rel == 1)
-        const size_t need = opt.radix_local ? radix_ws_need(*k, 0) : dbhip_join_workspace_bytes(*std::max_element(k->sub_r, k->sub_r + H));
+        const size_t need = radix_ws_need(*k, 0);
         if (need > k->join_ws.bytes || total * 4 > k->ids.bytes) {
           sync_all();
           k->join_ws.reserve(k->device, need + need / 16);
@@ -276,7 +270,7 @@ struct Engine::Impl {
           k->cnt.reserve(k->device, total * 4 + total / 16 * 4);
           k->out_rid.reserve(k->device, total * 4 + total / 16 * 4);
         }
-        if (opt.radix_local && radix_ws_need(*k, 0) > k->join_ws.bytes) {
+        if (radix_ws_need(*k, 0) > k->join_ws.bytes) {
           // (steady state never gets here: plan() sized the workspace for both sides; growing it would lose the
           //  build side already partitioned into it, so this is a hard error rather than a silent re-run)
           fail("partitioned join: receive sizes changed between the planning pass and a step");
@@ -473,8 +467,7 @@ void Engine::plan() {
     k.recv_r = k.recv_s = k.n_local;
     k.sub_r[0] = k.sub_s[0] = k.n_local;
     k.off_r[1] = k.off_s[1] = k.n_local;
-    k.join_ws.reserve(k.device, m.opt.radix_local ? dbhip_join_radix_workspace_bytes(k.n_local, k.n_local)
-                                                   : dbhip_join_workspace_bytes(k.n_local));
+    k.join_ws.reserve(k.device, dbhip_join_radix_workspace_bytes(k.n_local, k.n_local));
     k.ids.reserve(k.device, k.n_local * 4);
     k.pos.reserve(k.device, k.n_local * 4);
     k.cnt.reserve(k.device, k.n_local * 4);
@@ -502,8 +495,7 @@ void Engine::plan() {
         k->sub_s[h] += m.cell(*k, 1, q, k->id, h);
       }
     }
-  for (auto &k : m.ranks)
-    if (m.opt.radix_local) k->join_ws.reserve(k->device, m.radix_ws_need(*k, 16));  // the headroom the buffers get
+  for (auto &k : m.ranks) k->join_ws.reserve(k->device, m.radix_ws_need(*k, 16));  // the headroom the buffers get
   m.size_receives(0);
   m.size_receives(1);
   m.planned = true;
@@ -518,23 +510,14 @@ StepTimes Engine::step() {
     Rank &k = m.local(0);
     m.set(k);
     hip_ok(hipEventRecord(k.ev_start, k.compute), "hipEventRecord");
-    if (m.opt.radix_local) {
-      db_ok(dbhip_join_radix_partition_u32(0, k.build.as<uint32_t>(), nullptr, k.n_local, k.n_local, k.n_local, k.join_ws.p,
-                                           k.join_ws.bytes, k.compute), "dbhip_join_radix_partition_u32");
-      hip_ok(hipEventRecord(k.ev_build, k.compute), "hipEventRecord");
-      db_ok(dbhip_join_radix_partition_u32(1, k.probe.as<uint32_t>(), nullptr, k.n_local, k.n_local, k.n_local, k.join_ws.p,
-                                           k.join_ws.bytes, k.compute), "dbhip_join_radix_partition_u32");
-      db_ok(dbhip_join_radix_match_u32(k.n_local, k.n_local, k.ids.as<uint32_t>(), k.out_rid.as<uint32_t>(),
-                                       k.pos.as<uint32_t>(), k.cnt.as<uint32_t>(), k.join_ws.p, k.join_ws.bytes, k.compute),
-            "dbhip_join_radix_match_u32");
-    } else {
-      db_ok(dbhip_join_build_u32(k.build.as<uint32_t>(), k.n_local, k.ids.as<uint32_t>(), k.join_ws.p, k.join_ws.bytes, k.compute),
-            "dbhip_join_build_u32");
-      hip_ok(hipEventRecord(k.ev_build, k.compute), "hipEventRecord");
-      db_ok(dbhip_join_probe_u32(k.probe.as<uint32_t>(), k.n_local, k.join_ws.p, k.n_local, k.pos.as<uint32_t>(),
-                                 k.cnt.as<uint32_t>(), k.compute),
-            "dbhip_join_probe_u32");
-    }
+    db_ok(dbhip_join_radix_partition_u32(0, k.build.as<uint32_t>(), nullptr, k.n_local, k.n_local, k.n_local, k.join_ws.p,
+                                         k.join_ws.bytes, k.compute), "dbhip_join_radix_partition_u32");
+    hip_ok(hipEventRecord(k.ev_build, k.compute), "hipEventRecord");
+    db_ok(dbhip_join_radix_partition_u32(1, k.probe.as<uint32_t>(), nullptr, k.n_local, k.n_local, k.n_local, k.join_ws.p,
+                                         k.join_ws.bytes, k.compute), "dbhip_join_radix_partition_u32");
+    db_ok(dbhip_join_radix_match_u32(k.n_local, k.n_local, k.ids.as<uint32_t>(), k.out_rid.as<uint32_t>(),
+                                     k.pos.as<uint32_t>(), k.cnt.as<uint32_t>(), k.join_ws.p, k.join_ws.bytes, k.compute),
+          "dbhip_join_radix_match_u32");
     hip_ok(hipEventRecord(k.ev_done, k.compute), "hipEventRecord");
     hip_ok(hipEventSynchronize(k.ev_build), "hipEventSynchronize");
     t.until_build_done = std::chrono::duration<double, std::micro>(clk::now() - t0).count();
@@ -593,21 +576,15 @@ StepTimes Engine::step() {
       uint32_t *ids = k->ids.as<uint32_t>() + k->off_r[h];
       uint32_t *pos = k->pos.as<uint32_t>() + k->off_s[h], *cnt = k->cnt.as<uint32_t>() + k->off_s[h];
       uint32_t *orid = k->out_rid.as<uint32_t>() + k->off_s[h];
-      if (rel == 0) {
-        if (m.opt.radix_local)  // the received build pairs into the local partitions (the probe side's size is not known yet
-                                // in sub-join 0: the build side's part of the workspace does not depend on it)
-          db_ok(dbhip_join_radix_partition_u32(0, rk, rr, k->sub_r[h], k->sub_r[h], 0, k->join_ws.p, k->join_ws.bytes, k->compute),
-                "dbhip_join_radix_partition_u32");
-        else
-          db_ok(dbhip_join_build_pairs_u32(rk, rr, k->sub_r[h], ids, k->join_ws.p, k->join_ws.bytes, k->compute),
-                "dbhip_join_build_pairs_u32");
-      } else if (m.opt.radix_local) {
+      if (rel == 0) {  // the received build pairs into the local partitions (the probe side's size is not known yet in
+                       // sub-join 0: the build side's part of the workspace does not depend on it)
+        db_ok(dbhip_join_radix_partition_u32(0, rk, rr, k->sub_r[h], k->sub_r[h], 0, k->join_ws.p, k->join_ws.bytes, k->compute),
+              "dbhip_join_radix_partition_u32");
+      } else {
         db_ok(dbhip_join_radix_partition_u32(1, sk, sr, k->sub_s[h], k->sub_r[h], k->sub_s[h], k->join_ws.p, k->join_ws.bytes,
                                              k->compute), "dbhip_join_radix_partition_u32");
         db_ok(dbhip_join_radix_match_u32(k->sub_r[h], k->sub_s[h], ids, orid, pos, cnt, k->join_ws.p, k->join_ws.bytes, k->compute),
               "dbhip_join_radix_match_u32");
-      } else {
-        db_ok(dbhip_join_probe_u32(sk, k->sub_s[h], k->join_ws.p, k->sub_r[h], pos, cnt, k->compute), "dbhip_join_probe_u32");
       }
       hip_ok(hipEventRecord(k->ev_l1[rel][h], k->compute), "hipEventRecord");
     }
@@ -726,23 +703,20 @@ CheckReport Engine::check() {
         db_ok(dbhip_radix_sort_u32(sorted.as<uint32_t>(), tmp.as<uint32_t>(), nr, 8, sort_ws.p, sort_ws.bytes, s),
               "dbhip_radix_sort_u32");
       }
-      // radix local join: results come in the probe side's partition order with their row ids: the probe keys are
+      // the radix join's results come in the probe side's partition order with their row ids: the probe keys are
       // regenerated in that order, and the row ids must be exactly the received ones (multiset fingerprint / permutation)
       DevMem pk_result, perm_ws;
-      const uint32_t *pk_aligned = pkeys + o_s;
       const uint32_t *orid = k.out_rid.as<uint32_t>() + o_s;
-      if (m.opt.radix_local) {
-        pk_result.reserve(k.device, ns * 4);
-        db_ok(dbhip_gen_uniform_at_u32(pk_result.as<uint32_t>(), orid, ns, m.opt.probe_seed, 0, key_hi, s), "dbhip_gen_uniform_at_u32");
-        pk_aligned = pk_result.as<uint32_t>();
-        if (m.direct) {
-          const size_t pb = dbhip_check_permutation_workspace_bytes(ns);
-          perm_ws.reserve(k.device, pb);
-          db_ok(dbhip_check_permutation_u32(orid, ns, res + 8, perm_ws.p, perm_ws.bytes, s), "dbhip_check_permutation_u32");
-        } else {
-          db_ok(dbhip_check_sorted_u32(orid, ns, 0, res + 8, s), "dbhip_check_sorted_u32");
-          db_ok(dbhip_check_sorted_u32(k.sr.as<uint32_t>() + o_s, ns, 0, res + 12, s), "dbhip_check_sorted_u32");
-        }
+      pk_result.reserve(k.device, ns * 4);
+      db_ok(dbhip_gen_uniform_at_u32(pk_result.as<uint32_t>(), orid, ns, m.opt.probe_seed, 0, key_hi, s), "dbhip_gen_uniform_at_u32");
+      const uint32_t *pk_aligned = pk_result.as<uint32_t>();
+      if (m.direct) {
+        const size_t pb = dbhip_check_permutation_workspace_bytes(ns);
+        perm_ws.reserve(k.device, pb);
+        db_ok(dbhip_check_permutation_u32(orid, ns, res + 8, perm_ws.p, perm_ws.bytes, s), "dbhip_check_permutation_u32");
+      } else {
+        db_ok(dbhip_check_sorted_u32(orid, ns, 0, res + 8, s), "dbhip_check_sorted_u32");
+        db_ok(dbhip_check_sorted_u32(k.sr.as<uint32_t>() + o_s, ns, 0, res + 12, s), "dbhip_check_sorted_u32");
       }
       const uint32_t *pos = k.pos.as<uint32_t>() + o_s, *cnt = k.cnt.as<uint32_t>() + o_s, *ids = k.ids.as<uint32_t>() + o_r;
       if (m.direct)  // local row indices: the key of an id is a lookup
@@ -755,10 +729,9 @@ CheckReport Engine::check() {
       h = d2h<uint64_t>(res, 40, k.device);
       if (!m.direct) rep.bad_route += h[2] + h[3];
       rep.bad_rows += h[4];
-      if (m.opt.radix_local) {  // the result's row ids are the received ones, each once
-        if (m.direct) rep.bad_rows += h[8];
-        else if (h[9] != h[13] || h[10] != h[14]) rep.bad_rows += ns ? ns : 1;
-      }
+      // the result's row ids are the received ones, each once
+      if (m.direct) rep.bad_rows += h[8];
+      else if (h[9] != h[13] || h[10] != h[14]) rep.bad_rows += ns ? ns : 1;
       rep.matches += h[5];
     }
     rep.recv_build += k.recv_r;
@@ -793,23 +766,15 @@ Engine::HostShard Engine::download(unsigned i) const {
   Rank &k = m.local(i);
   HostShard h;
   const uint32_t key_hi = static_cast<uint32_t>(m.n ? m.n - 1 : 0);
-  if (m.opt.radix_local) {  // results in the probe side's partition order: row ids from the join, keys regenerated
-    h.probe_row_ids = d2h<uint32_t>(k.out_rid.p, k.recv_s, k.device);
-    DevMem pk;
-    pk.reserve(k.device, k.recv_s * 4);
-    m.set(k);
-    db_ok(dbhip_gen_uniform_at_u32(pk.as<uint32_t>(), k.out_rid.as<uint32_t>(), k.recv_s, m.opt.probe_seed, 0, key_hi, k.compute),
-          "dbhip_gen_uniform_at_u32");
-    hip_ok(hipStreamSynchronize(k.compute), "hipStreamSynchronize");
-    h.probe_keys = d2h<uint32_t>(pk.p, k.recv_s, k.device);
-  } else if (m.direct) {
-    h.probe_keys = d2h<uint32_t>(k.probe.p, k.n_local, k.device);
-    h.probe_row_ids.resize(k.n_local);
-    for (size_t j = 0; j < k.n_local; ++j) h.probe_row_ids[j] = static_cast<uint32_t>(k.lo + j);
-  } else {
-    h.probe_keys = d2h<uint32_t>(k.sk.p, k.recv_s, k.device);
-    h.probe_row_ids = d2h<uint32_t>(k.sr.p, k.recv_s, k.device);
-  }
+  // results in the probe side's partition order: row ids from the join, keys regenerated
+  h.probe_row_ids = d2h<uint32_t>(k.out_rid.p, k.recv_s, k.device);
+  DevMem pk;
+  pk.reserve(k.device, k.recv_s * 4);
+  m.set(k);
+  db_ok(dbhip_gen_uniform_at_u32(pk.as<uint32_t>(), k.out_rid.as<uint32_t>(), k.recv_s, m.opt.probe_seed, 0, key_hi, k.compute),
+        "dbhip_gen_uniform_at_u32");
+  hip_ok(hipStreamSynchronize(k.compute), "hipStreamSynchronize");
+  h.probe_keys = d2h<uint32_t>(pk.p, k.recv_s, k.device);
   h.pos = d2h<uint32_t>(k.pos.p, k.recv_s, k.device);
   h.cnt = d2h<uint32_t>(k.cnt.p, k.recv_s, k.device);
   h.ids = d2h<uint32_t>(k.ids.p, k.recv_r, k.device);
@@ -853,8 +818,6 @@ extern "C" void *dbench_pjoin_create(uint64_t n_total, unsigned rank, unsigned w
                                      int direct_single) {
   try {
     pjoin::Options o;
-    const char *local = std::getenv("DWARF_BENCH_PJOIN_LOCAL");
-    o.radix_local = !(local && std::string(local) == "probe");
     o.world = world;
     o.all_local = false;
     o.rank = rank;

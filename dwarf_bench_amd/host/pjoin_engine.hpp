@@ -4,7 +4,8 @@
 //
 //     compute stream :  partition R |            partition S | local partition R' | local partition S' + match
 //     exchange stream:          counts R | exchange R | counts S | exchange S |
-// (local join = the radix join of include/dbhip.h; with Options::radix_local = false: build R | probe S)
+// (local join = the radix join of include/dbhip.h: both received sides partitioned alike, fused LDS build + probe, no
+// table in HBM)
 //
 // Per rank two HIP streams and events between them; the only host waits inside a step are the two tiny count
 // gathers (the receive sizes must be host integers) and the final sync.  The exchange is ONE RCCL group of
@@ -35,8 +36,6 @@ struct Options {
   const void *nccl_id = nullptr;  // all_local == false: the 128-byte ncclUniqueId every rank passes
   bool force_copy = false;     // all_local: exchange by hipMemcpyPeerAsync even where RCCL could be used
   bool direct_single = false;  // world == 1: plain local join without partition / exchange
-  bool radix_local = true;     // local join = the radix join (both received sides partitioned alike, fused LDS build +
-                               // probe, no table in HBM); false: build + row-ordered probe (the first implementation)
   uint64_t build_seed = 42, probe_seed = 43;  // columns: key_i = mix64(seed, i) % n_total (SURVEY 8d join regime)
   // SUB-JOINS (round 4): every rank's rows are cut by one or two more bits of the rank hash into `sub_joins` (1, 2 or 4)
   // independent joins — equal keys share all hash bits — whose exchanges follow each other on the links while the local
