@@ -28,6 +28,9 @@ SIGNATURES = {
     "dbhip_radix_sort_workspace_bytes": (_sz, [_sz, _int]),
     "dbhip_radix_sort_u32": (_int, [_vp, _vp, _sz, _int, _vp, _sz, _vp]),
     "dbhip_radix_sort_i32": (_int, [_vp, _vp, _sz, _int, _vp, _sz, _vp]),
+    "dbhip_radix_sort_pairs_workspace_bytes": (_sz, [_sz, _int]),
+    "dbhip_radix_sort_pairs_u32": (_int, [_vp, _vp, _vp, _vp, _sz, _int, _int, _vp, _sz, _vp]),
+    "dbhip_radix_sort_pairs_i32": (_int, [_vp, _vp, _vp, _vp, _sz, _int, _int, _vp, _sz, _vp]),
     "dbhip_radix_sort_rank_mode": (_int, []),
     "dbhip_radix_sort_prepare": (_int, [_vp]),
     "dbhip_groupby_sum_u32_workspace_bytes": (_sz, [_sz, _u32]),
@@ -74,6 +77,7 @@ SIGNATURES = {
     "dbhip_check_fingerprint_workspace_bytes": (_sz, [_sz]),
     "dbhip_check_fingerprint_lt_i32": (_int, [_vp, _sz, _i32, _vp, _vp, _sz, _vp]),
     "dbhip_check_sorted_u32": (_int, [_vp, _sz, _int, _vp, _vp]),
+    "dbhip_check_sorted_pairs_u32": (_int, [_vp, _vp, _vp, _sz, _int, _vp, _vp]),
     "dbhip_check_weighted_sum_u32": (_int, [_vp, _vp, _sz, _vp, _vp]),
     "dbhip_check_permutation_workspace_bytes": (_sz, [_sz]),
     "dbhip_check_permutation_u32": (_int, [_vp, _sz, _vp, _vp, _sz, _vp]),

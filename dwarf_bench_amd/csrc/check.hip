@@ -144,6 +144,26 @@ __global__ __launch_bounds__(kCkThreads) void sorted_kernel(const unsigned *__re
   block_add_u64(ksum, result + 2);
 }
 
+// ---- stable sort permutation (key-value sort / argsort) -----------------------------------------------------------------
+// strictly increasing (key, id) pairs whose ids each name a row carrying that key (include/dbhip.h says why that is enough)
+__global__ __launch_bounds__(kCkThreads) void sorted_pairs_kernel(const unsigned *__restrict__ keys_in,
+                                                                  const unsigned *__restrict__ keys_out,
+                                                                  const unsigned *__restrict__ ids_out, size_t n,
+                                                                  unsigned xor_mask, unsigned long long *result) {
+  const size_t stride = static_cast<size_t>(gridDim.x) * kCkThreads;
+  unsigned long long descents = 0, mismatches = 0;
+  for (size_t i = static_cast<size_t>(blockIdx.x) * kCkThreads + threadIdx.x; i < n; i += stride) {
+    const unsigned k = keys_out[i], id = ids_out[i];
+    if (i + 1 < n) {
+      const unsigned a = k ^ xor_mask, b = keys_out[i + 1] ^ xor_mask;
+      if (a > b || (a == b && id >= ids_out[i + 1])) ++descents;
+    }
+    if (id >= n || keys_in[id] != k) ++mismatches;
+  }
+  block_add_u64(descents, result + 0);
+  block_add_u64(mismatches, result + 1);
+}
+
 // ---- weighted sum (group-by) ---------------------------------------------------------------------------------------
 __device__ __forceinline__ unsigned wt0(unsigned k) { return fmix32(k) | 1u; }
 __device__ __forceinline__ unsigned wt1(unsigned k) { return fmix32(k ^ 0x9E3779B9u) | 1u; }
@@ -346,6 +366,20 @@ extern "C" int dbhip_check_sorted_u32(const uint32_t *keys, size_t n, int signed
   if (e != hipSuccess) return static_cast<int>(e);
   if (n == 0) return DBHIP_OK;
   hipLaunchKernelGGL(sorted_kernel, dim3(ck_grid(n, dev)), dim3(kCkThreads), 0, s, keys, n,
+                     signed_order ? 0x80000000u : 0u, reinterpret_cast<unsigned long long *>(result));
+  return launch_status();
+}
+
+extern "C" int dbhip_check_sorted_pairs_u32(const uint32_t *keys_in, const uint32_t *keys_out, const uint32_t *ids_out,
+                                            size_t n, int signed_order, uint64_t *result, dbhip_stream_t stream) {
+  if (!result || n >= (1ull << 32) || (n && (!keys_in || !keys_out || !ids_out))) return DBHIP_EINVAL;
+  const DeviceInfo &dev = current_device_info();
+  if (!dev.ok) return DBHIP_ENODEVICE;
+  hipStream_t s = as_stream(stream);
+  const hipError_t e = fill_async(result, 0, 2 * sizeof(uint64_t), s);
+  if (e != hipSuccess) return static_cast<int>(e);
+  if (n == 0) return DBHIP_OK;
+  hipLaunchKernelGGL(sorted_pairs_kernel, dim3(ck_grid(n, dev)), dim3(kCkThreads), 0, s, keys_in, keys_out, ids_out, n,
                      signed_order ? 0x80000000u : 0u, reinterpret_cast<unsigned long long *>(result));
   return launch_status();
 }

@@ -938,6 +938,379 @@ int radix_sort_entry(unsigned *keys, unsigned *tmp, size_t n, int radix_bits, un
              : radix_sort_impl<4>(keys, tmp, n, xor_mask, workspace, as_stream(stream), dev);
 }
 
+// ---- key-value sort and argsort (dbhip_radix_sort_pairs_*) ------------------------------------------------------------
+// The same passes with a second 32-bit column that travels with the keys.  The up-front histogram, the plan, the chunk
+// histogram and the chunk scan read keys only and are launched as they are; the three kernels that MOVE data have a
+// pairs variant below.  The ranking is the keys-only sort's (rs_rank_rows: stable, both rank modes, the crowded-digit
+// switch), so is the order tripwire; a stable LSD sort of (key, value) pairs has exactly one answer.
+//   * values are not live while a tile is ranked: they are loaded once the digit offsets are known, right before the
+//     re-order, and go through a second LDS tile (s_vals, 32 KiB: 74 KiB per workgroup, two workgroups per CU as in
+//     the keys-only scatter) to the position their key takes.  (Requested one barrier earlier, so that the loads fly
+//     during the digit owners' scan, the ballot-ranking scatter needs 16 bytes of scratch at its 128 VGPRs.)
+//   * argsort (vals_are_row_ids): the FIRST EXECUTED pass — known on the device only: every earlier pass has its skip
+//     flag set — makes the value from the row position instead of loading it; when no pass executes the finalize
+//     kernel writes 0..n-1.  The header is the keys-only one: the flag is derived from the plan's skip flags.
+// Bytes per executed pass: 4n (chunk histogram) + 8n + 8n (scatter) = 20n, argsort's first executed pass 16n.
+__device__ __forceinline__ bool rs_first_executed(const RsHeader *hdr, int pass) {
+  bool first = true;
+  for (int q = 0; q < pass; ++q) first = first && hdr->pass[q].skip != 0;
+  return first;
+}
+
+template <int BITS, bool FULL, bool ARANK>
+__device__ __forceinline__ unsigned rsp_scatter_tile(const unsigned *__restrict__ src, const unsigned *__restrict__ vsrc,
+                                                     unsigned *__restrict__ dst, unsigned *__restrict__ vdst,
+                                                     size_t tile_base, unsigned valid_in_tile, int shift, unsigned xor_mask,
+                                                     bool make_ids, unsigned &running, unsigned (*s_cnt)[1 << BITS],
+                                                     unsigned *s_dexcl, unsigned *s_goff, unsigned *s_wsum, unsigned *s_keys,
+                                                     unsigned *s_vals) {
+  constexpr int kRadix = 1 << BITS;
+  const unsigned tid = threadIdx.x, lane = tid & (kWave - 1), wave = tid / kWave;
+  const unsigned wave_first = wave * kRsWaveKeys + lane;
+  unsigned key[kRsKpt];
+#pragma unroll
+  for (int j = 0; j < kRsKpt; ++j) {
+    const unsigned idx = wave_first + j * kWave;
+    key[j] = (FULL || idx < valid_in_tile) ? src[tile_base + idx] : 0xFFFFFFFFu;
+  }
+  for (int i = tid; i < kRsWaves * kRadix; i += kRsThreads) (&s_cnt[0][0])[i] = 0;
+  __syncthreads();
+
+  unsigned rank[kRsKpt];
+  rs_rank_rows<BITS, !FULL, ARANK>(key, rank, s_cnt[wave], wave_first, valid_in_tile, shift, xor_mask);
+  __syncthreads();
+
+  unsigned tile_count = 0;
+  if (tid < kRadix) {
+#pragma unroll
+    for (int w = 0; w < kRsWaves; ++w) {
+      const unsigned c = s_cnt[w][tid];
+      s_cnt[w][tid] = tile_count;
+      tile_count += c;
+    }
+  }
+  const unsigned incl = wave_inclusive_scan(tile_count);
+  if (lane == kWave - 1) s_wsum[wave] = incl;
+  __syncthreads();
+  unsigned dexcl = incl - tile_count;
+  for (unsigned w = 0; w < wave; ++w) dexcl += s_wsum[w];
+  if (tid < kRadix) {
+    s_dexcl[tid] = dexcl;
+    s_goff[tid] = running - dexcl;
+    running += tile_count;
+  }
+  __syncthreads();
+
+  // ---- the values, loaded late (argsort's first executed pass: the row position)
+  unsigned val[kRsKpt];
+#pragma unroll
+  for (int j = 0; j < kRsKpt; ++j) {
+    const unsigned idx = wave_first + j * kWave;
+    if (make_ids)
+      val[j] = static_cast<unsigned>(tile_base) + idx;
+    else
+      val[j] = (FULL || idx < valid_in_tile) ? vsrc[tile_base + idx] : 0u;
+  }
+
+  // ---- re-order the tile by digit in LDS, both columns to the same position
+#pragma unroll
+  for (int j = 0; j < kRsKpt; ++j) {
+    if (FULL || wave_first + j * kWave < valid_in_tile) {
+      const unsigned d = ((key[j] ^ xor_mask) >> shift) & (kRadix - 1);
+      const unsigned pos = s_dexcl[d] + s_cnt[wave][d] + rank[j];
+      s_keys[pos] = key[j];
+      s_vals[pos] = val[j];
+    }
+  }
+  __syncthreads();
+
+  // ---- write out in digit order: two coalesced stores per position; the order check of rs_scatter_tile
+  const unsigned low_mask = shift + BITS >= 32 ? 0xFFFFFFFFu : (1u << (shift + BITS)) - 1u;
+  unsigned bad = 0;
+#pragma unroll
+  for (int k = 0; k < kRsKpt; ++k) {
+    const unsigned p = k * kRsThreads + tid;
+    if (FULL || p < valid_in_tile) {
+      const unsigned kk = s_keys[p];
+      const unsigned vv = s_vals[p];
+      const unsigned kx = kk ^ xor_mask;
+      const unsigned mine = kx & low_mask;
+      const unsigned left = __builtin_amdgcn_update_dpp(0u, mine, 0x138, 0xf, 0xf, false);
+      bad |= left > mine ? 1u : 0u;
+      const unsigned d = (kx >> shift) & (kRadix - 1);
+      const unsigned at = s_goff[d] + p;
+      dst[at] = kk;
+      vdst[at] = vv;
+    }
+  }
+  __syncthreads();
+  return bad;
+}
+
+template <int BITS, bool ARANK>
+__global__ __launch_bounds__(kRsThreads, DBHIP_RS_WPE) void rsp_chunk_scatter_kernel(
+    unsigned *keys, unsigned *vals, unsigned *tmp, unsigned *vtmp, size_t n, int pass, unsigned xor_mask, unsigned row_ids,
+    RsHeader *hdr, const unsigned *__restrict__ offsets, const unsigned *__restrict__ bases, size_t tiles_per_chunk,
+    size_t num_chunks) {
+  constexpr int kRadix = 1 << BITS;
+  __shared__ unsigned s_cnt[kRsWaves][kRadix];
+  __shared__ unsigned s_dexcl[kRadix];
+  __shared__ unsigned s_goff[kRadix];
+  __shared__ unsigned s_wsum[kRsWaves];
+  __shared__ unsigned s_keys[kRsTile];
+  __shared__ unsigned s_vals[kRsTile];
+
+  const RsPass plan = hdr->pass[pass];
+  if (plan.skip) return;  // uniform over the grid
+  const bool make_ids = row_ids != 0 && rs_first_executed(hdr, pass);  // uniform over the grid
+  const unsigned *__restrict__ src = plan.src_is_tmp ? tmp : keys;
+  const unsigned *__restrict__ vsrc = plan.src_is_tmp ? vtmp : vals;
+  unsigned *__restrict__ dst = plan.src_is_tmp ? keys : tmp;
+  unsigned *__restrict__ vdst = plan.src_is_tmp ? vals : vtmp;
+  const int shift = pass * BITS;
+
+  const unsigned tid = threadIdx.x;
+  const size_t per_xcd = (num_chunks + 7) / 8;  // XCD-aware chunk order, as in rs_chunk_scatter_kernel
+  const size_t chunk = (blockIdx.x % 8u) * per_xcd + blockIdx.x / 8u;
+  if (chunk >= num_chunks || blockIdx.x / 8u >= per_xcd) return;
+  const size_t first_tile = chunk * tiles_per_chunk;
+  const size_t total_tiles = (n + kRsTile - 1) / kRsTile;
+  size_t last_tile = first_tile + tiles_per_chunk;
+  last_tile = last_tile < total_tiles ? last_tile : total_tiles;
+  unsigned running = 0;
+  if (tid < kRadix) {
+    if (bases) {
+      running = bases[pass * kRsMaxRadix + tid];
+      const unsigned *row = offsets + static_cast<size_t>(tid) * rs_row_stride(num_chunks);
+      for (size_t c = 0; c < chunk; ++c) running += row[c];
+    } else {
+      running = offsets[static_cast<size_t>(tid) * rs_row_stride(num_chunks) + chunk];
+    }
+  }
+  unsigned bad = 0;
+  for (size_t tile = first_tile; tile < last_tile; ++tile) {
+    const size_t tile_base = tile * kRsTile;
+    const unsigned valid_in_tile = static_cast<unsigned>(n - tile_base < kRsTile ? n - tile_base : kRsTile);
+    if (valid_in_tile == kRsTile)
+      bad |= rsp_scatter_tile<BITS, true, ARANK>(src, vsrc, dst, vdst, tile_base, valid_in_tile, shift, xor_mask, make_ids,
+                                                 running, s_cnt, s_dexcl, s_goff, s_wsum, s_keys, s_vals);
+    else
+      bad |= rsp_scatter_tile<BITS, false, ARANK>(src, vsrc, dst, vdst, tile_base, valid_in_tile, shift, xor_mask, make_ids,
+                                                  running, s_cnt, s_dexcl, s_goff, s_wsum, s_keys, s_vals);
+  }
+  if (bad) atomicOr(&hdr->status, DBHIP_DEV_RANK_ORDER);
+}
+
+// n <= one tile: both columns stay in registers between the passes of one workgroup (rs_single_tile_kernel with values)
+template <int BITS, bool ARANK>
+__global__ __launch_bounds__(kRsThreads, DBHIP_RS_WPE) void rsp_single_tile_kernel(unsigned *keys, unsigned *vals, unsigned n,
+                                                                                   unsigned xor_mask, unsigned row_ids,
+                                                                                   unsigned *status) {
+  constexpr int kRadix = 1 << BITS;
+  constexpr int kPasses = 32 / BITS;
+  __shared__ unsigned s_cnt[kRsWaves][kRadix];
+  __shared__ unsigned s_dexcl[kRadix];
+  __shared__ unsigned s_wsum[kRsWaves];
+  __shared__ unsigned s_keys[kRsTile];
+  __shared__ unsigned s_vals[kRsTile];
+  __shared__ unsigned s_or, s_and;
+  const unsigned tid = threadIdx.x, lane = tid & (kWave - 1), wave = tid / kWave;
+  const unsigned wave_first = wave * kRsWaveKeys + lane;
+
+  unsigned key[kRsKpt], val[kRsKpt];
+  unsigned my_or = 0, my_and = ~0u;
+#pragma unroll
+  for (int j = 0; j < kRsKpt; ++j) {
+    const unsigned idx = wave_first + j * kWave;
+    key[j] = idx < n ? keys[idx] : 0xFFFFFFFFu;
+    if (row_ids)
+      val[j] = idx;
+    else
+      val[j] = idx < n ? vals[idx] : 0u;
+    if (idx < n) {
+      my_or |= key[j];
+      my_and &= key[j];
+    }
+  }
+  if (tid == 0) {
+    s_or = 0;
+    s_and = ~0u;
+  }
+  __syncthreads();
+  atomicOr(&s_or, my_or);
+  atomicAnd(&s_and, my_and);
+  __syncthreads();
+  const unsigned varying = s_or ^ s_and;
+
+  unsigned bad = 0;
+  for (int pass = 0; pass < kPasses; ++pass) {
+    const int shift = pass * BITS;
+    if (((varying >> shift) & (kRadix - 1)) == 0) continue;
+    const unsigned low_mask = shift + BITS >= 32 ? 0xFFFFFFFFu : (1u << (shift + BITS)) - 1u;
+    for (int i = tid; i < kRsWaves * kRadix; i += kRsThreads) (&s_cnt[0][0])[i] = 0;
+    __syncthreads();
+    unsigned rank[kRsKpt];
+    rs_rank_rows<BITS, true, ARANK>(key, rank, s_cnt[wave], wave_first, n, shift, xor_mask);
+    __syncthreads();
+    unsigned tile_count = 0;
+    if (tid < kRadix) {
+#pragma unroll
+      for (int w = 0; w < kRsWaves; ++w) {
+        const unsigned c = s_cnt[w][tid];
+        s_cnt[w][tid] = tile_count;
+        tile_count += c;
+      }
+    }
+    const unsigned incl = wave_inclusive_scan(tile_count);
+    if (lane == kWave - 1) s_wsum[wave] = incl;
+    __syncthreads();
+    unsigned dexcl = incl - tile_count;
+    for (unsigned w = 0; w < wave; ++w) dexcl += s_wsum[w];
+    if (tid < kRadix) s_dexcl[tid] = dexcl;
+    __syncthreads();
+#pragma unroll
+    for (int j = 0; j < kRsKpt; ++j) {
+      if (wave_first + j * kWave < n) {
+        const unsigned d = ((key[j] ^ xor_mask) >> shift) & (kRadix - 1);
+        const unsigned pos = s_dexcl[d] + s_cnt[wave][d] + rank[j];
+        s_keys[pos] = key[j];
+        s_vals[pos] = val[j];
+      }
+    }
+    __syncthreads();
+#pragma unroll
+    for (int j = 0; j < kRsKpt; ++j) {
+      const unsigned idx = wave_first + j * kWave;
+      key[j] = idx < n ? s_keys[idx] : 0xFFFFFFFFu;
+      val[j] = idx < n ? s_vals[idx] : 0u;
+      if (idx < n && idx > 0)  // the same order check as in rs_scatter_tile
+        bad |= ((s_keys[idx - 1] ^ xor_mask) & low_mask) > ((key[j] ^ xor_mask) & low_mask) ? 1u : 0u;
+    }
+    __syncthreads();
+  }
+  if (bad) atomicOr(status, DBHIP_DEV_RANK_ORDER);
+#pragma unroll
+  for (int j = 0; j < kRsKpt; ++j) {
+    const unsigned idx = wave_first + j * kWave;
+    if (idx < n) {
+      keys[idx] = key[j];
+      vals[idx] = val[j];
+    }
+  }
+}
+
+// both columns tmp -> result when an odd number of passes ran; argsort with no executed pass: vals = 0..n-1
+__global__ __launch_bounds__(kRsThreads) void rsp_finalize_kernel(unsigned *__restrict__ keys, unsigned *__restrict__ vals,
+                                                                  const unsigned *__restrict__ tmp,
+                                                                  const unsigned *__restrict__ vtmp, size_t n,
+                                                                  unsigned row_ids, int passes, const RsHeader *hdr) {
+  const size_t stride = static_cast<size_t>(gridDim.x) * kRsThreads;
+  const size_t first = static_cast<size_t>(blockIdx.x) * kRsThreads + threadIdx.x;
+  const size_t n4 = n / 4;
+  if (!hdr->final_in_tmp) {
+    if (!row_ids || !rs_first_executed(hdr, passes)) return;
+    u32x4 *v4 = reinterpret_cast<u32x4 *>(vals);
+    for (size_t i = first; i < n4; i += stride) {
+      const unsigned b = static_cast<unsigned>(i * 4);
+      v4[i] = u32x4{b, b + 1, b + 2, b + 3};
+    }
+    if (blockIdx.x == 0 && threadIdx.x < (n & 3)) vals[n4 * 4 + threadIdx.x] = static_cast<unsigned>(n4 * 4 + threadIdx.x);
+    return;
+  }
+  const u32x4 *s4 = reinterpret_cast<const u32x4 *>(tmp);
+  const u32x4 *sv4 = reinterpret_cast<const u32x4 *>(vtmp);
+  u32x4 *d4 = reinterpret_cast<u32x4 *>(keys);
+  u32x4 *dv4 = reinterpret_cast<u32x4 *>(vals);
+  for (size_t i = first; i < n4; i += stride) {
+    d4[i] = s4[i];
+    dv4[i] = sv4[i];
+  }
+  if (blockIdx.x == 0 && threadIdx.x < (n & 3)) {
+    keys[n4 * 4 + threadIdx.x] = tmp[n4 * 4 + threadIdx.x];
+    vals[n4 * 4 + threadIdx.x] = vtmp[n4 * 4 + threadIdx.x];
+  }
+}
+
+template <int BITS>
+int radix_sort_pairs_impl(unsigned *keys, unsigned *vals, unsigned *tmp, unsigned *vtmp, size_t n, unsigned xor_mask,
+                          unsigned row_ids, void *workspace, hipStream_t s, const DeviceInfo &dev) {
+  constexpr int kPasses = 32 / BITS;
+  constexpr int kRadix = 1 << BITS;
+  const RsGeometry g = rs_geometry(n, BITS);
+  char *base = static_cast<char *>(workspace);
+  RsHeader *hdr = reinterpret_cast<RsHeader *>(base);
+  unsigned *totals = reinterpret_cast<unsigned *>(base + kRsTotalsOff);
+  unsigned *bases = reinterpret_cast<unsigned *>(base + kRsBasesOff);
+  unsigned *counts = reinterpret_cast<unsigned *>(base + kRsCountsOff);
+
+  const bool arank = rank_by_lds_atomics();
+  if (n <= static_cast<size_t>(kRsTile)) {
+    const hipError_t e0 = fill_async(workspace, 0, kWsHeader, s);
+    if (e0 != hipSuccess) return static_cast<int>(e0);
+    if (arank)
+      hipLaunchKernelGGL((rsp_single_tile_kernel<BITS, true>), dim3(1), dim3(kRsThreads), 0, s, keys, vals,
+                         static_cast<unsigned>(n), xor_mask, row_ids, &hdr->status);
+    else
+      hipLaunchKernelGGL((rsp_single_tile_kernel<BITS, false>), dim3(1), dim3(kRsThreads), 0, s, keys, vals,
+                         static_cast<unsigned>(n), xor_mask, row_ids, &hdr->status);
+    return launch_status();
+  }
+  hipError_t e = fill_async(workspace, 0, kRsCountsOff, s);
+  if (e != hipSuccess) return static_cast<int>(e);
+
+  const size_t want = (n / 4 + kRsThreads - 1) / kRsThreads;
+  const size_t cap = static_cast<size_t>(dev.cus) * 4;
+  const unsigned hgrid = static_cast<unsigned>(want < cap ? (want ? want : 1) : cap);
+  const size_t hist_groups = (g.chunks + rs_hist_cpw<BITS>() - 1) / rs_hist_cpw<BITS>();
+  const unsigned hist_grid = static_cast<unsigned>(hist_groups < cap ? hist_groups : cap);
+  hipLaunchKernelGGL((rs_histogram_kernel<BITS>), dim3(hist_grid), dim3(kRsThreads), 0, s, keys, n, xor_mask, totals,
+                     counts, g.tiles_per_chunk, g.chunks);
+  hipLaunchKernelGGL((rs_plan_kernel<BITS>), dim3(1), dim3(kRsThreads), 0, s, n, hdr, totals, bases);
+  const unsigned cgrid = static_cast<unsigned>(g.chunks);
+  const bool fused_scan = g.chunks <= kRsFusedScanChunks;
+  for (int p = 0; p < kPasses; ++p) {
+    if (p > 0)
+      hipLaunchKernelGGL((rs_chunk_hist_kernel<BITS>), dim3((cgrid + rs_hist_cpw<BITS>() - 1) / rs_hist_cpw<BITS>()),
+                         dim3(kRsThreads), 0, s, keys, tmp, n, p, xor_mask, hdr, counts, g.tiles_per_chunk, g.chunks);
+    if (!fused_scan)
+      hipLaunchKernelGGL((rs_chunk_scan_kernel<BITS>), dim3(kRadix), dim3(kRsThreads), 0, s, p, hdr, bases, counts,
+                         g.chunks);
+    const unsigned *fused_bases = fused_scan ? bases : static_cast<const unsigned *>(nullptr);
+    if (arank)
+      hipLaunchKernelGGL((rsp_chunk_scatter_kernel<BITS, true>), dim3((cgrid + 7) / 8 * 8), dim3(kRsThreads), 0, s, keys,
+                         vals, tmp, vtmp, n, p, xor_mask, row_ids, hdr, counts, fused_bases, g.tiles_per_chunk, g.chunks);
+    else
+      hipLaunchKernelGGL((rsp_chunk_scatter_kernel<BITS, false>), dim3((cgrid + 7) / 8 * 8), dim3(kRsThreads), 0, s, keys,
+                         vals, tmp, vtmp, n, p, xor_mask, row_ids, hdr, counts, fused_bases, g.tiles_per_chunk, g.chunks);
+  }
+  hipLaunchKernelGGL(rsp_finalize_kernel, dim3(hgrid), dim3(kRsThreads), 0, s, keys, vals, tmp, vtmp, n, row_ids, kPasses,
+                     hdr);
+  return launch_status();
+}
+
+int radix_sort_pairs_entry(unsigned *keys, unsigned *vals, unsigned *tmp, unsigned *vtmp, size_t n, int radix_bits,
+                           unsigned xor_mask, int vals_are_row_ids, void *workspace, size_t workspace_bytes,
+                           dbhip_stream_t stream) {
+  if (radix_bits != 4 && radix_bits != 8) return DBHIP_EINVAL;
+  if (n >= (1ull << 32)) return DBHIP_EINVAL;  // 32-bit offsets and row ids
+  if (n == 0) {
+    if (workspace && ws_ok(workspace, workspace_bytes, kWsHeader))
+      return static_cast<int>(fill_async(workspace, 0, kWsHeader, as_stream(stream)));
+    return DBHIP_OK;
+  }
+  if (!keys || !vals || !tmp || !vtmp) return DBHIP_EINVAL;
+  if ((reinterpret_cast<uintptr_t>(keys) | reinterpret_cast<uintptr_t>(vals) | reinterpret_cast<uintptr_t>(tmp) |
+       reinterpret_cast<uintptr_t>(vtmp)) & 15u)
+    return DBHIP_EINVAL;  // dbhip.h: 16-byte aligned
+  if (!ws_ok(workspace, workspace_bytes, dbhip_radix_sort_pairs_workspace_bytes(n, radix_bits))) return DBHIP_EWORKSPACE;
+  const DeviceInfo &dev = current_device_info();
+  if (!dev.ok) return DBHIP_ENODEVICE;
+  const unsigned row_ids = vals_are_row_ids ? 1u : 0u;
+  return radix_bits == 8
+             ? radix_sort_pairs_impl<8>(keys, vals, tmp, vtmp, n, xor_mask, row_ids, workspace, as_stream(stream), dev)
+             : radix_sort_pairs_impl<4>(keys, vals, tmp, vtmp, n, xor_mask, row_ids, workspace, as_stream(stream), dev);
+}
+
 }  // namespace
 }  // namespace dbhip
 
@@ -990,4 +1363,23 @@ extern "C" int dbhip_radix_sort_i32(int32_t *keys, int32_t *tmp, size_t n, int r
   // signed order = unsigned order with the sign bit flipped (applied on the fly, keys unchanged)
   return radix_sort_entry(reinterpret_cast<unsigned *>(keys), reinterpret_cast<unsigned *>(tmp), n,
                           radix_bits, 0x80000000u, workspace, workspace_bytes, stream);
+}
+
+// the keys-only layout: the kernels that fill the workspace never see the values
+extern "C" size_t dbhip_radix_sort_pairs_workspace_bytes(size_t n, int radix_bits) {
+  return dbhip_radix_sort_workspace_bytes(n, radix_bits);
+}
+
+extern "C" int dbhip_radix_sort_pairs_u32(uint32_t *keys, uint32_t *vals, uint32_t *tmp_keys, uint32_t *tmp_vals, size_t n,
+                                          int radix_bits, int vals_are_row_ids, void *workspace, size_t workspace_bytes,
+                                          dbhip_stream_t stream) {
+  return radix_sort_pairs_entry(keys, vals, tmp_keys, tmp_vals, n, radix_bits, 0u, vals_are_row_ids, workspace,
+                                workspace_bytes, stream);
+}
+
+extern "C" int dbhip_radix_sort_pairs_i32(int32_t *keys, uint32_t *vals, int32_t *tmp_keys, uint32_t *tmp_vals, size_t n,
+                                          int radix_bits, int vals_are_row_ids, void *workspace, size_t workspace_bytes,
+                                          dbhip_stream_t stream) {
+  return radix_sort_pairs_entry(reinterpret_cast<unsigned *>(keys), vals, reinterpret_cast<unsigned *>(tmp_keys), tmp_vals,
+                                n, radix_bits, 0x80000000u, vals_are_row_ids, workspace, workspace_bytes, stream);
 }

@@ -172,6 +172,8 @@ void populate_experimental_registry();
 void populate_slab_registry();
 // GroupByHashHip: only the dwarf_bench_groupby_hash CLI registers it, after populate_registry()
 void populate_groupby_hash_registry();
+// RadixPairsHip: only the dwarf_bench_sort_pairs CLI registers it, after populate_registry()
+void populate_sort_pairs_registry();
 
 namespace helpers {
 // $DWARF_BENCH_ROOT or the executable's directory (common/common.cpp:38-41, without Boost.DLL)

@@ -382,6 +382,63 @@ void RadixHip::init(const RunOptions &opts) {
 }
 
 // =====================================================================================================
+// RadixPairsHip — the argsort (dbhip_radix_sort_pairs_i32 with vals_are_row_ids): RadixHip's column, the timed region
+// is one call that sorts the keys and returns the stable sort permutation.  No reference counterpart.
+void RadixPairsHip::_run(const size_t n, Meter &meter) {
+  const RunOptions &opts = meter.opts();
+  if (n >= (static_cast<size_t>(1) << 32)) fail("RadixPairsHip: fewer than 2^32 rows");
+  const int bits = [] {
+    const char *e = std::getenv("DWARF_BENCH_RADIX_BITS");
+    return (e && std::atoi(e) == 4) ? 4 : 8;
+  }();
+  DevBuf<int32_t> src(n), keys(n), tmp(n);
+  DevBuf<uint32_t> perm(n), tmp_perm(n);
+  const size_t ws_bytes = dbhip_radix_sort_pairs_workspace_bytes(n, bits);
+  DevBuf<unsigned char> ws(ws_bytes);
+  db_ok(dbhip_gen_uniform_u32(reinterpret_cast<uint32_t *>(src.get()), n, 42, 0, 1, 10000, nullptr), "gen");
+  hip_ok(hipDeviceSynchronize(), "sync");
+  const bool host_check = n <= validate_limit();
+  std::vector<int32_t> expected_keys;
+  std::vector<uint32_t> expected_perm;
+  CheckWords chk;
+  if (host_check) {  // the stable sort of (key, row) pairs
+    const std::vector<int32_t> h = src.to_host(n);
+    expected_perm.resize(n);
+    for (size_t i = 0; i < n; ++i) expected_perm[i] = static_cast<uint32_t>(i);
+    std::stable_sort(expected_perm.begin(), expected_perm.end(), [&](uint32_t a, uint32_t b) { return h[a] < h[b]; });
+    expected_keys.resize(n);
+    for (size_t i = 0; i < n; ++i) expected_keys[i] = h[expected_perm[i]];
+  }
+  Events ev;
+  for (size_t it = 0; it < opts.iterations; ++it) {
+    hip_ok(hipMemcpy(keys.get(), src.get(), n * sizeof(int32_t), hipMemcpyDeviceToDevice), "refresh");  // not timed
+    auto result = std::make_unique<Result>();
+    time_launch(*result, ev, [&] {
+      db_ok(dbhip_radix_sort_pairs_i32(keys.get(), perm.get(), tmp.get(), tmp_perm.get(), n, bits, 1, ws.get(), ws_bytes,
+                                       nullptr),
+            "dbhip_radix_sort_pairs_i32");
+    });
+    if (n) check_status(ws.get(), "RadixPairsHip");
+    if (inject_fault() && n) poke_xor(perm.get() + n / 2, 1u);  // one id
+    bool ok;
+    if (host_check) {
+      ok = keys.to_host(n) == expected_keys && perm.to_host(n) == expected_perm;
+    } else {  // strictly increasing (key, id) pairs, every id naming a row with that key (include/dbhip.h)
+      db_ok(dbhip_check_sorted_pairs_u32(reinterpret_cast<uint32_t *>(src.get()), reinterpret_cast<uint32_t *>(keys.get()),
+                                         perm.get(), n, 1, chk.dev(), nullptr),
+            "dbhip_check_sorted_pairs_u32");
+      const auto g = chk.get();
+      ok = g[0] == 0 && g[1] == 0;
+    }
+    record(meter, n, std::move(result), ok, "incorrect results");
+  }
+}
+void RadixPairsHip::init(const RunOptions &opts) {
+  HipDwarf::init(opts);
+  (void)dbhip_radix_sort_prepare(nullptr);  // as RadixHip::init
+}
+
+// =====================================================================================================
 // ---- group-by: the buffers and the check shared by GroupByHip and GroupByLocalHip ----------------
 namespace {
 class GroupByBuffers {

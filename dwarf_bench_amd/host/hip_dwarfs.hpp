@@ -100,3 +100,10 @@ struct GroupByHashHip : HipDwarf {  // groupby/groupby.cpp:58-93 (the hash table
   GroupByHashHip() : HipDwarf("GroupByHashHip") {}
   void _run(size_t buf_size, Meter &meter) override;
 };
+// the argsort (key-value radix sort with row ids as values): registered by populate_sort_pairs_registry() only (the
+// dwarf_bench_sort_pairs CLI); no reference counterpart, the reference sorts keys only
+struct RadixPairsHip : HipDwarf {
+  RadixPairsHip() : HipDwarf("RadixPairsHip") {}
+  void init(const RunOptions &opts) override;  // HipDwarf::init, then dbhip_radix_sort_prepare
+  void _run(size_t buf_size, Meter &meter) override;
+};

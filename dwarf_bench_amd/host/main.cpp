@@ -6,7 +6,8 @@
 // Built twice: `dwarf_bench`, and with -DEXPERIMENTAL `dwarf_bench_experimental`, which also registers the reference's
 // EXPERIMENTAL dwarfs that have a HIP counterpart (populate_experimental_registry), and with -DEXPERIMENTAL_SLAB
 // `dwarf_bench_slab`, the default set plus the slab dwarfs (populate_slab_registry), and with -DEXPERIMENTAL_GROUPBY_HASH
-// `dwarf_bench_groupby_hash`, the default set plus GroupByHashHip (populate_groupby_hash_registry).
+// `dwarf_bench_groupby_hash`, the default set plus GroupByHashHip (populate_groupby_hash_registry), and with
+// -DEXPERIMENTAL_SORT_PAIRS `dwarf_bench_sort_pairs`, the default set plus RadixPairsHip (populate_sort_pairs_registry).
 #include <iostream>
 #include <memory>
 #include <sstream>
@@ -44,6 +45,9 @@ int main(int argc, char *argv[]) {
 #endif
 #ifdef EXPERIMENTAL_GROUPBY_HASH
   populate_groupby_hash_registry();  // dwarf_bench_groupby_hash
+#endif
+#ifdef EXPERIMENTAL_SORT_PAIRS
+  populate_sort_pairs_registry();  // dwarf_bench_sort_pairs
 #endif
   Registry *registry = Registry::instance();
 

@@ -54,3 +54,11 @@ void populate_groupby_hash_registry() {
   Registry::instance()->registerd(new GroupByHashHip());
 #endif
 }
+
+// the key-value sort's argsort (dbhip_radix_sort_pairs_i32): only the dwarf_bench_sort_pairs CLI (main.cpp built with
+// -DEXPERIMENTAL_SORT_PAIRS) calls this, so the lists of the other four CLIs stay as they are
+void populate_sort_pairs_registry() {
+#ifdef HIP_ENABLED
+  Registry::instance()->registerd(new RadixPairsHip());
+#endif
+}

@@ -163,6 +163,56 @@ def radix_sort_(keys: torch.Tensor, signed: bool = False, radix_bits: int = 8) -
     return keys
 
 
+class RadixSortPairs:
+    """Stable key-value sort / argsort plan (dbhip_radix_sort_pairs_*): owns the workspace, both ping-pong buffers and
+    the permutation buffer of the argsort."""
+
+    def __init__(self, n: int, radix_bits: int = 8, device="cuda"):
+        self.n, self.bits = n, radix_bits
+        self.ws_bytes = _capi.lib().dbhip_radix_sort_pairs_workspace_bytes(n, radix_bits)
+        self.ws = _ws(self.ws_bytes, device)
+        self.tmp_keys = torch.empty(max(n, 1), dtype=torch.int32, device=device)
+        self.tmp_vals = torch.empty(max(n, 1), dtype=torch.int32, device=device)
+        self.perm = torch.empty(max(n, 1), dtype=torch.int32, device=device)
+
+    def launch(self, keys: torch.Tensor, vals: torch.Tensor | None = None, signed: bool = False) -> torch.Tensor:
+        """Asynchronous.  Sorts `keys` in place (signed=False orders the bits as uint32) and carries `vals` along, in
+        place; vals=None is the argsort: the stable sort permutation goes to the plan's buffer.  Returns the value
+        column (vals, or self.perm[:n]: int32 storage of uint32 ids)."""
+        _need(keys, torch.int32, "keys")
+        _need16(keys, "keys")
+        if keys.numel() != self.n:
+            raise ValueError("size mismatch")
+        row_ids = vals is None
+        if row_ids:
+            vals = self.perm[:self.n]
+        else:
+            _need(vals, torch.int32, "vals")
+            _need16(vals, "vals")
+            if vals.numel() != self.n:
+                raise ValueError("size mismatch")
+        fn = _capi.lib().dbhip_radix_sort_pairs_i32 if signed else _capi.lib().dbhip_radix_sort_pairs_u32
+        _capi.check(fn(keys.data_ptr(), vals.data_ptr(), self.tmp_keys.data_ptr(), self.tmp_vals.data_ptr(), self.n,
+                       self.bits, int(row_ids), self.ws.data_ptr(), self.ws_bytes, _stream()), "radix_sort_pairs")
+        return vals
+
+
+def radix_sort_pairs_(keys: torch.Tensor, vals: torch.Tensor, signed: bool = False, radix_bits: int = 8):
+    """Stable sort of (keys, vals) by key, both in place -> (keys, vals)."""
+    plan = RadixSortPairs(keys.numel(), radix_bits, keys.device)
+    plan.launch(keys, vals, signed)
+    _check_status(plan.ws, "radix_sort_pairs")
+    return keys, vals
+
+
+def radix_argsort_(keys: torch.Tensor, signed: bool = False, radix_bits: int = 8) -> torch.Tensor:
+    """Sorts `keys` in place and returns the stable sort permutation (int32 storage of uint32 row ids)."""
+    plan = RadixSortPairs(keys.numel(), radix_bits, keys.device)
+    perm = plan.launch(keys, None, signed)
+    _check_status(plan.ws, "radix_sort_pairs")
+    return perm
+
+
 # ---------------------------------------------------------------------------------------------
 # dwarf 3: group-by SUM
 # ---------------------------------------------------------------------------------------------
@@ -776,6 +826,20 @@ def check_sorted(keys: torch.Tensor, signed: bool = False):
     res = _result(3, keys.device)
     _capi.check(_capi.lib().dbhip_check_sorted_u32(keys.data_ptr(), keys.numel(), int(signed), res.data_ptr(), _stream()),
                 "check_sorted_u32")
+    return tuple(_u64(res))
+
+
+def check_sorted_pairs(keys_in: torch.Tensor, keys_out: torch.Tensor, ids_out: torch.Tensor, signed: bool = False):
+    """-> (descents of the (key, id) pairs, ids out of range or naming a row with another key); (0, 0) iff ids_out is
+    the stable sort permutation of keys_in and keys_out the sorted column"""
+    for t, name in ((keys_in, "keys_in"), (keys_out, "keys_out"), (ids_out, "ids_out")):
+        _need(t, torch.int32, name)
+    if keys_out.numel() != keys_in.numel() or ids_out.numel() != keys_in.numel():
+        raise ValueError("size mismatch")
+    res = _result(2, keys_in.device)
+    _capi.check(_capi.lib().dbhip_check_sorted_pairs_u32(keys_in.data_ptr(), keys_out.data_ptr(), ids_out.data_ptr(),
+                                                         keys_in.numel(), int(signed), res.data_ptr(), _stream()),
+                "check_sorted_pairs_u32")
     return tuple(_u64(res))
 
 

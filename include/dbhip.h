@@ -36,6 +36,7 @@
  *                             probe/slab_probe.cpp, join/slab_join.cpp:10-144, tests/slab_tests.cpp
  *   dbhip_reduce_sum_i32      reduce/reduce.cpp:27-88
  *   dbhip_nested_join_u32     join/nested_join.cpp:52-66
+ *   dbhip_radix_sort_pairs_*  no reference counterpart (the reference sorts keys only, dpl_wrapper.hpp:35-39)
  *   dbhip_pjoin_*             no reference counterpart (multi-GPU radix-partitioned join)
  *   dbhip_gen_*               common/common.hpp:31-40, common/common.cpp:7-20 (data generators)
  *   dbhip_exclusive_scan_u32  scan/scan.cl:44-66, tests/scan_tests.cpp:14-21, dpl_wrapper.hpp:18-25 (exclusive_scan)
@@ -149,6 +150,31 @@ int dbhip_radix_sort_rank_mode(void);
  * resulting rank mode (1 / 0), DBHIP_EINVAL while `stream` is being captured, or an error code.  The sort entry
  * points never call it and never synchronise.                                                                    */
 int dbhip_radix_sort_prepare(dbhip_stream_t stream);
+
+/* ---- dwarf 2, key-value sort and argsort (no reference counterpart: the reference sorts keys only) ----------
+ * Ascending STABLE sort of n (key, value) pairs, both columns in place: keys ends up ascending (_u32 as unsigned, _i32 as
+ * signed: the sign bit is flipped on the fly as in dbhip_radix_sort_i32, keys unchanged), vals[i] is the value that
+ * travelled with keys[i], equal keys keep their input order.  The result is therefore unique:
+ * vals_out == vals_in[argsort_stable(keys_in)].  vals is 32 bits of anything, no value is special.  tmp_keys and tmp_vals
+ * are n-element ping-pong buffers.
+ *   vals_are_row_ids != 0  the argsort: vals is treated as holding 0..n-1 on entry and is NEVER READ (the first executed
+ *                          pass makes the ids from the row position: 4n bytes of reads saved); on return vals is the
+ *                          stable sort permutation.  Also when no pass executes (all keys equal, n == 1, every digit
+ *                          constant): vals = 0..n-1, keys unchanged.
+ * radix_bits in {4, 8}; n < 2^32 (the keys-only bound: row ids then fit 32 bits); all four buffers 16-byte aligned.
+ * DBHIP_EINVAL: a NULL buffer with n > 0, other radix_bits, n >= 2^32, a misaligned buffer; DBHIP_EWORKSPACE: a short or
+ * misaligned workspace — all before any HIP call.  n == 0 is DBHIP_OK (a workspace that was passed gets a clean status
+ * word).  Never allocates, never synchronises, can be captured; ranks as dbhip_radix_sort_rank_mode() says, and every
+ * tile runs the order check of the keys-only sort (DBHIP_DEV_RANK_ORDER); skipped passes are decided on the device.
+ * The workspace is the keys-only layout (the kernels that fill it never see the values): the query returns
+ * dbhip_radix_sort_workspace_bytes(n, radix_bits).                                                               */
+size_t dbhip_radix_sort_pairs_workspace_bytes(size_t n, int radix_bits);
+int dbhip_radix_sort_pairs_u32(uint32_t *keys, uint32_t *vals, uint32_t *tmp_keys, uint32_t *tmp_vals, size_t n,
+                               int radix_bits, int vals_are_row_ids, void *workspace, size_t workspace_bytes,
+                               dbhip_stream_t stream);
+int dbhip_radix_sort_pairs_i32(int32_t *keys, uint32_t *vals, int32_t *tmp_keys, uint32_t *tmp_vals, size_t n,
+                               int radix_bits, int vals_are_row_ids, void *workspace, size_t workspace_bytes,
+                               dbhip_stream_t stream);
 
 /* ---- dwarf 3: group-by hash aggregate, SUM ------------------------------------------------------
  * out[g] = sum of vals[i] over rows with keys[i] == g (uint32 wrap-around), g in [0, groups).
@@ -431,7 +457,14 @@ int dbhip_exclusive_scan_u32(const uint32_t *src, size_t n, uint32_t init, uint3
  *                       the workspace): 0 iff the keys are distinct.  A group-by output (dbhip_groupby_hash_u32) is right
  *                       iff its keys are distinct, weighted_sum over (out_keys, out_sums) equals weighted_sum over
  *                       (keys, vals), the same holds for (out_keys, out_counts) against a column of ones, and the counts
- *                       sum to n.                                                                        */
+ *                       sum to n.
+ *   sorted_pairs_u32    (n < 2^32) result[0] = number of i < n-1 with (keys_out[i], ids_out[i]) >= (keys_out[i+1],
+ *                       ids_out[i+1]), compared lexicographically, keys as int32 when signed_order != 0; result[1] =
+ *                       number of i with ids_out[i] >= n or keys_in[ids_out[i]] != keys_out[i].  Both zero iff ids_out is
+ *                       the stable sort permutation of keys_in and keys_out the sorted column: strictly increasing
+ *                       pairs are n distinct pairs, and as every id names a row that carries the key beside it, equal
+ *                       ids would make equal pairs — so the ids are n distinct values below n, a permutation; keys_out
+ *                       is keys_in under it, ascending, and ties stand in row order.                        */
 size_t dbhip_check_fingerprint_workspace_bytes(size_t n);
 int dbhip_check_fingerprint_lt_i32(const int32_t *src, size_t n, int32_t filter_value, uint64_t *result,
                                    void *workspace, size_t workspace_bytes, dbhip_stream_t stream);
@@ -453,6 +486,8 @@ int dbhip_check_ujoin_u32(const uint32_t *sorted_build_keys, const uint32_t *bui
 size_t dbhip_check_distinct_workspace_bytes(size_t n);
 int dbhip_check_distinct_u32(const uint32_t *keys, size_t n, uint64_t *result, void *workspace, size_t workspace_bytes,
                              dbhip_stream_t stream);
+int dbhip_check_sorted_pairs_u32(const uint32_t *keys_in, const uint32_t *keys_out, const uint32_t *ids_out, size_t n,
+                                 int signed_order, uint64_t *result, dbhip_stream_t stream);
 int dbhip_check_gen_uniform_u32(const uint32_t *values, const uint32_t *indices, size_t n, uint64_t seed,
                                 uint64_t first_index, uint32_t lo, uint32_t hi, uint64_t *result,
                                 dbhip_stream_t stream);

@@ -6,6 +6,11 @@ the contract numbers come from bench.py.
 
   scan            two-launch vs dense copy_if at 2^28 rows over a selectivity sweep (median of 9)
   sort [lg]       2^lg-key sort, 8- and 4-bit digits (drop-max-mean of 9, refresh copy subtracted); default lg 24
+  sort-pairs [lg] key-value sort and argsort (dbhip_radix_sort_pairs_*), 8- and 4-bit digits, at 2^20 / 2^24 / 2^26 rows (or
+                  2^lg alone), full-range keys and keys in [1, 10000]; beside them, in the same run, the keys-only sort and
+                  torch.sort(stable=True) (which returns 8-byte indices) (median of 9, refresh copy subtracted); every
+                  column of every mode checked against torch's stable sort
+  launch-sort-pairs [lg]  five 8-bit argsorts of 2^lg full-range keys (default 24) and nothing else (`rocprofv3 --kernel-trace`)
   sort-only       three 2^24 sorts and nothing else (counter collection; SORT_BITS=4|8, SORT_SHAPE=<index into sort-shapes' list>)
   groupby         2^26 rows at 2^16 / 2^15 / 2^10 / 64 groups (drop-max-mean of 9)
   groupby-shapes  more than 32768 groups over row counts, group counts and value ranges (median of 5): run it with
@@ -109,6 +114,61 @@ def sort(lg):
         ok = bool(torch.equal(u64(keys), ref)) and ops.workspace_status(plan.ws) == 0
         res.append(f"{bits}-bit {t:7.1f} us {'ok' if ok else 'WRONG'}")
     print(f"{TAG:24s} 2^{lg or 24}: " + "   ".join(res), flush=True)
+
+
+def sort_pairs(lg):
+    for n in ([1 << lg] if lg else [1 << 20, 1 << 24, 1 << 26]):
+        for lo, hi, name in ((0, 2**32 - 1, "full-range"), (1, 10000, "[1,10000]")):
+            keys0 = ops.gen_uniform_u32(n, 42, lo, hi)
+            vals0 = ops.gen_uniform_u32(n, 43, 0, 2**32 - 1)
+            keys, vals = keys0.clone(), vals0.clone()
+            ref = torch.sort(u64(keys0), stable=True)
+            copy_k = median(times(lambda: keys.copy_(keys0), 9))
+            copy_kv = median(times(lambda: (keys.copy_(keys0), vals.copy_(vals0)), 9))
+            t_torch = median(times(lambda: torch.sort(u64(keys0), stable=True), 5))
+            res = []
+            for bits in (8, 4):
+                plan, ko = ops.RadixSortPairs(n, bits), ops.RadixSort(n, bits)
+
+                def pairs():
+                    keys.copy_(keys0)
+                    vals.copy_(vals0)
+                    plan.launch(keys, vals)
+
+                def argsort():
+                    keys.copy_(keys0)
+                    plan.launch(keys)
+
+                def keys_only():
+                    keys.copy_(keys0)
+                    ko.launch(keys)
+
+                t_p = median(times(pairs, 9)) - copy_kv
+                pairs()
+                ok_p = torch.equal(u64(keys), ref.values) and torch.equal(vals, vals0[ref.indices]) and ops.workspace_status(plan.ws) == 0
+                t_a = median(times(argsort, 9)) - copy_k
+                argsort()
+                ok_a = (torch.equal(u64(keys), ref.values) and torch.equal(u64(plan.perm[:n]), ref.indices) and ops.workspace_status(plan.ws) == 0
+                        and ops.check_sorted_pairs(keys0, keys, plan.perm[:n]) == (0, 0))
+                t_k = median(times(keys_only, 9)) - copy_k
+                keys_only()
+                ok_k = torch.equal(u64(keys), ref.values) and ops.workspace_status(ko.ws) == 0
+                res.append(f"{bits}-bit pairs {t_p:8.1f} us {'ok' if ok_p else 'WRONG'}  argsort {t_a:8.1f} us {'ok' if ok_a else 'WRONG'}  "
+                           f"keys-only {t_k:8.1f} us {'ok' if ok_k else 'WRONG'}  (pairs / keys-only {t_p / t_k:4.2f}, argsort / keys-only {t_a / t_k:4.2f})")
+            for r in res:
+                print(f"{TAG:12s} n={n:9d} {name:10s} {r}   torch.sort(stable) {t_torch:8.1f} us", flush=True)
+            del keys0, vals0, keys, vals, ref
+
+
+def launch_sort_pairs(lg):
+    n = 1 << (lg or 24)
+    keys0 = ops.gen_uniform_u32(n, 42, 0, 2**32 - 1)
+    plan = ops.RadixSortPairs(n, 8)
+    for _i in range(5):
+        k = keys0.clone()
+        plan.launch(k)
+    torch.cuda.synchronize()
+    print("ok" if ops.workspace_status(plan.ws) == 0 and ops.check_sorted_pairs(keys0, k, plan.perm[:n]) == (0, 0) else "WRONG")
 
 
 def sort_only(_):
@@ -799,7 +859,7 @@ def launch_all(_):
 
 MODES = {"radix": radix, "ramp": ramp, "radix-idle": radix_idle, "radix-stream": radix_stream, "radix-alloc": radix_alloc, "radix-offsets": radix_offsets, "radix-sizes": radix_sizes, "graph": graph, "launch-join": launch_join, "launch-sort": launch_sort, "launch-all": launch_all, "scan": scan, "sort": sort, "sort-only": sort_only, "groupby": groupby, "groupby-shapes": groupby_shapes, "groupby-skew": groupby_skew, "sort-shapes": sort_shapes, "join": join, "join-skew": join_skew, "size-sweep": size_sweep, "partition": partition,
          "reduce": reduce, "xscan": xscan, "cuckoo": cuckoo, "slab": slab,
-         "groupby-hash": groupby_hash}
+         "groupby-hash": groupby_hash, "sort-pairs": sort_pairs, "launch-sort-pairs": launch_sort_pairs}
 
 if __name__ == "__main__":
     if len(sys.argv) < 2 or sys.argv[1] not in MODES:

@@ -2,6 +2,7 @@
 // primitives (rocPRIM) on the workloads of BASELINE.json, on the same box, so that DESIGN.md can say where
 // the hand-written kernels stand next to the vendor library (context for the roofline fractions).
 //   hipcc --offload-arch=gfx950 -O3 -std=c++17 tools/vendor_compare.hip -o tools/_vendor_compare
+//   tools/_vendor_compare [sort]     `sort`: only the radix sort cases (keys, and uint32 keys with uint32 values)
 #include <cstring>
 #include <hip/hip_runtime.h>
 
@@ -56,8 +57,13 @@ static float median_us(F &&f, int iters = 9) {
   return t[t.size() / 2];
 }
 
-int main() {
-  {  // select (copy_if x < 5) on 2^28 int32, reference distribution
+__global__ void iota(uint32_t *out, size_t n) {
+  for (size_t i = blockIdx.x * size_t(blockDim.x) + threadIdx.x; i < n; i += size_t(gridDim.x) * blockDim.x) out[i] = uint32_t(i);
+}
+
+int main(int argc, char **argv) {
+  const bool sort_only = argc > 1 && std::strcmp(argv[1], "sort") == 0;
+  if (!sort_only) {  // select (copy_if x < 5) on 2^28 int32, reference distribution
     const size_t n = size_t(1) << 28;
     int *src, *out;
     size_t *count;
@@ -93,7 +99,7 @@ int main() {
     CK(hipFree(out));
     CK(hipFree(count));
   }
-  for (int lg : {20, 24}) {  // radix sort of uint32 keys
+  for (int lg : {20, 22, 24, 26}) {  // radix sort of uint32 keys
     const size_t n = size_t(1) << lg;
     uint32_t *src, *a, *b;
     CK(hipMalloc(&src, n * 4));
@@ -117,6 +123,40 @@ int main() {
     CK(hipFree(src));
     CK(hipFree(a));
     CK(hipFree(b));
+  }
+  // radix sort of (uint32 key, uint32 value) pairs, values = row ids: the vendor's counterpart of dbhip_radix_sort_pairs_u32.
+  // Input and output columns are separate, so no refresh copy is inside the timed call; the result is checked on the host
+  // (keys ascending, every value a row that carries the key, ties in row order)
+  for (int lg : {20, 22, 24, 26}) {
+    const size_t n = size_t(1) << lg;
+    uint32_t *src, *ids, *ko, *vo;
+    CK(hipMalloc(&src, n * 4));
+    CK(hipMalloc(&ids, n * 4));
+    CK(hipMalloc(&ko, n * 4));
+    CK(hipMalloc(&vo, n * 4));
+    iota<<<4096, 256>>>(ids, n);
+    for (int full = 1; full >= 0; --full) {
+      gen<<<4096, 256>>>(src, n, 42, full ? 0u : 1u, full ? (uint64_t(1) << 32) : 10000ull);
+      size_t tmp_bytes = 0;
+      CK(rocprim::radix_sort_pairs(nullptr, tmp_bytes, src, ko, ids, vo, n));
+      void *tmp;
+      CK(hipMalloc(&tmp, tmp_bytes));
+      const float us = median_us([&] { (void)rocprim::radix_sort_pairs(tmp, tmp_bytes, src, ko, ids, vo, n); });
+      std::vector<uint32_t> hs(n), hk(n), hv(n);
+      CK(hipMemcpy(hs.data(), src, n * 4, hipMemcpyDeviceToHost));
+      CK(hipMemcpy(hk.data(), ko, n * 4, hipMemcpyDeviceToHost));
+      CK(hipMemcpy(hv.data(), vo, n * 4, hipMemcpyDeviceToHost));
+      bool ok = true;
+      for (size_t i = 0; i < n && ok; ++i)
+        ok = hv[i] < n && hs[hv[i]] == hk[i] && (i == 0 || hk[i - 1] < hk[i] || (hk[i - 1] == hk[i] && hv[i - 1] < hv[i]));
+      std::printf("rocprim::radix_sort_pairs n=2^%d %s: %.1f us  %.0f Mpairs/s  %s (temporary storage %zu bytes)\n", lg,
+                  full ? "full-range" : "ref[1,10000]", us, n / us, ok ? "ok" : "WRONG", tmp_bytes);
+      CK(hipFree(tmp));
+    }
+    CK(hipFree(src));
+    CK(hipFree(ids));
+    CK(hipFree(ko));
+    CK(hipFree(vo));
   }
   return 0;
 }
