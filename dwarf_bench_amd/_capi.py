@@ -48,6 +48,8 @@ SIGNATURES = {
     "dbhip_join_radix_match_u32": (_int, [_sz, _sz, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "dbhip_join_radix_u32": (_int, [_vp, _vp, _sz, _vp, _vp, _sz, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "dbhip_join_answers_u32": (_int, [_vp, _vp, _vp, _sz, _vp, _vp]),
+    "dbhip_join_pairs_workspace_bytes": (_sz, [_sz]),
+    "dbhip_join_pairs_u32": (_int, [_vp, _sz, _vp, _vp, _vp, _sz, _int, _u64, _vp, _vp, _vp, _vp, _sz, _vp]),
     "dbhip_ujoin_workspace_bytes": (_sz, [_sz]),
     "dbhip_ujoin_build_u32": (_int, [_vp, _vp, _sz, _vp, _sz, _vp]),
     "dbhip_ujoin_probe_u32": (_int, [_vp, _vp, _sz, _vp, _sz, _vp, _vp, _vp, _vp]),
@@ -85,6 +87,7 @@ SIGNATURES = {
     "dbhip_check_ujoin_u32": (_int, [_vp, _vp, _sz, _vp, _vp, _sz, _vp, _vp, _vp, _vp, _vp]),
     "dbhip_check_distinct_workspace_bytes": (_sz, [_sz]),
     "dbhip_check_distinct_u32": (_int, [_vp, _sz, _vp, _vp, _sz, _vp]),
+    "dbhip_check_join_pairs_u32": (_int, [_vp, _sz, _vp, _sz, _vp, _vp, _vp, _vp, _int, _vp, _vp, _u64, _vp, _vp]),
     "dbhip_check_gen_uniform_u32": (_int, [_vp, _vp, _sz, _u64, _u64, _u32, _u32, _vp, _vp]),
 }
 

@@ -174,6 +174,8 @@ void populate_slab_registry();
 void populate_groupby_hash_registry();
 // RadixPairsHip: only the dwarf_bench_sort_pairs CLI registers it, after populate_registry()
 void populate_sort_pairs_registry();
+// JoinPairsHip: only the dwarf_bench_join_pairs CLI registers it, after populate_registry()
+void populate_join_pairs_registry();
 
 namespace helpers {
 // $DWARF_BENCH_ROOT or the executable's directory (common/common.cpp:38-41, without Boost.DLL)

@@ -569,6 +569,112 @@ void JoinOmnisciHip::_run(const size_t n, Meter &meter) {
 }
 
 // =====================================================================================================
+// JoinPairsHip — the one-to-many join as a table of (build row, probe row) pairs: dbhip_join_radix_u32, then
+// dbhip_join_pairs_u32 on its answer.  No reference counterpart (JoinOmnisci stops at the per-row {pointer, size} record).
+// n rows a side, keys uniform in [1, max(10000, n)] from JoinOmnisciHip's seeds: the reference's distribution up to 10000
+// rows and about n pairs above (n^2 / 10000 would be 2.8e10 pairs at 2^24 rows).  Timed: the join (build_time) and the
+// expansion (probe_time) with the capacity an untimed count-only call returned.
+void JoinPairsHip::_run(const size_t n, Meter &meter) {
+  const RunOptions &opts = meter.opts();
+  if (n == 0 || n > (static_cast<size_t>(1) << 31)) fail("JoinPairsHip: between 1 and 2^31 rows a side");
+  DevBuf<uint32_t> a(n), b(n), ids(n), rid(n), pos(n), cnt(n);
+  const size_t join_bytes = dbhip_join_radix_workspace_bytes(n, n), pairs_bytes = dbhip_join_pairs_workspace_bytes(n);
+  DevBuf<unsigned char> join_ws(join_bytes), pairs_ws(pairs_bytes);
+  DevBuf<uint64_t> total(1);
+  const uint32_t key_hi = static_cast<uint32_t>(std::max<size_t>(10000, n));
+  db_ok(dbhip_gen_uniform_u32(a.get(), n, 42, 0, 1, key_hi, nullptr), "gen a");
+  db_ok(dbhip_gen_uniform_u32(b.get(), n, 43, 0, 1, key_hi, nullptr), "gen b");
+  const auto join = [&] {
+    db_ok(dbhip_join_radix_u32(a.get(), nullptr, n, b.get(), nullptr, n, ids.get(), rid.get(), pos.get(), cnt.get(),
+                               join_ws.get(), join_bytes, nullptr),
+          "dbhip_join_radix_u32");
+  };
+  const auto pairs = [&](uint64_t capacity, uint32_t *out_b, uint32_t *out_p) {
+    db_ok(dbhip_join_pairs_u32(ids.get(), n, rid.get(), pos.get(), cnt.get(), n, 0, capacity, out_b, out_p, total.get(),
+                               pairs_ws.get(), pairs_bytes, nullptr),
+          "dbhip_join_pairs_u32");
+  };
+  join();  // not timed: the count-only call that sizes the output
+  pairs(0, nullptr, nullptr);
+  check_status(join_ws.get(), "JoinPairsHip");
+  check_status(pairs_ws.get(), "JoinPairsHip");
+  const uint64_t capacity = total.to_host(1)[0];
+  DevBuf<uint32_t> out_b(capacity), out_p(capacity);
+
+  const bool host_check = n <= validate_limit();
+  std::vector<uint64_t> expected;  // probe row << 32 | build row, ascending
+  DevBuf<uint32_t> sorted_a(host_check ? 0 : n), sort_tmp(host_check ? 0 : n), b_part(host_check ? 0 : n);
+  const size_t perm_bytes = dbhip_check_permutation_workspace_bytes(n);
+  DevBuf<unsigned char> perm_ws(host_check ? 0 : perm_bytes);
+  CheckWords chk;
+  if (host_check) {  // sort-merge join of the two key columns on the host
+    const auto ha = a.to_host(n), hb = b.to_host(n);
+    std::vector<uint32_t> ia(n), ib(n);
+    for (size_t i = 0; i < n; ++i) ia[i] = ib[i] = static_cast<uint32_t>(i);
+    std::sort(ia.begin(), ia.end(), [&](uint32_t x, uint32_t y) { return ha[x] < ha[y]; });
+    std::sort(ib.begin(), ib.end(), [&](uint32_t x, uint32_t y) { return hb[x] < hb[y]; });
+    for (size_t i = 0, j = 0; i < n && j < n;) {
+      if (ha[ia[i]] < hb[ib[j]]) {
+        ++i;
+      } else if (ha[ia[i]] > hb[ib[j]]) {
+        ++j;
+      } else {
+        size_t i1 = i, j1 = j;
+        while (i1 < n && ha[ia[i1]] == ha[ia[i]]) ++i1;
+        while (j1 < n && hb[ib[j1]] == hb[ib[j]]) ++j1;
+        for (size_t y = j; y < j1; ++y)
+          for (size_t x = i; x < i1; ++x) expected.push_back(static_cast<uint64_t>(ib[y]) << 32 | ia[x]);
+        i = i1;
+        j = j1;
+      }
+    }
+    std::sort(expected.begin(), expected.end());
+  } else {
+    const size_t sort_bytes = dbhip_radix_sort_workspace_bytes(n, 8);
+    DevBuf<unsigned char> sort_ws(sort_bytes);
+    hip_ok(hipMemcpy(sorted_a.get(), a.get(), n * sizeof(uint32_t), hipMemcpyDeviceToDevice), "copy");
+    db_ok(dbhip_radix_sort_u32(sorted_a.get(), sort_tmp.get(), n, 8, sort_ws.get(), sort_bytes, nullptr), "sort build keys");
+    hip_ok(hipDeviceSynchronize(), "sync");
+  }
+  Events join_ev, pairs_ev;
+  for (size_t it = 0; it < opts.iterations; ++it) {
+    auto result = std::make_unique<HashJoinResult>();
+    time_build_probe(*result, join_ev, pairs_ev, join, [&] { pairs(capacity, out_b.get(), out_p.get()); });
+    check_status(join_ws.get(), "JoinPairsHip");
+    check_status(pairs_ws.get(), "JoinPairsHip");
+    if (inject_fault() && capacity) poke_xor(out_b.get() + capacity / 2, 1u);  // one build-row id
+    bool ok = total.to_host(1)[0] == capacity;
+    if (host_check) {
+      const auto hb_rows = out_b.to_host(capacity), hp_rows = out_p.to_host(capacity);
+      std::vector<uint64_t> got(capacity);
+      for (size_t k = 0; k < capacity; ++k) got[k] = static_cast<uint64_t>(hp_rows[k]) << 32 | hb_rows[k];
+      std::sort(got.begin(), got.end());
+      ok = ok && got == expected;
+    } else {
+      // the pair table against the answer it was made from, and the answer itself as JoinOmnisciHip checks it (the
+      // probe keys brought into the radix join's partition order first)
+      db_ok(dbhip_check_join_pairs_u32(a.get(), n, b.get(), n, ids.get(), rid.get(), pos.get(), cnt.get(), 0, out_b.get(),
+                                       out_p.get(), capacity, chk.dev(), nullptr),
+            "dbhip_check_join_pairs_u32");
+      const auto g = chk.get();
+      db_ok(dbhip_gather_u32(b.get(), rid.get(), n, b_part.get(), nullptr), "dbhip_gather_u32");
+      db_ok(dbhip_check_join_u32(sorted_a.get(), n, b_part.get(), n, pos.get(), cnt.get(), ids.get(), a.get(), 0, 0, 0,
+                                 chk.dev(), nullptr),
+            "dbhip_check_join_u32");
+      const auto j = chk.get();
+      db_ok(dbhip_check_permutation_u32(ids.get(), n, chk.dev(), perm_ws.get(), perm_bytes, nullptr),
+            "dbhip_check_permutation_u32");
+      const auto pi = chk.get();
+      db_ok(dbhip_check_permutation_u32(rid.get(), n, chk.dev(), perm_ws.get(), perm_bytes, nullptr),
+            "dbhip_check_permutation_u32");
+      ok = ok && g[0] == 0 && g[1] == capacity && g[2] == g[3] && j[0] == 0 && j[1] == capacity && pi[0] == 0 &&
+           chk.get()[0] == 0;
+    }
+    record(meter, n, std::move(result), ok, "Incorrect results");
+  }
+}
+
+// =====================================================================================================
 // ---- unique-key join: the buffers and the check shared by JoinHip and SlabJoinHip -----------------
 namespace {
 class UniqueJoinBuffers {

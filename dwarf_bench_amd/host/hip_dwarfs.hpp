@@ -107,3 +107,10 @@ struct RadixPairsHip : HipDwarf {
   void init(const RunOptions &opts) override;  // HipDwarf::init, then dbhip_radix_sort_prepare
   void _run(size_t buf_size, Meter &meter) override;
 };
+// the join result as a table of (build row, probe row) pairs (radix join + dbhip_join_pairs_u32): registered by
+// populate_join_pairs_registry() only (the dwarf_bench_join_pairs CLI); no reference counterpart, JoinOmnisci stops at the
+// per-row {pointer, size} record
+struct JoinPairsHip : HipDwarf {
+  JoinPairsHip() : HipDwarf("JoinPairsHip") {}
+  void _run(size_t buf_size, Meter &meter) override;
+};

@@ -7,7 +7,9 @@
 // EXPERIMENTAL dwarfs that have a HIP counterpart (populate_experimental_registry), and with -DEXPERIMENTAL_SLAB
 // `dwarf_bench_slab`, the default set plus the slab dwarfs (populate_slab_registry), and with -DEXPERIMENTAL_GROUPBY_HASH
 // `dwarf_bench_groupby_hash`, the default set plus GroupByHashHip (populate_groupby_hash_registry), and with
-// -DEXPERIMENTAL_SORT_PAIRS `dwarf_bench_sort_pairs`, the default set plus RadixPairsHip (populate_sort_pairs_registry).
+// -DEXPERIMENTAL_SORT_PAIRS `dwarf_bench_sort_pairs`, the default set plus RadixPairsHip (populate_sort_pairs_registry),
+// and with -DEXPERIMENTAL_JOIN_PAIRS `dwarf_bench_join_pairs`, the default set plus JoinPairsHip
+// (populate_join_pairs_registry).
 #include <iostream>
 #include <memory>
 #include <sstream>
@@ -48,6 +50,9 @@ int main(int argc, char *argv[]) {
 #endif
 #ifdef EXPERIMENTAL_SORT_PAIRS
   populate_sort_pairs_registry();  // dwarf_bench_sort_pairs
+#endif
+#ifdef EXPERIMENTAL_JOIN_PAIRS
+  populate_join_pairs_registry();  // dwarf_bench_join_pairs
 #endif
   Registry *registry = Registry::instance();
 

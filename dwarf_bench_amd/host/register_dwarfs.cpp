@@ -62,3 +62,11 @@ void populate_sort_pairs_registry() {
   Registry::instance()->registerd(new RadixPairsHip());
 #endif
 }
+
+// the join's pair table (dbhip_join_pairs_u32): only the dwarf_bench_join_pairs CLI (main.cpp built with
+// -DEXPERIMENTAL_JOIN_PAIRS) calls this, so the lists of the other five CLIs stay as they are
+void populate_join_pairs_registry() {
+#ifdef HIP_ENABLED
+  Registry::instance()->registerd(new JoinPairsHip());
+#endif
+}

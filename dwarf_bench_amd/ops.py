@@ -414,6 +414,90 @@ def hash_join(build_keys: torch.Tensor, probe_keys: torch.Tensor):
     return plan.result()
 
 
+class JoinPairs:
+    """Reusable plan that turns a one-to-many join answer into the table of (build row, probe row) pairs
+    (dbhip_join_pairs_u32): owns the workspace, both output columns (`capacity` entries each) and the device total.
+    capacity = 0: a count-only plan, no output columns."""
+
+    def __init__(self, n_probe: int, capacity: int, device="cuda"):
+        self.np, self.capacity = n_probe, int(capacity)
+        self.ws_bytes = _capi.lib().dbhip_join_pairs_workspace_bytes(n_probe)
+        if self.ws_bytes == 0:
+            raise ValueError(f"n_probe = {n_probe} is above the join's 2^32 - 1 probe rows")
+        self.ws = _ws(self.ws_bytes, device)
+        self.build_rows = torch.empty(self.capacity, dtype=torch.int32, device=device) if self.capacity else None
+        self.probe_rows = torch.empty(self.capacity, dtype=torch.int32, device=device) if self.capacity else None
+        self.total = torch.zeros(1, dtype=torch.int64, device=device)
+
+    def launch(self, ids: torch.Tensor, pos: torch.Tensor, cnt: torch.Tensor, probe_row_ids: torch.Tensor | None = None,
+               left_outer: bool = False) -> None:
+        """Asynchronous on the current stream; nothing is read back (graph-capturable).  (ids, pos, cnt) as
+        HashJoin.result() returns them, or with the probe_row_ids column of RadixJoin.result()."""
+        _need(ids, torch.int32, "ids")
+        _need(pos, torch.int32, "pos")
+        _need(cnt, torch.int32, "cnt")
+        if pos.numel() != self.np or cnt.numel() != self.np:
+            raise ValueError("size mismatch")
+        if probe_row_ids is not None:
+            _need(probe_row_ids, torch.int32, "probe_row_ids")
+            if probe_row_ids.numel() != self.np:
+                raise ValueError("size mismatch")
+        _capi.check(_capi.lib().dbhip_join_pairs_u32(
+            ids.data_ptr(), ids.numel(), probe_row_ids.data_ptr() if probe_row_ids is not None else None, pos.data_ptr(),
+            cnt.data_ptr(), self.np, int(left_outer), self.capacity,
+            self.build_rows.data_ptr() if self.capacity else None, self.probe_rows.data_ptr() if self.capacity else None,
+            self.total.data_ptr(), self.ws.data_ptr(), self.ws_bytes, _stream()), "join_pairs_u32")
+
+    def count(self) -> int:
+        """the total number of pairs of the last launch, whatever the capacity (synchronises)"""
+        return int(self.total.item())
+
+    def result(self):
+        """-> (build_rows, probe_rows) cut to the total, int32 storage of uint32 row ids (a left-outer miss: -1 as the
+        build row); raises on a device status (more pairs than the capacity: DBHIP_DEV_TABLE_FULL)"""
+        st = workspace_status(self.ws)
+        total = self.count()
+        if st & DEV_TABLE_FULL:
+            raise _capi.DbhipError(f"join_pairs_u32: device status {st:#x}: {total} pairs are needed, the capacity is "
+                                   f"{self.capacity}")
+        if st != DEV_OK:
+            raise _capi.DbhipError(f"join_pairs_u32: device status {st:#x}")
+        if not self.capacity:
+            empty = torch.empty(0, dtype=torch.int32, device=self.ws.device)
+            return empty, empty.clone()
+        return self.build_rows[:total], self.probe_rows[:total]
+
+
+def join_pairs(build_keys: torch.Tensor, probe_keys: torch.Tensor, left_outer: bool = False, capacity: int | None = None,
+               ordered: bool = False):
+    """The whole join: -> (build_rows, probe_rows), one entry per matching pair of rows (left_outer: and one with build
+    row -1 per probe row without a match).  ordered=False runs RadixJoin: the pairs are grouped by probe row, the probe
+    rows stand in partition order; ordered=True runs HashJoin: probe rows ascending.  capacity=None: a count-only launch,
+    one read-back, an exact allocation, the fill; a given capacity: one launch and no read-back before the result (more
+    pairs than that raise DbhipError, which names the total)."""
+    nb, npr = build_keys.numel(), probe_keys.numel()
+    if ordered:
+        join = HashJoin(nb, npr, build_keys.device)
+        join.build(build_keys)
+        join.probe(probe_keys)
+        rid = None
+    else:
+        join = RadixJoin(nb, npr, build_keys.device)
+        join.partition_build(build_keys)
+        join.partition_probe(probe_keys)
+        join.match()
+        rid = join.rid[:npr]
+    ids, pos, cnt = join.ids[:nb], join.pos[:npr], join.cnt[:npr]
+    if capacity is None:
+        counter = JoinPairs(npr, 0, build_keys.device)
+        counter.launch(ids, pos, cnt, rid, left_outer)
+        capacity = counter.count()
+    plan = JoinPairs(npr, capacity, build_keys.device)
+    plan.launch(ids, pos, cnt, rid, left_outer)
+    _check_status(join.ws, "join")  # the first read-back when a capacity was given
+    return plan.result()
+
+
 # ---------------------------------------------------------------------------------------------
 # dwarf 4b: unique-key payload join (Join semantics)
 # ---------------------------------------------------------------------------------------------
@@ -888,6 +972,28 @@ def check_join(sorted_build: torch.Tensor, probe: torch.Tensor, pos: torch.Tenso
                                                  probe.numel(), pos.data_ptr(), cnt.data_ptr(), ids.data_ptr(),
                                                  build_keys.data_ptr() if build_keys is not None else None,
                                                  gen[0], gen[1], gen[2], res.data_ptr(), _stream()), "check_join_u32")
+    return tuple(_u64(res))
+
+
+def check_join_pairs(build_keys: torch.Tensor, probe_keys: torch.Tensor, ids: torch.Tensor, pos: torch.Tensor,
+                     cnt: torch.Tensor, build_rows: torch.Tensor, probe_rows: torch.Tensor,
+                     probe_row_ids: torch.Tensor | None = None, left_outer: bool = False):
+    """-> (bad pairs, pairs expected, fingerprint of the pairs given, fingerprint expected); the pair table is right iff
+    the first is 0, the second equals build_rows.numel() and the last two are equal.  Row ids are row indices into the
+    key columns."""
+    for t, name in ((build_keys, "build_keys"), (probe_keys, "probe_keys"), (ids, "ids"), (pos, "pos"), (cnt, "cnt"),
+                    (build_rows, "build_rows"), (probe_rows, "probe_rows")):
+        _need(t, torch.int32, name)
+    if probe_row_ids is not None:
+        _need(probe_row_ids, torch.int32, "probe_row_ids")
+    if probe_rows.numel() != build_rows.numel() or pos.numel() != probe_keys.numel() or cnt.numel() != probe_keys.numel():
+        raise ValueError("size mismatch")
+    res = _result(4, probe_keys.device)
+    _capi.check(_capi.lib().dbhip_check_join_pairs_u32(
+        build_keys.data_ptr(), build_keys.numel(), probe_keys.data_ptr(), probe_keys.numel(), ids.data_ptr(),
+        probe_row_ids.data_ptr() if probe_row_ids is not None else None, pos.data_ptr(), cnt.data_ptr(), int(left_outer),
+        build_rows.data_ptr(), probe_rows.data_ptr(), build_rows.numel(), res.data_ptr(), _stream()),
+        "check_join_pairs_u32")
     return tuple(_u64(res))
 
 

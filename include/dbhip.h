@@ -38,6 +38,8 @@
  *   dbhip_nested_join_u32     join/nested_join.cpp:52-66
  *   dbhip_radix_sort_pairs_*  no reference counterpart (the reference sorts keys only, dpl_wrapper.hpp:35-39)
  *   dbhip_pjoin_*             no reference counterpart (multi-GPU radix-partitioned join)
+ *   dbhip_join_pairs_u32      no reference counterpart (the reference stops at HashTable::lookup's {pointer, size} record,
+ *                             common/dpcpp/omnisci_hashtable.hpp:12-17)
  *   dbhip_gen_*               common/common.hpp:31-40, common/common.cpp:7-20 (data generators)
  *   dbhip_exclusive_scan_u32  scan/scan.cl:44-66, tests/scan_tests.cpp:14-21, dpl_wrapper.hpp:18-25 (exclusive_scan)
  *   dbhip_check_*             the dwarfs' own result checks (scan/scan.cpp:157-164, sort/radix.cpp:46-52,
@@ -66,7 +68,8 @@ extern "C" {
 #define DBHIP_DEV_SPIN_TIMEOUT 1u  /* dbhip_copy_if_lt_dense_i32 and the single-launch path of dbhip_exclusive_scan_u32:
                                       a chunk waited 2 s for its predecessors (never seen); the output is then wrong;
                                       the slab table: an insert reached a loop bound (a workspace that was not reset) */
-#define DBHIP_DEV_KEY_RANGE 2u     /* group key >= groups_count, or the 0xFFFFFFFF sentinel as a join build key */
+#define DBHIP_DEV_KEY_RANGE 2u     /* group key >= groups_count, or the 0xFFFFFFFF sentinel as a join build key;
+                                      dbhip_join_pairs_u32: a probe row whose id range leaves the id buffer */
 #define DBHIP_DEV_TABLE_FULL 4u    /* open-addressing table wrapped without finding a slot: the bitmask-claimed table (a
                                       table that really is full: the reference spins forever there) and the small-input
                                       unique-key table; the cuckoo table: an insert's eviction chain reached max_iter
@@ -76,7 +79,8 @@ extern "C" {
                                       dbhip_ujoin_* from 2^16 rows): a partition with more distinct keys than its 3072-slot
                                       LDS sub-table holds is built in a spill table of its own, any keys join (the one
                                       exception: a one-to-many build of exactly 2^31 rows has no spare bit to mark such a
-                                      sub-table and still raises this) */
+                                      sub-table and still raises this).  dbhip_join_pairs_u32: more pairs than the
+                                      caller's capacity (a normal result: *out_pairs holds the total) */
 #define DBHIP_DEV_RANK_ORDER 8u    /* radix sort: a tile re-ordered by the pass's digit was not sorted by its lower digits —
                                       the ranking was not stable (or an earlier pass was damaged); the output is wrong */
 
@@ -281,6 +285,39 @@ typedef struct dbhip_join_one_to_many {
 int dbhip_join_answers_u32(const uint32_t *ids, const uint32_t *out_pos, const uint32_t *out_count, size_t n_probe,
                            dbhip_join_one_to_many *answers, dbhip_stream_t stream);
 
+/* ---- dwarf 4a, the join result as rows (no reference counterpart: OmniSci::HashTable::lookup stops at the per-row
+ * {pointer, size} record) ----------------------------------------------------------------------------------------------
+ * Turns the answer of either one-to-many join into the table of matching (build row, probe row) pairs.  Input: (ids, pos,
+ * cnt) of dbhip_join_probe_u32 (probe-row order, probe_row_ids = NULL: probe row i has id i) or (ids, out_probe_row_ids,
+ * out_pos, out_count) of dbhip_join_radix_match_u32.  With rid(i) = probe_row_ids ? probe_row_ids[i] : i, e[i] = cnt[i]
+ * (inner) or max(cnt[i], 1) (left_outer != 0) and off the 64-BIT exclusive prefix sum of e: for k < cnt[i], pair number
+ * off[i] + k is (ids[pos[i] + k], rid(i)); a probe row with cnt[i] == 0 yields in left-outer mode the one pair
+ * (0xFFFFFFFF, rid(i)).  The pairs are thus grouped by probe row in input order and follow the id buffer inside a row:
+ * given (ids, pos, cnt) the output is unique.  *out_pairs (a DEVICE uint64, like copy_if's out_size) = the sum of e, always
+ * the full total, which may exceed 2^32.
+ *   capacity   entries of out_build_rows and of out_probe_rows.  Only pairs numbered below it are written; a total above
+ *              it sets DBHIP_DEV_TABLE_FULL in the workspace status word, and *out_pairs still holds the total, so a caller
+ *              can allocate and call again.  The count-only call, capacity == 0 with both output pointers NULL, computes
+ *              *out_pairs alone and never raises DBHIP_DEV_TABLE_FULL.
+ *   a row with pos[i] + cnt[i] > n_build (not an answer of this library) counts as cnt[i] = 0 and sets
+ *              DBHIP_DEV_KEY_RANGE: nothing outside ids[0..n_build) is read whatever the input holds.
+ * Any 4-byte aligned columns, inputs and outputs (16-byte stores are used when both output columns sit at the same distance
+ * from a 16-byte boundary).  n_probe < 2^32, n_build <= 2^31, as in the joins.  n_probe == 0: *out_pairs = 0 (when given)
+ * and a clean status word (when a workspace is given).  DBHIP_EINVAL: sizes out of range, a NULL output with capacity > 0,
+ * and with n_probe > 0 a NULL ids (n_build > 0), pos, cnt, out_pairs or workspace; DBHIP_EWORKSPACE: a short or misaligned
+ * workspace; all before any HIP call.  Never allocates, never synchronises, no workgroup waits on another (four dependent
+ * launches: chunk sums, their scan, the row offsets, the expansion), can be captured into a graph, and gives the same
+ * answers whatever the workspace held before.  The expansion is partitioned by output: a fixed grid takes equal chunks of
+ * 2048 items, an item being a probe row or a pair, so neither a row with millions of matches nor millions of rows with no
+ * match make one workgroup's share longer than another's.
+ * Workspace: 256-byte header (status word, total, pairs written) | 4096 chunk sums | off[n_probe], 8 bytes per probe row;
+ * the query returns 0 for n_probe >= 2^32.                                                                           */
+size_t dbhip_join_pairs_workspace_bytes(size_t n_probe);
+int dbhip_join_pairs_u32(const uint32_t *ids, size_t n_build, const uint32_t *probe_row_ids, const uint32_t *pos,
+                         const uint32_t *cnt, size_t n_probe, int left_outer, uint64_t capacity,
+                         uint32_t *out_build_rows, uint32_t *out_probe_rows, uint64_t *out_pairs, void *workspace,
+                         size_t workspace_bytes, dbhip_stream_t stream);
+
 /* ---- dwarf 4b: unique-key join carrying payloads (Join semantics, join/join.cpp:60-104) ---------
  * Build keys are unique.  For probe row i: on a hit out_key[i] = key, out_build_val[i] = payload of
  * the build row, out_probe_val[i] = probe payload; on a miss all three are left at 0xFFFFFFFF
@@ -464,7 +501,16 @@ int dbhip_exclusive_scan_u32(const uint32_t *src, size_t n, uint32_t init, uint3
  *                       the stable sort permutation of keys_in and keys_out the sorted column: strictly increasing
  *                       pairs are n distinct pairs, and as every id names a row that carries the key beside it, equal
  *                       ids would make equal pairs — so the ids are n distinct values below n, a permutation; keys_out
- *                       is keys_in under it, ascending, and ties stand in row order.                        */
+ *                       is keys_in under it, ascending, and ties stand in row order.
+ *   join_pairs_u32      the pair table of dbhip_join_pairs_u32 against the answer it was made from.  result[0] = number of
+ *                       bad pairs among out_*[0..n_pairs): a row id out of range, build_keys[b] != probe_keys[p], or
+ *                       b == 0xFFFFFFFF when left_outer is 0 (a sentinel on a row that has matches shows in the
+ *                       fingerprints); result[1] = the number of pairs expected; result[2] = fingerprint of the pairs
+ *                       given, result[3] = fingerprint expected: order-independent 64-bit sums of a mix of (b, p), the
+ *                       expected one from a one-thread-per-probe-row walk over (pos, cnt, ids): another algorithm than
+ *                       the expansion, slow, a checker only.  Valid iff result[0] == 0 && result[1] == n_pairs &&
+ *                       result[2] == result[3].  Row ids are taken as ROW INDICES into the key columns given, which is
+ *                       what both joins produce when no row_ids column is passed to them.                       */
 size_t dbhip_check_fingerprint_workspace_bytes(size_t n);
 int dbhip_check_fingerprint_lt_i32(const int32_t *src, size_t n, int32_t filter_value, uint64_t *result,
                                    void *workspace, size_t workspace_bytes, dbhip_stream_t stream);
@@ -488,6 +534,10 @@ int dbhip_check_distinct_u32(const uint32_t *keys, size_t n, uint64_t *result, v
                              dbhip_stream_t stream);
 int dbhip_check_sorted_pairs_u32(const uint32_t *keys_in, const uint32_t *keys_out, const uint32_t *ids_out, size_t n,
                                  int signed_order, uint64_t *result, dbhip_stream_t stream);
+int dbhip_check_join_pairs_u32(const uint32_t *build_keys, size_t n_build, const uint32_t *probe_keys, size_t n_probe,
+                               const uint32_t *ids, const uint32_t *probe_row_ids, const uint32_t *pos, const uint32_t *cnt,
+                               int left_outer, const uint32_t *out_build_rows, const uint32_t *out_probe_rows,
+                               uint64_t n_pairs, uint64_t *result /* 4 device words */, dbhip_stream_t stream);
 int dbhip_check_gen_uniform_u32(const uint32_t *values, const uint32_t *indices, size_t n, uint64_t seed,
                                 uint64_t first_index, uint32_t lo, uint32_t hi, uint64_t *result,
                                 dbhip_stream_t stream);

@@ -10,6 +10,13 @@ the contract numbers come from bench.py.
                   2^lg alone), full-range keys and keys in [1, 10000]; beside them, in the same run, the keys-only sort and
                   torch.sort(stable=True) (which returns 8-byte indices) (median of 9, refresh copy subtracted); every
                   column of every mode checked against torch's stable sort
+  join-pairs [lg] the join's pair table (dbhip_join_pairs_u32: scan + expansion, one call, capacity given) on the radix join's
+                  answer at 2^20 / 2^24 / 2^26 rows a side (or 2^lg alone) with keys in [1, n], and on 2^13 x 2^13 rows of one
+                  key (2^26 pairs); beside it the count-only call and, in the same process on the same (ids, pos, cnt), the
+                  torch composition repeat_interleave + cumsum + gather (median of 9); both columns of both legs compared
+                  with each other and the pair table checked by dbhip_check_join_pairs_u32
+  launch-join-pairs [lg]  five expansions at 2^lg rows a side (default 24) and five of the one-key shape, nothing else
+                  (`rocprofv3 --kernel-trace --stats`)
   launch-sort-pairs [lg]  five 8-bit argsorts of 2^lg full-range keys (default 24) and nothing else (`rocprofv3 --kernel-trace`)
   sort-only       three 2^24 sorts and nothing else (counter collection; SORT_BITS=4|8, SORT_SHAPE=<index into sort-shapes' list>)
   groupby         2^26 rows at 2^16 / 2^15 / 2^10 / 64 groups (drop-max-mean of 9)
@@ -158,6 +165,60 @@ def sort_pairs(lg):
             for r in res:
                 print(f"{TAG:12s} n={n:9d} {name:10s} {r}   torch.sort(stable) {t_torch:8.1f} us", flush=True)
             del keys0, vals0, keys, vals, ref
+
+
+def _join_pairs_shapes(lg):
+    """(name, build keys, probe keys)"""
+    for n in ([1 << lg] if lg else [1 << 20, 1 << 24, 1 << 26]):
+        yield f"2^{n.bit_length() - 1} keys [1,n]", ops.gen_uniform_u32(n, 42, 1, n), ops.gen_uniform_u32(n, 43, 1, n)
+    hot = torch.full((1 << 13,), 12345, dtype=torch.int32, device="cuda")
+    yield "2^13 x 2^13 one key", hot, hot.clone()
+
+
+def _torch_pairs(ids, pos, cnt, rid):
+    """the same pairs from the same answer with torch ops: what a caller of ops.radix_join had to write before"""
+    c = u64(cnt)
+    rows = torch.repeat_interleave(torch.arange(c.numel(), device=c.device), c)
+    first = torch.cumsum(c, 0) - c
+    k = torch.arange(rows.numel(), device=c.device) - first[rows]
+    return ids[u64(pos)[rows] + k], rid[rows]
+
+
+def join_pairs(lg):
+    for name, bk, pk in _join_pairs_shapes(lg):
+        n = pk.numel()
+        rid, pos, cnt, ids = ops.radix_join(bk, pk)
+        counter = ops.JoinPairs(n, 0)
+        counter.launch(ids, pos, cnt, rid)
+        total = counter.count()
+        plan = ops.JoinPairs(n, total)
+        t_count = median(times(lambda: counter.launch(ids, pos, cnt, rid), 9))
+        t_mine = median(times(lambda: plan.launch(ids, pos, cnt, rid), 9))
+        b, p = plan.result()
+        t_torch = median(times(lambda: _torch_pairs(ids, pos, cnt, rid), 9))
+        tb, tp = _torch_pairs(ids, pos, cnt, rid)
+        words = ops.check_join_pairs(bk, pk, ids, pos, cnt, b, p, rid)
+        ok = (b.numel() == total and torch.equal(b, tb) and torch.equal(p, tp) and words[0] == 0 and words[1] == total
+              and words[2] == words[3])
+        gbytes = (12 * total + 44 * n) / 1e9  # DESIGN 4: 8 P written + 4 P ids + 44 n_probe of per-row columns and offsets
+        print(f"{TAG:12s} {name:22s} pairs={total:9d}  join_pairs {t_mine:8.1f} us ({t_mine * 1e3 / max(total, 1):6.3f} ns/pair, "
+              f"{gbytes / (t_mine * 1e-6) / 1e3:5.2f} TB/s = {gbytes / (t_mine * 1e-6) / 8e3:4.2f} of 8 TB/s)  count-only {t_count:7.1f} us  "
+              f"torch {t_torch:9.1f} us  (torch / join_pairs {t_torch / t_mine:5.2f})  {'ok' if ok else 'WRONG'}", flush=True)
+        del rid, pos, cnt, ids, b, p, tb, tp, plan, counter
+
+
+def launch_join_pairs(lg):
+    for name, bk, pk in _join_pairs_shapes(lg or 24):
+        n = pk.numel()
+        rid, pos, cnt, ids = ops.radix_join(bk, pk)
+        counter = ops.JoinPairs(n, 0)
+        counter.launch(ids, pos, cnt, rid)
+        plan = ops.JoinPairs(n, counter.count())
+        for _i in range(5):
+            plan.launch(ids, pos, cnt, rid)
+        b, p = plan.result()
+        words = ops.check_join_pairs(bk, pk, ids, pos, cnt, b, p, rid)
+        print(name, "ok" if words[0] == 0 and words[1] == b.numel() and words[2] == words[3] else "WRONG")
 
 
 def launch_sort_pairs(lg):
@@ -859,7 +920,8 @@ def launch_all(_):
 
 MODES = {"radix": radix, "ramp": ramp, "radix-idle": radix_idle, "radix-stream": radix_stream, "radix-alloc": radix_alloc, "radix-offsets": radix_offsets, "radix-sizes": radix_sizes, "graph": graph, "launch-join": launch_join, "launch-sort": launch_sort, "launch-all": launch_all, "scan": scan, "sort": sort, "sort-only": sort_only, "groupby": groupby, "groupby-shapes": groupby_shapes, "groupby-skew": groupby_skew, "sort-shapes": sort_shapes, "join": join, "join-skew": join_skew, "size-sweep": size_sweep, "partition": partition,
          "reduce": reduce, "xscan": xscan, "cuckoo": cuckoo, "slab": slab,
-         "groupby-hash": groupby_hash, "sort-pairs": sort_pairs, "launch-sort-pairs": launch_sort_pairs}
+         "groupby-hash": groupby_hash, "sort-pairs": sort_pairs, "launch-sort-pairs": launch_sort_pairs,
+         "join-pairs": join_pairs, "launch-join-pairs": launch_join_pairs}
 
 if __name__ == "__main__":
     if len(sys.argv) < 2 or sys.argv[1] not in MODES:
