@@ -7,25 +7,10 @@ import pytest
 import torch
 
 from oracle import pyoracle as po
+from tests.graph_testlib import capture as _capture  # one eager warm-up run, then the capture on one stream
+from tests.graph_testlib import fill as _fill
 
 pytestmark = pytest.mark.gpu
-
-
-def _fill(t, host):
-    t.copy_(torch.from_numpy(np.ascontiguousarray(host).view(np.int32)))
-
-
-def _capture(fn):
-    side = torch.cuda.Stream()
-    side.wait_stream(torch.cuda.current_stream())
-    with torch.cuda.stream(side):
-        fn()  # warm-up outside capture (lazy module loads, attribute calls)
-    torch.cuda.current_stream().wait_stream(side)
-    torch.cuda.synchronize()
-    g = torch.cuda.CUDAGraph()
-    with torch.cuda.graph(g):
-        fn()
-    return g
 
 
 @pytest.mark.parametrize("n", [5000, 1 << 20, (1 << 23) + 5])
