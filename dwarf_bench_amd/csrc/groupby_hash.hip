@@ -11,7 +11,7 @@
 //      summed across the wave and added once (a hot key costs no 64-way queue on one LDS word).  At the end every
 //      workgroup inserts its occupied slots into the global table: one global insert per (workgroup, group).  A row that
 //      finds no LDS slot within kGbhProbe steps goes to the global table directly: slow, correct.
-//   b. PARTITION (more groups): the radix join's partition step (jl_partition_side, geometry jl_layout(n)) hash-partitions
+//   b. PARTITION (more groups): the radix join's partition step (partition.hip jl_partition_side, geometry jl_geometry(n)) hash-partitions
 //      the (key, val) pairs — the vals column rides where the join passes row ids — into ~2048-row partitions; one
 //      workgroup per partition aggregates it in a kGbhSubSlots-slot LDS sub-table and writes its groups straight to the
 //      outputs at an offset taken from a ticket.  A partition of more than kGbhGiantRows rows (a hot key) is listed instead
@@ -412,7 +412,7 @@ struct GbhLayout {
   int path;
   unsigned long long slots;  // global table
   unsigned max_giants;
-  JlLayout part;  // geometry only (path b)
+  JlGeometry part;  // path b
   size_t giants_off, keys_off, sums_off, cnts_off, pairs_a_off, pairs_b_off, meta_off, total;
 };
 
@@ -426,7 +426,7 @@ GbhLayout gbh_layout(size_t n, uint32_t max_groups) {
   const size_t col = align_up(static_cast<size_t>(L.slots) * sizeof(unsigned), kWsAlign);
   size_t off = kWsHeader;
   if (L.path == kPathPart) {
-    L.part = jl_layout(n);
+    L.part = jl_geometry(n, kJlRowsPerPart);
     L.max_giants = static_cast<unsigned>(n / kGbhGiantRows + 1);
     L.giants_off = off;
     off += align_up(static_cast<size_t>(L.max_giants) * sizeof(unsigned), kWsAlign);
@@ -440,7 +440,7 @@ GbhLayout gbh_layout(size_t n, uint32_t max_groups) {
     L.pairs_a_off = off;
     L.pairs_b_off = off + pairs;
     L.meta_off = L.pairs_b_off + (L.part.k2 > 1 ? pairs : 0);
-    off = align_up(L.meta_off + L.part.meta_bytes, kWsAlign);
+    off = align_up(L.meta_off + jl_meta(L.part).bytes(), kWsAlign);
   }
   L.total = off;
   return L;
@@ -494,17 +494,15 @@ extern "C" int dbhip_groupby_hash_u32(const uint32_t *keys, const uint32_t *vals
     hipLaunchKernelGGL(gbh_global_kernel, dim3(static_cast<unsigned>(blocks < cap ? blocks : cap)), dim3(256), 0, s, keys,
                        vals, n, g, hdr);
   } else {
-    const JlLayout &P = L.part;
     const unsigned *pairs = nullptr;
     const unsigned long long *starts = nullptr;
-    const int rc = jl_partition_side(keys, vals, n, P.parts, P.k1, P.k2, P.log2_k2, reinterpret_cast<u32x2 *>(base + L.pairs_a_off),
+    const int rc = jl_partition_side(keys, vals, n, L.part, reinterpret_cast<u32x2 *>(base + L.pairs_a_off),
                                      reinterpret_cast<u32x2 *>(base + L.pairs_b_off),
-                                     reinterpret_cast<unsigned long long *>(base + L.meta_off), P.meta_bytes, s, dev, &pairs,
-                                     &starts);
+                                     reinterpret_cast<unsigned long long *>(base + L.meta_off), s, dev, &pairs, &starts);
     if (rc != 0) return rc;
     const size_t lds = (3 * static_cast<size_t>(kGbhSubSlots) + 8) * sizeof(unsigned);
     unsigned *giants = reinterpret_cast<unsigned *>(base + L.giants_off);
-    hipLaunchKernelGGL(gbh_part_kernel, dim3(P.parts), dim3(kGbhPartThreads), lds, s, reinterpret_cast<const u32x2 *>(pairs),
+    hipLaunchKernelGGL(gbh_part_kernel, dim3(L.part.parts), dim3(kGbhPartThreads), lds, s, reinterpret_cast<const u32x2 *>(pairs),
                        starts, g, out, giants, L.max_giants);
     hipLaunchKernelGGL(gbh_giant_kernel, dim3(static_cast<unsigned>(dev.cus) * 4), dim3(kGbhPartThreads), lds, s,
                        reinterpret_cast<const u32x2 *>(pairs), starts, g, hdr, static_cast<const unsigned *>(giants),

@@ -1,8 +1,10 @@
 // join_common.hpp — geometry shared by join.hip (the C entry points, the small-input unique-key table, the
 // bitmask-claimed table) and join_lds.hip (radix-partitioned build with LDS sub-tables, every size).  Everything is a pure function of n_build, so build
-// and probe agree without reading anything back from the device.
+// and probe agree without reading anything back from the device.  The partition step itself — its geometry, its meta
+// array, its plan — is partition.hpp's.
 #pragma once
 #include "dbhip_common.hpp"
+#include "partition.hpp"
 
 namespace dbhip {
 
@@ -56,9 +58,6 @@ inline bool jl_use_ujoin(size_t n_build) {
   return n_build >= kJlMinRows && n_build <= kJlMaxRows;
 }
 
-#ifndef DBHIP_JL_K2_BIAS
-#define DBHIP_JL_K2_BIAS 0
-#endif
 // A GIANT partition: one hot key (or a few) gives a partition far more rows than one workgroup should walk alone —
 // every other row of 2^24 carrying one key made the build 22.5 ms against 0.3 ms.  A partition above jl_giant_rows(n)
 // rows is left out by the per-partition build and counted / filled by all workgroups together, slice by slice
@@ -106,9 +105,9 @@ inline size_t jl_spill_bytes(unsigned parts, size_t n) {
   return align_up(8 * static_cast<size_t>(parts) + 4 * jl_spill_list_words(n) + 12 * jl_spill_pool_slots(n), kWsAlign);
 }
 
-struct JlLayout {
-  unsigned parts, k1, k2, log2_k2, max_giants;
-  size_t table_off, keys_a_off, rids_a_off, keys_b_off, rids_b_off, meta_off, meta_bytes, giant_off, spill_off, total;
+struct JlLayout : JlGeometry {
+  unsigned max_giants;
+  size_t table_off, pairs_a_off, pairs_b_off, meta_off, meta_bytes, giant_off, spill_off, total;
 };
 
 // The radix join's fused build + probe kernel likes its partitions emptier than the build kernel does (2^26 x 2^26, rows
@@ -122,40 +121,14 @@ static_assert(kJrRowsPerPart <= kJlRowsPerPart, "the build kernel caches kJlRows
 
 inline JlLayout jl_layout(size_t n, size_t rows_per_part = kJlRowsPerPart) {
   JlLayout L;
-  // parts = ceil(n / kJlRowsPerPart) rounded up to a multiple of the level-1 fan-out k2 (a power of two: level 1 takes
-  // the low bits of the partition id, level 0 the rest — any number k1 <= 1024 of buckets; the partition id itself is a
-  // multiply-shift of the hash and takes any range).  Until late in round 3 parts was the next POWER of two: one row
-  // more than 2^26 meant 65536 half-empty partitions — build 1245 us against 1029, twice the table.
-  size_t want = (n + rows_per_part - 1) / rows_per_part;
-  if (want == 0) want = 1;
-  if (want > (static_cast<size_t>(1) << 20)) want = static_cast<size_t>(1) << 20;  // 2^20 partitions at most
-  unsigned lg = 0;
-  while ((static_cast<size_t>(1) << lg) < want) ++lg;
-  if (want <= 1024) {  // one scatter level handles up to 1024 buckets
-    L.log2_k2 = 0;
-  } else {
-    // split of the partition bits between the two scatter levels, by floor(log2(parts)): between two powers of two
-    // level 0 takes the extra buckets (37504 partitions as 293 x 128: one side of 2^26 rows 615 us; as 147 x 256: 639)
-    const unsigned lgs = (static_cast<size_t>(1) << lg) != want ? lg - 1 : lg;
-    L.log2_k2 = (lgs + DBHIP_JL_K2_BIAS) / 2;
-  }
-  L.k2 = 1u << L.log2_k2;
-  L.k1 = static_cast<unsigned>((want + L.k2 - 1) / L.k2);
-  while (L.k1 > 1024) {  // level 0 (one workgroup of 1024 threads owns the bucket offsets) takes at most 1024 buckets
-    ++L.log2_k2;
-    L.k2 <<= 1;
-    L.k1 = static_cast<unsigned>((want + L.k2 - 1) / L.k2);
-  }
-  L.parts = L.k1 * L.k2;
-  const size_t col = align_up((n ? n : 1) * sizeof(unsigned), kWsAlign);
+  static_cast<JlGeometry &>(L) = jl_geometry(n, rows_per_part);
+  const size_t pairs = 2 * align_up((n ? n : 1) * sizeof(unsigned), kWsAlign);  // (key, row id) per row
   L.table_off = kWsHeader;
   // 8-byte slots {key, first id position} + one sentinel slot after the last sub-table
-  L.keys_a_off = align_up(L.table_off + (static_cast<size_t>(L.parts) * kJlSubSlots + 1) * 8, kWsAlign);
-  L.rids_a_off = L.keys_a_off + col;
-  L.keys_b_off = L.rids_a_off + col;
-  L.rids_b_off = L.keys_b_off + (L.k2 > 1 ? col : 0);
-  L.meta_off = L.rids_b_off + (L.k2 > 1 ? col : 0);
-  L.meta_bytes = sizeof(unsigned long long) * ((2 * 64 + 2) * static_cast<size_t>(L.k1) + 2 + 3 * static_cast<size_t>(L.parts) + 1);  // 64 = kJlGroups
+  L.pairs_a_off = align_up(L.table_off + (static_cast<size_t>(L.parts) * kJlSubSlots + 1) * 8, kWsAlign);
+  L.pairs_b_off = L.pairs_a_off + pairs;
+  L.meta_off = L.pairs_b_off + (L.k2 > 1 ? pairs : 0);
+  L.meta_bytes = jl_meta(L).bytes();
   L.max_giants = jl_max_giants(n);
   L.giant_off = align_up(L.meta_off + L.meta_bytes, kWsAlign);
   L.spill_off = align_up(L.giant_off + jl_giant_bytes(L.max_giants), kWsAlign);
@@ -163,29 +136,15 @@ inline JlLayout jl_layout(size_t n, size_t rows_per_part = kJlRowsPerPart) {
   return L;
 }
 
-// The partition step of every join (join_lds.hip), also the group-by's (groupby_hash.hip): the (key, row id) pairs of a
-// column of n rows hash-partitioned into `parts` partitions of the geometry (parts, k1, k2, log2_k2) of jl_layout; level-0
-// output in rows_a, level-1 output (k2 > 1) in rows_b, offsets in `meta` (meta_bytes).  *out_pairs: the partition-major
-// pairs, *out_starts: parts + 1 offsets into them.  row_ids == nullptr: the row index.  Any key, 0xFFFFFFFF included, is
-// carried like any other.
-int jl_partition_side(const unsigned *keys, const unsigned *row_ids, size_t n, unsigned parts, unsigned k1, unsigned k2,
-                      unsigned log2_k2, u32x2 *rows_a, u32x2 *rows_b, unsigned long long *meta, size_t meta_bytes,
-                      hipStream_t s, const DeviceInfo &dev, const unsigned **out_pairs,
-                      const unsigned long long **out_starts);
+// join_lds.hip
 int join_lds_build(const unsigned *build_keys, const unsigned *row_ids, size_t n, unsigned *ids, void *workspace,
                    hipStream_t s, const DeviceInfo &dev);
-size_t jl_partition_workspace_bytes(unsigned parts);
-int jl_partition(const unsigned *keys, size_t n, unsigned long long first_row, unsigned parts, unsigned *out_keys,
-                 unsigned *out_rids, unsigned long long *out_counts, void *workspace, hipStream_t s,
-                 const DeviceInfo &dev);
 size_t join_radix_workspace_bytes(size_t n_build, size_t n_probe);
 size_t jr_max_probe_rows();  // the radix join's largest n_probe (include/dbhip.h)
 int join_radix_partition(int probe_side, const unsigned *keys, const unsigned *row_ids, size_t n, size_t n_build,
                          size_t n_probe, void *workspace, hipStream_t s, const DeviceInfo &dev);
 int join_radix_match(size_t n_build, size_t n_probe, unsigned *ids, unsigned *out_rid, unsigned *out_pos, unsigned *out_cnt,
                      void *workspace, hipStream_t s, const DeviceInfo &dev);
-int jl_route_check(const unsigned *keys, size_t n, unsigned parts, unsigned rank, unsigned long long *result,
-                   hipStream_t s, const DeviceInfo &dev);
 int ujoin_lds_build(const unsigned *build_keys, const unsigned *build_vals, size_t n, void *workspace, hipStream_t s,
                     const DeviceInfo &dev);
 int ujoin_lds_probe(const unsigned *probe_keys, const unsigned *probe_vals, size_t n_probe, const void *workspace,

@@ -5,10 +5,10 @@
 // Why: on MI355X a table in HBM costs one memory-side atomic per step (20-27 G/s random, tools/ubench) — three per
 // build row — and three 4-byte gathers per probe row (53 G/s).  Random LDS atomics run at ~4,000 G/s chip-wide
 // (profiles/r04_ubench.txt).  So:
-//   build  1. partition the build column into K = ceil(n / 2048) partitions (join_common.hpp jl_layout) by the mixed hash,
-//             in one or two levels of <= 1024-way scatter (jl_hist / jl_offsets / jl_scatter: LDS counts, one global
+//   build  1. partition the build column into K = ceil(n / 2048) partitions (partition.hpp jl_geometry) by the mixed hash,
+//             in one or two levels of <= 1024-way scatter (partition.hip: jl_hist / jl_offsets / jl_scatter: LDS counts, one global
 //             reservation per bucket per tile, runs of (key, row id) pairs written contiguously; tiles of 4096 rows,
-//             of 16384 where a level has 512+ buckets: JlShape; both histograms from ONE read of the keys up to 81920
+//             of 16384 where a level has 512+ buckets: JlSidePlan; both histograms from ONE read of the keys up to 81920
 //             partitions, above that level 0 leaves every row's level-1 bucket as a 16-bit column for the level-1
 //             histogram to read instead of the pairs);
 //          2. persistent workgroups — as many as are RESIDENT, partitions dealt by ticket — walk the partitions
@@ -36,18 +36,6 @@
 namespace dbhip {
 namespace {
 
-constexpr unsigned kEmptyKey = 0xFFFFFFFFu;
-#ifndef DBHIP_JL_THREADS
-#define DBHIP_JL_THREADS 512
-#endif
-constexpr int kJlThreads = DBHIP_JL_THREADS;  // scatter / histogram / probe workgroups
-#ifndef DBHIP_JL_KPT
-#define DBHIP_JL_KPT 8
-#endif
-constexpr int kJlKpt = DBHIP_JL_KPT;
-constexpr int kJlTile = kJlThreads * kJlKpt;  // 4096 rows per scatter tile, 36 KiB of LDS: four 512-thread workgroups
-                                              // per CU.  Measured at 2^26 rows (build, us): 512x8 1361, 512x16 1423,
-                                              // 1024x8 1390, 512x4 1442, 256x8 1499, 512x32 1687
 #ifndef DBHIP_JL_BUILD_THREADS
 #define DBHIP_JL_BUILD_THREADS 512
 #endif
@@ -55,716 +43,6 @@ constexpr int kJlBuildThreads = DBHIP_JL_BUILD_THREADS;  // per-partition build 
                                                         // 256 -> 1514 us, 1024 -> 1465 us (whole build); round 4, resident
                                                         // ticketed grid: build 920 / 938 / 1148 us and the radix join's fused
                                                         // kernel 605 / 700 / 1285 us with 512 / 256 / 1024 threads
-
-__device__ __forceinline__ unsigned jl_pid(unsigned key, unsigned parts) {
-  return static_cast<unsigned>((static_cast<unsigned long long>(fmix32(key)) * parts) >> 32);
-}
-// Destination RANK of the multi-GPU partitioner: a second, independent hash.  It must not be the high bits of
-// fmix32(key) again: a rank only receives keys of one rank bucket, and its local build (jl_pid above) would then
-// find all of them in 1/P of its partitions — P times overfull sub-tables (at P = 8 more keys than slots: the spill path).
-__device__ __forceinline__ unsigned jl_rank_of(unsigned key, unsigned parts) {
-  return static_cast<unsigned>((static_cast<unsigned long long>(fmix32(key * 0x9E3779B1u + 0x7F4A7C15u)) * parts) >> 32);
-}
-template <bool RANK>
-__device__ __forceinline__ unsigned jl_pid_sel(unsigned key, unsigned parts) {
-  return RANK ? jl_rank_of(key, parts) : jl_pid(key, parts);
-}
-
-// ---- level 0: histogram per (tile group, bucket) --------------------------------------------------
-// The column's 4096-row tiles are cut into kJlGroups contiguous groups; every group owns a private slice
-// of every bucket (its rows' share), so the scatter's reservations on one cursor come from 1/64 of
-// the tiles: 16384 tiles bumping the SAME 128 cursors serialise on the memory-side atomic unit
-// (measured: 544 us for a 768 MiB scatter).
-constexpr unsigned kJlGroups = 64;
-constexpr unsigned kJlHistWgPerGroup = 32;
-
-// rows of a tile group: a whole number of the level-0 scatter's tiles (`tile` rows each — the scatter comes in three
-// tile shapes, see JlShape), so histogram and scatter agree on which rows are group g's
-__host__ __device__ __forceinline__ size_t jl_group_rows(size_t n, unsigned tile) {
-  const size_t tiles = (n + tile - 1) / tile;
-  return (tiles + kJlGroups - 1) / kJlGroups * tile;
-}
-
-template <bool RANK>
-__global__ __launch_bounds__(kJlThreads) void jl_hist0_kernel(const unsigned *__restrict__ keys, size_t n, size_t group_rows,
-                                                              unsigned parts, unsigned k2_shift,
-                                                              unsigned k1, unsigned long long *counts_g) {
-  extern __shared__ unsigned s_hist[];
-  const unsigned group = blockIdx.x / kJlHistWgPerGroup, w = blockIdx.x % kJlHistWgPerGroup;
-  const size_t lo = static_cast<size_t>(group) * group_rows;
-  size_t hi = lo + group_rows;
-  hi = hi < n ? hi : n;
-  if (lo >= hi) return;
-  for (unsigned i = threadIdx.x; i < k1; i += kJlThreads) s_hist[i] = 0;
-  __syncthreads();
-  for (size_t i = lo + static_cast<size_t>(w) * 4 * kJlThreads + threadIdx.x; i < hi;
-       i += static_cast<size_t>(kJlHistWgPerGroup) * 4 * kJlThreads) {  // four independent loads per lane per step
-    unsigned k[4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) k[j] = i + j * kJlThreads < hi ? keys[i + j * kJlThreads] : 0u;
-#pragma unroll
-    for (int j = 0; j < 4; ++j)
-      if (i + j * kJlThreads < hi) atomicAdd(&s_hist[jl_pid_sel<RANK>(k[j], parts) >> k2_shift], 1u);
-  }
-  __syncthreads();
-  for (unsigned i = threadIdx.x; i < k1; i += kJlThreads)
-    if (s_hist[i]) atomicAdd(&counts_g[static_cast<size_t>(group) * k1 + i], static_cast<unsigned long long>(s_hist[i]));
-}
-
-// ---- both levels' histograms in ONE read of the keys (parts <= 32768: the counters fit 128 KiB of LDS) --------------
-// Workgroup (group g, w) counts the FINAL partition of every row of its share of group g in an LDS histogram of `parts`
-// bins and stores it, plainly, as its own row of wgcnt[][]; jl_hist_reduce sums the rows: per (group, level-0 bucket)
-// for the level-0 cursors and per partition for level 1.  Replaces jl_hist0 + jl_hist1: the second used to re-read the
-// level-0 output (8 bytes per row: 113 us of the 2^26-row build).
-constexpr unsigned kJlFusedWgPerGroup = 4;   // 64 groups x 4 = 256 workgroups of 1024 threads: one per CU
-constexpr unsigned kJlFusedThreads = 1024;
-#ifndef DBHIP_JL_FUSED_MAX_PARTS
-#define DBHIP_JL_FUSED_MAX_PARTS 32768
-#endif
-constexpr unsigned kJlFusedMaxParts = DBHIP_JL_FUSED_MAX_PARTS;  // 0 disables the fused histogram (A/B timing)
-// two 16-bit counters per LDS word (jl_hist_fused16_kernel): as many partitions as the CU's 160 KiB hold — 2^27 rows
-// and a quarter more (a rank of the 8-GPU join receives 2^27 rows +- a few thousand: 65537+ partitions)
-constexpr unsigned kJlFused16MaxParts = 80 * 1024;
-#ifndef DBHIP_JL_HIST_LOADS
-#define DBHIP_JL_HIST_LOADS 4
-#endif
-constexpr int kJlHistLoads = DBHIP_JL_HIST_LOADS;  // 16-byte key loads in flight per lane of the fused16 histogram
-
-__global__ __launch_bounds__(kJlFusedThreads) void jl_hist_fused_kernel(const unsigned *__restrict__ keys, size_t n, size_t group_rows,
-                                                                        unsigned parts, unsigned *__restrict__ wgcnt) {
-  extern __shared__ unsigned s_hist[];
-  const unsigned group = blockIdx.x / kJlFusedWgPerGroup, w = blockIdx.x % kJlFusedWgPerGroup;
-  for (unsigned i = threadIdx.x; i < parts; i += kJlFusedThreads) s_hist[i] = 0;
-  __syncthreads();
-  const size_t lo = static_cast<size_t>(group) * group_rows;
-  size_t hi = lo + group_rows;
-  hi = hi < n ? hi : n;
-  if (lo < hi && (reinterpret_cast<uintptr_t>(keys + lo) & 15u) == 0) {
-    // 16-byte loads, four in flight per lane (4-byte loads kept 16 KiB per CU in flight: 79 us for 256 MiB of keys)
-    const u32x4 *k4 = reinterpret_cast<const u32x4 *>(keys + lo);
-    const size_t n4 = (hi - lo) / 4;
-    for (size_t i = static_cast<size_t>(w) * 4 * kJlFusedThreads + threadIdx.x; i < n4;
-         i += static_cast<size_t>(kJlFusedWgPerGroup) * 4 * kJlFusedThreads) {
-      u32x4 v[4];
-#pragma unroll
-      for (int j = 0; j < 4; ++j) v[j] = i + j * kJlFusedThreads < n4 ? k4[i + j * kJlFusedThreads] : u32x4{0, 0, 0, 0};
-#pragma unroll
-      for (int j = 0; j < 4; ++j)
-        if (i + j * kJlFusedThreads < n4) {
-          atomicAdd(&s_hist[jl_pid(v[j].x, parts)], 1u);
-          atomicAdd(&s_hist[jl_pid(v[j].y, parts)], 1u);
-          atomicAdd(&s_hist[jl_pid(v[j].z, parts)], 1u);
-          atomicAdd(&s_hist[jl_pid(v[j].w, parts)], 1u);
-        }
-    }
-    if (w == 0 && lo + n4 * 4 + threadIdx.x < hi) atomicAdd(&s_hist[jl_pid(keys[lo + n4 * 4 + threadIdx.x], parts)], 1u);
-  } else {
-    for (size_t i = lo + static_cast<size_t>(w) * 4 * kJlFusedThreads + threadIdx.x; i < hi;
-         i += static_cast<size_t>(kJlFusedWgPerGroup) * 4 * kJlFusedThreads) {  // four independent loads per lane per step
-      unsigned k[4];
-#pragma unroll
-      for (int j = 0; j < 4; ++j) k[j] = i + j * kJlFusedThreads < hi ? keys[i + j * kJlFusedThreads] : 0u;
-#pragma unroll
-      for (int j = 0; j < 4; ++j)
-        if (i + j * kJlFusedThreads < hi) atomicAdd(&s_hist[jl_pid(k[j], parts)], 1u);
-    }
-  }
-  __syncthreads();
-  unsigned *mine = wgcnt + static_cast<size_t>(blockIdx.x) * parts;
-  for (unsigned i = threadIdx.x; i < parts; i += kJlFusedThreads) mine[i] = s_hist[i];
-}
-
-// ---- the same for 32768 < parts <= 65536 (2^27-row shards: what every rank of the 8-GPU join partitions) ----------------
-// 65536 32-bit counters do not fit the LDS; 16 bits are enough for a workgroup's share of a partition (2^27 rows / 256
-// workgroups / 65536 partitions = 8 rows) unless the input is heavily skewed.  TWO counters per LDS word, fed by
-// RETURNING ds_add: from the returned value a lane sees exactly when its increment carried out of the low half (the
-// even partition's counter wrapped and the odd one's now holds one too many) or out of bit 31 (the odd one wrapped) and
-// settles that in the global accumulators the reduce kernel adds to — correct for any input, and free for every input
-// that is not pathological.  The workgroup's row of wgcnt is the LDS image: parts / 2 words.
-__global__ __launch_bounds__(kJlFusedThreads) void jl_hist_fused16_kernel(const unsigned *__restrict__ keys, size_t n, size_t group_rows,
-                                                                          unsigned parts, unsigned log2_k2, unsigned k1,
-                                                                          unsigned *__restrict__ wgcnt,
-                                                                          unsigned long long *counts0g,
-                                                                          unsigned long long *counts1) {
-  extern __shared__ unsigned s_hist[];
-  const unsigned group = blockIdx.x / kJlFusedWgPerGroup, w = blockIdx.x % kJlFusedWgPerGroup;
-  const unsigned words = parts / 2;
-  for (unsigned i = threadIdx.x; i < words; i += kJlFusedThreads) s_hist[i] = 0;
-  __syncthreads();
-  auto count = [&](unsigned key) {
-    const unsigned p = jl_pid(key, parts);
-    const unsigned inc = 1u << ((p & 1u) << 4);
-    const unsigned old = atomicAdd(&s_hist[p >> 1], inc);
-    const bool carry16 = (p & 1u) == 0 && (old & 0xFFFFu) == 0xFFFFu, carry32 = old + inc < old;
-    if (carry16 || carry32) {  // (more than 65535 rows of this workgroup's share in one partition)
-      const unsigned even = p & ~1u, odd = p | 1u;
-      unsigned long long *g0 = counts0g + static_cast<size_t>(group) * k1;
-      if (carry16) {
-        atomicAdd(&counts1[even], 65536ull);
-        atomicAdd(&g0[even >> log2_k2], 65536ull);
-        atomicAdd(&counts1[odd], ~0ull);  // minus one: the carry landed in the odd partition's half
-        atomicAdd(&g0[odd >> log2_k2], ~0ull);
-      }
-      if (carry32) {
-        atomicAdd(&counts1[odd], 65536ull);
-        atomicAdd(&g0[odd >> log2_k2], 65536ull);
-      }
-    }
-  };
-  const size_t lo = static_cast<size_t>(group) * group_rows;
-  size_t hi = lo + group_rows;
-  hi = hi < n ? hi : n;
-  if (lo < hi && (reinterpret_cast<uintptr_t>(keys + lo) & 15u) == 0) {
-    const u32x4 *k4 = reinterpret_cast<const u32x4 *>(keys + lo);
-    const size_t n4 = (hi - lo) / 4;
-    // (round 4, measured and dropped: the next step's loads in flight while this step's keys are counted, two register
-    //  sets as in the group-by — 80.7 -> 99.6 us for the 256 MiB of keys of a 2^26-row side; eight loads per lane in
-    //  flight instead of four: partition of one side 572 -> 590 us, two: the same as four)
-    for (size_t i = static_cast<size_t>(w) * kJlHistLoads * kJlFusedThreads + threadIdx.x; i < n4;
-         i += static_cast<size_t>(kJlFusedWgPerGroup) * kJlHistLoads * kJlFusedThreads) {
-      u32x4 v[kJlHistLoads];
-#pragma unroll
-      for (int j = 0; j < kJlHistLoads; ++j) v[j] = i + j * kJlFusedThreads < n4 ? k4[i + j * kJlFusedThreads] : u32x4{0, 0, 0, 0};
-#pragma unroll
-      for (int j = 0; j < kJlHistLoads; ++j)
-        if (i + j * kJlFusedThreads < n4) {
-          count(v[j].x);
-          count(v[j].y);
-          count(v[j].z);
-          count(v[j].w);
-        }
-    }
-    if (w == 0 && lo + n4 * 4 + threadIdx.x < hi) count(keys[lo + n4 * 4 + threadIdx.x]);
-  } else {
-    for (size_t i = lo + static_cast<size_t>(w) * kJlFusedThreads + threadIdx.x; i < hi;
-         i += static_cast<size_t>(kJlFusedWgPerGroup) * kJlFusedThreads)
-      count(keys[i]);
-  }
-  __syncthreads();
-  unsigned *mine = wgcnt + static_cast<size_t>(blockIdx.x) * words;
-  for (unsigned i = threadIdx.x; i < words; i += kJlFusedThreads) mine[i] = s_hist[i];
-}
-
-// reduce of the packed rows; ADDS to counts1 / counts0g (zeroed with the metadata, and possibly holding the carries
-// the histogram kernel settled): one thread per WORD (two partitions) for the column sums, one wave per (row, bucket)
-// for the level-0 counts — the sum of both halves of a bucket's words
-__global__ __launch_bounds__(256) void jl_hist_reduce16_kernel(const unsigned *__restrict__ wgcnt, unsigned parts, unsigned k1,
-                                                               unsigned k2, unsigned long long *counts0g,
-                                                               unsigned long long *counts1) {
-  constexpr unsigned kRows = kJlGroups * kJlFusedWgPerGroup;
-  const unsigned words = parts / 2, col_blocks = (words + 255) / 256;
-  if (blockIdx.x < col_blocks) {
-    const unsigned wd = blockIdx.x * 256 + threadIdx.x;
-    if (wd >= words) return;
-    unsigned long long lo = 0, hi = 0;
-    for (unsigned r0 = 0; r0 < kRows; r0 += 8) {
-      unsigned v[8];
-#pragma unroll
-      for (int u = 0; u < 8; ++u) v[u] = wgcnt[static_cast<size_t>(r0 + u) * words + wd];
-#pragma unroll
-      for (int u = 0; u < 8; ++u) {
-        lo += v[u] & 0xFFFFu;
-        hi += v[u] >> 16;
-      }
-    }
-    counts1[2 * wd] += lo;  // (the histogram kernel has finished: no one else touches these words now)
-    counts1[2 * wd + 1] += hi;
-    return;
-  }
-  const unsigned lane = threadIdx.x & (kWave - 1), wave = threadIdx.x / kWave;
-  const size_t item = static_cast<size_t>(blockIdx.x - col_blocks) * 4 + wave;  // (row, bucket)
-  if (item >= static_cast<size_t>(kRows) * k1) return;
-  const unsigned row = static_cast<unsigned>(item / k1), bucket = static_cast<unsigned>(item % k1);
-  const unsigned *src = wgcnt + static_cast<size_t>(row) * words + static_cast<size_t>(bucket) * (k2 / 2);
-  unsigned mine = 0;
-  for (unsigned sub = lane; sub < k2 / 2; sub += kWave) mine += (src[sub] & 0xFFFFu) + (src[sub] >> 16);
-  mine = wave_reduce_add(mine);
-  if (lane == kWave - 1 && mine)
-    atomicAdd(&counts0g[static_cast<size_t>(row / kJlFusedWgPerGroup) * k1 + bucket], static_cast<unsigned long long>(mine));
-}
-
-// counts1[p] = rows of partition p (column sums of wgcnt, one thread per partition: the first parts/256 workgroups),
-// counts0g[g][b] = rows of group g in level-0 bucket b (one WAVE per (workgroup row, bucket): k2 contiguous counters,
-// added to the zeroed counts0g with one atomic per wave: the remaining workgroups)
-__global__ __launch_bounds__(256) void jl_hist_reduce_kernel(const unsigned *__restrict__ wgcnt, unsigned parts, unsigned k1,
-                                                             unsigned k2, unsigned long long *counts0g,
-                                                             unsigned long long *counts1) {
-  constexpr unsigned kRows = kJlGroups * kJlFusedWgPerGroup;
-  const unsigned col_blocks = (parts + 255) / 256;
-  if (blockIdx.x < col_blocks) {
-    const unsigned p = blockIdx.x * 256 + threadIdx.x;
-    if (p >= parts) return;
-    unsigned long long sum = 0;
-    for (unsigned r0 = 0; r0 < kRows; r0 += 8) {
-      unsigned v[8];
-#pragma unroll
-      for (int u = 0; u < 8; ++u) v[u] = wgcnt[static_cast<size_t>(r0 + u) * parts + p];
-#pragma unroll
-      for (int u = 0; u < 8; ++u) sum += v[u];
-    }
-    counts1[p] = sum;
-    return;
-  }
-  const unsigned lane = threadIdx.x & (kWave - 1), wave = threadIdx.x / kWave;
-  const size_t item = static_cast<size_t>(blockIdx.x - col_blocks) * 4 + wave;  // (row, bucket)
-  if (item >= static_cast<size_t>(kRows) * k1) return;
-  const unsigned row = static_cast<unsigned>(item / k1), bucket = static_cast<unsigned>(item % k1);
-  const unsigned *src = wgcnt + static_cast<size_t>(row) * parts + static_cast<size_t>(bucket) * k2;
-  unsigned mine = 0;
-  for (unsigned sub = lane; sub < k2; sub += kWave) mine += src[sub];
-  mine = wave_reduce_add(mine);
-  if (lane == kWave - 1 && mine)
-    atomicAdd(&counts0g[static_cast<size_t>(row / kJlFusedWgPerGroup) * k1 + bucket], static_cast<unsigned long long>(mine));
-}
-
-// bucket starts, per-group cursors and the tile index of every bucket (for the 1-D grid of level 1).
-// One workgroup, thread b owns bucket b (k1 <= 1024).
-__global__ __launch_bounds__(1024) void jl_offsets0_kernel(const unsigned long long *__restrict__ counts_g,
-                                                           unsigned k1, unsigned tile1, unsigned long long *cursors_g,
-                                                           unsigned long long *starts, unsigned long long *tile_starts,
-                                                           unsigned long long *totals_out) {
-  __shared__ unsigned long long s_tot[1024], s_start[1025], s_tstart[1025];
-  __shared__ unsigned long long s_wrow[16], s_wtile[16];
-  const unsigned b = threadIdx.x, lane = b & (kWave - 1), wave = b / kWave;
-  unsigned long long tot = 0;
-  if (b < k1)
-    for (unsigned g = 0; g < kJlGroups; ++g) tot += counts_g[static_cast<size_t>(g) * k1 + b];
-  s_tot[b] = tot;
-  // exclusive prefix over the buckets of rows and of level-1 tiles: wave scans + a 16-entry pass
-  const unsigned long long tl = b < k1 ? (tot + tile1 - 1) / tile1 : 0ull;  // tiles of the level-1 scatter (tile1 rows each)
-  unsigned long long ir = tot, it = tl;
-#pragma unroll
-  for (int off = 1; off < kWave; off <<= 1) {
-    const unsigned long long pr = __shfl_up(ir, off, kWave), pt = __shfl_up(it, off, kWave);
-    if (lane >= static_cast<unsigned>(off)) {
-      ir += pr;
-      it += pt;
-    }
-  }
-  if (lane == kWave - 1) {
-    s_wrow[wave] = ir;
-    s_wtile[wave] = it;
-  }
-  __syncthreads();
-  unsigned long long base_r = 0, base_t = 0;
-  for (unsigned w = 0; w < wave; ++w) {
-    base_r += s_wrow[w];
-    base_t += s_wtile[w];
-  }
-  s_start[b] = base_r + ir - tot;
-  s_tstart[b] = base_t + it - tl;
-  if (b == 1023) {
-    s_start[1024] = base_r + ir;
-    s_tstart[1024] = base_t + it;
-  }
-  __syncthreads();
-  if (b < k1) {
-    starts[b] = s_start[b];
-    tile_starts[b] = s_tstart[b];
-    if (totals_out) totals_out[b] = s_tot[b];
-    unsigned long long run = s_start[b];
-    for (unsigned g = 0; g < kJlGroups; ++g) {
-      cursors_g[static_cast<size_t>(g) * k1 + b] = run;
-      run += counts_g[static_cast<size_t>(g) * k1 + b];
-    }
-  }
-  if (b == 0) {
-    starts[k1] = s_start[k1];
-    tile_starts[k1] = s_tstart[k1];
-  }
-}
-
-// level 1: bucket b's k2 sub-buckets live inside [starts0[b], starts0[b+1]).  One workgroup per bucket.
-__global__ __launch_bounds__(kJlThreads) void jl_offsets1_kernel(const unsigned long long *__restrict__ counts1,
-                                                                 const unsigned long long *__restrict__ starts0,
-                                                                 unsigned k1, unsigned k2, unsigned long long *starts1,
-                                                                 unsigned long long *cursors1) {
-  __shared__ unsigned s_wsum[kJlThreads / kWave];
-  const unsigned b = blockIdx.x, tid = threadIdx.x, lane = tid & (kWave - 1), wave = tid / kWave;
-  const unsigned per = (k2 + kJlThreads - 1) / kJlThreads;  // <= 4
-  unsigned c[4] = {0, 0, 0, 0}, mine = 0;
-#pragma unroll
-  for (unsigned u = 0; u < 4; ++u) {
-    const unsigned sidx = tid * per + u;
-    if (u < per && sidx < k2) c[u] = static_cast<unsigned>(counts1[static_cast<size_t>(b) * k2 + sidx]);
-    mine += c[u];
-  }
-  const unsigned incl = wave_inclusive_scan(mine);
-  if (lane == kWave - 1) s_wsum[wave] = incl;
-  __syncthreads();
-  unsigned long long run = starts0[b] + incl - mine;
-  for (unsigned w = 0; w < wave; ++w) run += s_wsum[w];
-#pragma unroll
-  for (unsigned u = 0; u < 4; ++u) {
-    const unsigned sidx = tid * per + u;
-    if (u < per && sidx < k2) {
-      starts1[static_cast<size_t>(b) * k2 + sidx] = run;
-      cursors1[static_cast<size_t>(b) * k2 + sidx] = run;
-      run += c[u];
-    }
-  }
-  if (b == k1 - 1 && tid == 0) starts1[static_cast<size_t>(k1) * k2] = starts0[k1];
-}
-
-// Scatter of one 4096-row tile into `nb` (<= 1024) buckets, staged through LDS so that the global
-// writes are runs: rows are ranked inside their bucket with LDS atomics, the tile is re-ordered by
-// bucket in LDS, every bucket's run gets ONE global reservation, and consecutive lanes then write
-// consecutive addresses of a run.  LEVEL selects how the bucket is recomputed from the key on the way
-// out (0: pid >> arg, 1: pid & arg).  dest[j] == nb marks an invalid (out-of-range) row.
-// LDS: cnt[nb] | excl[nb] | base[nb] (u64) | keys[4096] | rids[4096] | 4 wave sums.
-constexpr size_t jl_scatter_lds_bytes(unsigned nb, unsigned tile = kJlTile, unsigned threads = kJlThreads) {
-  return static_cast<size_t>(nb) * 16 + 2 * static_cast<size_t>(tile) * sizeof(unsigned) + sizeof(unsigned) * (threads / kWave);
-}
-struct JlNoHook {
-  __device__ __forceinline__ void operator()() const {}
-};
-// before_stores(): called once, right before the tile's global stores are issued (the level-0 kernel waits there for
-// the next tile's prefetched keys: see jl_scatter0_kernel)
-template <int LEVEL, int THREADS, int KPT, bool RANK = false, bool DIGITS = false, class Hook = JlNoHook>
-__device__ __forceinline__ void jl_scatter_tile(const unsigned (&key)[KPT], const unsigned (&rid)[KPT],
-                                                const unsigned (&dest)[KPT], unsigned nb, unsigned parts,
-                                                unsigned arg, unsigned long long *cursors,
-                                                unsigned *__restrict__ out_keys, unsigned *__restrict__ out_rids,
-                                                unsigned *s_mem, Hook before_stores = Hook()) {
-  unsigned long long *s_base = reinterpret_cast<unsigned long long *>(s_mem);  // 8-byte aligned first
-  unsigned *s_cnt = s_mem + 2 * nb;
-  unsigned *s_excl = s_cnt + nb;
-  unsigned *s_keys = s_excl + nb;
-  unsigned *s_rids = s_keys + (THREADS * KPT);
-  unsigned *s_wsum = s_rids + (THREADS * KPT);
-  const unsigned tid = threadIdx.x, lane = tid & (kWave - 1), wave = tid / kWave;
-
-  for (unsigned i = tid; i < nb; i += THREADS) s_cnt[i] = 0;
-  __syncthreads();
-  unsigned rank[KPT];
-#pragma unroll
-  for (int j = 0; j < KPT; ++j) rank[j] = dest[j] < nb ? atomicAdd(&s_cnt[dest[j]], 1u) : 0u;
-  __syncthreads();
-  // exclusive scan of the bucket counts (nb <= 1024: up to 4 consecutive buckets per thread)
-  const unsigned per = (nb + THREADS - 1) / THREADS;
-  unsigned c[4] = {0, 0, 0, 0}, mine = 0;
-#pragma unroll
-  for (unsigned u = 0; u < 4; ++u) {
-    const unsigned b = tid * per + u;
-    if (u < per && b < nb) c[u] = s_cnt[b];
-    mine += c[u];
-  }
-  const unsigned incl = wave_inclusive_scan(mine);
-  if (lane == kWave - 1) s_wsum[wave] = incl;
-  __syncthreads();
-  unsigned run = incl - mine;
-  for (unsigned w = 0; w < wave; ++w) run += s_wsum[w];
-  unsigned total = 0;
-#pragma unroll
-  for (int w = 0; w < (THREADS / kWave); ++w) total += s_wsum[w];
-#pragma unroll
-  for (unsigned u = 0; u < 4; ++u) {
-    const unsigned b = tid * per + u;
-    if (u < per && b < nb) {
-      s_excl[b] = run;
-      // (one returning global atomic per bucket per tile; replacing them by a precomputed offset in a timing
-      //  experiment did not make the kernel faster: the reservations are not what bounds it)
-      s_base[b] = c[u] ? atomicAdd(&cursors[b], static_cast<unsigned long long>(c[u])) : 0ull;
-      run += c[u];
-    }
-  }
-  __syncthreads();
-#pragma unroll
-  for (int j = 0; j < KPT; ++j) {
-    if (dest[j] < nb) {
-      const unsigned p = s_excl[dest[j]] + rank[j];
-      s_keys[p] = key[j];
-      s_rids[p] = rid[j];
-    }
-  }
-  __syncthreads();
-  before_stores();
-  for (unsigned p = tid; p < total; p += THREADS) {
-    const unsigned k = s_keys[p];
-    const unsigned pid = jl_pid_sel<RANK>(k, parts);
-    const unsigned d = LEVEL == 0 ? pid >> arg : pid & arg;
-    const size_t slot = s_base[d] + (p - s_excl[d]);
-    if (DIGITS) {  // pairs + the row's level-1 bucket as a 16-bit column of its own (behind `out_rids`): what the level-1
-                   // histogram reads instead of the pairs, 2 bytes per row for 8 (jl_hist1d_kernel)
-      reinterpret_cast<u32x2 *>(out_keys)[slot] = u32x2{k, s_rids[p]};
-      reinterpret_cast<unsigned short *>(out_rids)[slot] = static_cast<unsigned short>(pid & ((1u << arg) - 1u));
-    } else if (out_rids) {  // two columns (the rank-level partition: its outputs go into an all-to-all as they are)
-      out_keys[slot] = k;
-      out_rids[slot] = s_rids[p];
-    } else {  // one array of (key, row id) pairs: one 8-byte store per row, a run of r rows is 8r contiguous bytes
-      // (plain stores: the runs of neighbouring tiles meet in L2; non-temporal stores here made a partition side of
-      //  2^26 rows 778 us instead of 602)
-      reinterpret_cast<u32x2 *>(out_keys)[slot] = u32x2{k, s_rids[p]};
-    }
-  }
-  __syncthreads();  // LDS is reused by the next tile
-}
-
-// level-0 scatter: (key, row id) pairs bucket-major; row id = index (or row_ids[index] when given)
-// THREADS x KPT rows per tile (JlShape); RIDS: row ids come as a column (the received pairs of the multi-GPU join) —
-// a template parameter so that the other callers do not carry the prefetched row-id registers
-#ifndef DBHIP_JL_SC0_WPE
-#define DBHIP_JL_SC0_WPE 6
-#endif
-template <bool RANK, bool RIDS, int THREADS, int KPT, bool DIGITS = false>
-__global__ __launch_bounds__(THREADS) __attribute__((amdgpu_waves_per_eu(THREADS == 512 && !RIDS ? DBHIP_JL_SC0_WPE : 1))) void jl_scatter0_kernel(const unsigned *__restrict__ keys,
-                                                                 const unsigned *__restrict__ row_ids,
-                                                                 unsigned long long first_row, size_t n,
-                                                                 unsigned parts, unsigned k2_shift, unsigned k1,
-                                                                 unsigned long long *cursors,
-                                                                 unsigned *__restrict__ out_keys,
-                                                                 unsigned *__restrict__ out_rids) {
-  extern __shared__ __attribute__((aligned(16))) unsigned s_mem[];
-  const size_t tiles = (n + (THREADS * KPT) - 1) / (THREADS * KPT);
-  // XCD-aware tile order (speed only, any order is correct): workgroups are dealt to the 8 XCDs round-robin by
-  // blockIdx, so XCD x = blockIdx % 8 takes the tile groups g with g % 8 == x.  A (group, bucket) write frontier is
-  // then advanced by ONE XCD, whose L2 merges the partial lines of consecutive runs before they leave for memory
-  // (WRITE_SIZE 770 MB for 537 MB stored when every XCD touched every frontier; 338 -> 310 us at 2^26 rows).
-  // The same slicing of the level-1 scatter (buckets b % 8 == x per XCD, persistent grid) measured no faster.
-  const size_t tpg = jl_group_rows(n, THREADS * KPT) / (THREADS * KPT);
-  const unsigned xcd = blockIdx.x % 8u, slot = blockIdx.x / 8u, per_xcd = gridDim.x / 8u;  // host: grid % 8 == 0
-  const size_t locals = (kJlGroups / 8) * tpg;
-  // tile of the workgroup's `local`-th step, or `tiles` when that step has none (the ragged end of the last group)
-  auto tile_of = [&](size_t local, size_t *group) -> size_t {
-    *group = (local / tpg) * 8 + xcd;
-    const size_t tile = *group * tpg + local % tpg;
-    return local < locals && tile < tiles ? tile : tiles;
-  };
-  auto load_tile = [&](size_t tile, unsigned (&k)[KPT], unsigned (&r)[KPT]) {
-#pragma unroll
-    for (int j = 0; j < KPT; ++j) {
-      const size_t idx = tile * (THREADS * KPT) + static_cast<size_t>(j) * THREADS + threadIdx.x;
-      const bool valid = tile < tiles && idx < n;
-      k[j] = valid ? keys[idx] : 0u;
-      r[j] = RIDS && valid ? row_ids[idx] : 0u;
-    }
-  };
-  // The next tile's keys are requested before the current tile's LDS work and waited for right before the current
-  // tile's stores go out (vmcnt counts a wave's loads and stores in issue order: waiting for loads at the top of the
-  // next step would also wait for every store of this one).  They cross the loop in registers moved by a v_mov the
-  // compiler cannot see through — a loop-carried register that a load defined is waited for with vmcnt(0) at first use.
-  unsigned ckey[KPT], crid[KPT];
-  size_t group = 0, tile = tile_of(slot, &group);
-  load_tile(tile, ckey, crid);
-#pragma unroll
-  for (int j = 0; j < KPT; ++j) {
-    asm volatile("v_mov_b32 %0, %0" : "+v"(ckey[j]));
-    if (RIDS) asm volatile("v_mov_b32 %0, %0" : "+v"(crid[j]));
-  }
-  for (size_t local = slot; local < locals; local += per_xcd) {
-    size_t ngroup = 0;
-    const size_t ntile = tile_of(local + per_xcd, &ngroup);
-    unsigned nkey[KPT], nrid[KPT], mkey[KPT], mrid[KPT];
-    load_tile(ntile, nkey, nrid);
-    auto wait_next = [&]() {
-#pragma unroll
-      for (int j = 0; j < KPT; ++j) {
-        asm volatile("v_mov_b32 %0, %1" : "=v"(mkey[j]) : "v"(nkey[j]));
-        if (RIDS) asm volatile("v_mov_b32 %0, %1" : "=v"(mrid[j]) : "v"(nrid[j]));
-        else mrid[j] = 0u;
-      }
-    };
-    if (tile < tiles) {  // uniform over the workgroup
-      const size_t base = tile * (THREADS * KPT);
-      unsigned rid[KPT], dest[KPT];
-#pragma unroll
-      for (int j = 0; j < KPT; ++j) {
-        const size_t idx = base + static_cast<size_t>(j) * THREADS + threadIdx.x;
-        const bool valid = idx < n;
-        rid[j] = valid ? (RIDS ? crid[j] : static_cast<unsigned>(first_row + idx)) : 0u;
-        dest[j] = valid ? jl_pid_sel<RANK>(ckey[j], parts) >> k2_shift : k1;
-      }
-      // this tile bumps only its group's cursors
-      jl_scatter_tile<0, THREADS, KPT, RANK, DIGITS>(ckey, rid, dest, k1, parts, k2_shift, cursors + group * k1, out_keys, out_rids, s_mem, wait_next);
-    } else {
-      wait_next();
-    }
-#pragma unroll
-    for (int j = 0; j < KPT; ++j) {
-      ckey[j] = mkey[j];
-      crid[j] = mrid[j];
-    }
-    tile = ntile;
-    group = ngroup;
-  }
-}
-
-// (bucket, tile-in-bucket) of virtual tile `vt` by binary search over tile_starts[0..k1]
-__device__ __forceinline__ bool jl_locate(const unsigned long long *__restrict__ tile_starts, unsigned k1,
-                                          unsigned long long vt, unsigned *bucket, unsigned long long *tile) {
-  if (vt >= tile_starts[k1]) return false;
-  unsigned lo = 0, hi = k1;  // find largest b with tile_starts[b] <= vt
-  while (hi - lo > 1) {
-    const unsigned mid = (lo + hi) / 2;
-    if (tile_starts[mid] <= vt) lo = mid; else hi = mid;
-  }
-  *bucket = lo;
-  *tile = vt - tile_starts[lo];
-  return true;
-}
-
-// level-1 histogram: kJlHist1WgPerBucket workgroups stride over one level-0 bucket (four independent loads per
-// lane per step), so a bucket's k2 counters see 16 flushes instead of one per scatter tile
-constexpr unsigned kJlHist1WgPerBucket = 16;
-
-__global__ __launch_bounds__(kJlThreads) void jl_hist1_kernel(const u32x2 *__restrict__ rows,
-                                                              const unsigned long long *__restrict__ starts0,
-                                                              unsigned parts, unsigned k2,
-                                                              unsigned long long *counts1) {
-  extern __shared__ unsigned s_hist[];
-  const unsigned bucket = blockIdx.x / kJlHist1WgPerBucket, w = blockIdx.x % kJlHist1WgPerBucket;
-  const size_t lo = starts0[bucket], hi = starts0[bucket + 1];
-  if (lo + static_cast<size_t>(w) * 4 * kJlThreads >= hi) return;
-  for (unsigned i = threadIdx.x; i < k2; i += kJlThreads) s_hist[i] = 0;
-  __syncthreads();
-  for (size_t i = lo + static_cast<size_t>(w) * 4 * kJlThreads + threadIdx.x; i < hi;
-       i += static_cast<size_t>(kJlHist1WgPerBucket) * 4 * kJlThreads) {
-    unsigned k[4];  // the level-0 output is (key, row id) pairs: the histogram reads them whole (8 bytes per row)
-#pragma unroll
-    for (int j = 0; j < 4; ++j) k[j] = i + j * kJlThreads < hi ? rows[i + j * kJlThreads].x : 0u;
-#pragma unroll
-    for (int j = 0; j < 4; ++j)
-      if (i + j * kJlThreads < hi) atomicAdd(&s_hist[jl_pid(k[j], parts) & (k2 - 1)], 1u);
-  }
-  __syncthreads();
-  for (unsigned i = threadIdx.x; i < k2; i += kJlThreads)
-    if (s_hist[i]) atomicAdd(&counts1[static_cast<size_t>(bucket) * k2 + i], static_cast<unsigned long long>(s_hist[i]));
-}
-
-// The same histogram from the 16-bit level-1 bucket column the level-0 scatter wrote beside its pairs (jl_scatter_tile
-// DIGITS; the 16384-row shape, i.e. 2^28 rows and more): 2 bytes per row instead of 8, and no hash.  Eight digits per
-// 16-byte load over the aligned middle of the bucket's range, the ragged ends one digit per lane.
-__global__ __launch_bounds__(kJlThreads) void jl_hist1d_kernel(const unsigned short *__restrict__ digits,
-                                                               const unsigned long long *__restrict__ starts0, unsigned k2,
-                                                               unsigned long long *counts1) {
-  extern __shared__ unsigned s_hist[];
-  const unsigned bucket = blockIdx.x / kJlHist1WgPerBucket, w = blockIdx.x % kJlHist1WgPerBucket;
-  const size_t lo = starts0[bucket], hi = starts0[bucket + 1];
-  if (lo >= hi) return;
-  for (unsigned i = threadIdx.x; i < k2; i += kJlThreads) s_hist[i] = 0;
-  __syncthreads();
-  const unsigned mask = k2 - 1;
-  // head [lo, a) and tail [b, hi) one digit per lane (first workgroup of the bucket), [a, b) in whole 16-byte vectors
-  size_t a = (lo + 7) & ~static_cast<size_t>(7);
-  if (a > hi) a = hi;
-  size_t b = hi & ~static_cast<size_t>(7);
-  if (b < a) b = a;
-  if (w == 0) {
-    for (size_t i = lo + threadIdx.x; i < a; i += kJlThreads) atomicAdd(&s_hist[digits[i] & mask], 1u);
-    for (size_t i = b + threadIdx.x; i < hi; i += kJlThreads) atomicAdd(&s_hist[digits[i] & mask], 1u);
-  }
-  const u32x4 *vec = reinterpret_cast<const u32x4 *>(digits);
-  const size_t va = a / 8, vb = b / 8;
-  for (size_t v = va + static_cast<size_t>(w) * 2 * kJlThreads + threadIdx.x; v < vb;
-       v += static_cast<size_t>(kJlHist1WgPerBucket) * 2 * kJlThreads) {
-    u32x4 x[2];
-    const bool second = v + kJlThreads < vb;
-    x[0] = vec[v];
-    x[1] = second ? vec[v + kJlThreads] : u32x4{0u, 0u, 0u, 0u};
-#pragma unroll
-    for (int j = 0; j < 2; ++j) {
-      if (j == 1 && !second) break;
-      const unsigned word[4] = {x[j].x, x[j].y, x[j].z, x[j].w};
-#pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        atomicAdd(&s_hist[word[q] & mask], 1u);
-        atomicAdd(&s_hist[(word[q] >> 16) & mask], 1u);
-      }
-    }
-  }
-  __syncthreads();
-  for (unsigned i = threadIdx.x; i < k2; i += kJlThreads)
-    if (s_hist[i]) atomicAdd(&counts1[static_cast<size_t>(bucket) * k2 + i], static_cast<unsigned long long>(s_hist[i]));
-}
-
-// Level-1 scatter: a PERSISTENT grid of the resident workgroups over the "virtual tiles" (every level-0 bucket cut into
-// tiles of THREADS x KPT rows; tile_starts[b] = index of bucket b's first tile).  XCD x walks the x-th eighth of the
-// virtual tiles, its workgroups interleaved (workgroup j: tiles j, j + per, ...), so the tiles in flight on an XCD
-// belong to one or two level-0 buckets, whose k2 write frontiers then meet in ONE L2; a workgroup finds its next tile
-// by stepping on from the current one (the bucket changes every few steps: one or two loads), requests its rows
-// before the current tile's LDS work and waits for them right before the current tile's stores (the vmcnt rule of
-// jl_scatter0_kernel).  Until round 4 this was one tile per workgroup, each starting with a binary search for its
-// tile (eight to ten dependent loads) and then its row loads: radix join 2^22 / 2^24 / 2^26 / 2^27 rows 212 / 514 / 1737 /
-// 3240 us -> 205 / 496 / 1671 / 3144 (4096-row tiles), 2^30 rows 31.3 -> 26.8 ms (8192-row tiles; 16384-row ones 28.2:
-// their 32 prefetched words per lane no longer fit the 128 VGPRs of a 1024-thread workgroup).
-template <int THREADS, int KPT>
-__global__ __launch_bounds__(THREADS) void jl_scatter1p_kernel(const u32x2 *__restrict__ rows,
-                                                               const unsigned long long *__restrict__ starts0,
-                                                               const unsigned long long *__restrict__ tile_starts,
-                                                               unsigned parts, unsigned k1, unsigned k2,
-                                                               unsigned long long *cursors1, u32x2 *__restrict__ out_pairs) {
-  extern __shared__ __attribute__((aligned(16))) unsigned s_mem[];
-  constexpr unsigned kTile = THREADS * KPT;
-  const unsigned long long total = tile_starts[k1];
-  const unsigned xcd = blockIdx.x % 8u, j = blockIdx.x / 8u, per = gridDim.x / 8u;  // host: gridDim.x % 8 == 0
-  const unsigned long long per_xcd = (total + 7) / 8;
-  const unsigned long long vend = (xcd + 1) * per_xcd < total ? (xcd + 1) * per_xcd : total;
-  unsigned long long vt = xcd * per_xcd + j;
-  if (vt >= vend) return;
-  unsigned bucket;
-  unsigned long long tile;
-  if (!jl_locate(tile_starts, k1, vt, &bucket, &tile)) return;
-  auto load_tile = [&](unsigned b, unsigned long long t, unsigned (&k)[KPT], unsigned (&r)[KPT]) {
-    const size_t lo = starts0[b] + t * kTile, hi = starts0[b + 1];
-#pragma unroll
-    for (int q = 0; q < KPT; ++q) {
-      const size_t idx = lo + static_cast<size_t>(q) * THREADS + threadIdx.x;
-      const u32x2 row = idx < hi ? rows[idx] : u32x2{0u, 0u};  // (idx < lo + kTile by construction)
-      k[q] = row.x;
-      r[q] = row.y;
-    }
-  };
-  unsigned ckey[KPT], crid[KPT];
-  load_tile(bucket, tile, ckey, crid);
-#pragma unroll
-  for (int q = 0; q < KPT; ++q) {
-    asm volatile("v_mov_b32 %0, %0" : "+v"(ckey[q]));
-    asm volatile("v_mov_b32 %0, %0" : "+v"(crid[q]));
-  }
-  while (true) {
-    // the next tile of this workgroup: step on from the current bucket
-    const unsigned long long nvt = vt + per;
-    const bool more = nvt < vend;
-    unsigned nbucket = bucket;
-    if (more)
-      while (nbucket + 1 < k1 && nvt >= tile_starts[nbucket + 1]) ++nbucket;
-    const unsigned long long ntile = more ? nvt - tile_starts[nbucket] : 0ull;
-    unsigned nkey[KPT], nrid[KPT], mkey[KPT], mrid[KPT];
-    if (more) {
-      load_tile(nbucket, ntile, nkey, nrid);
-    } else {
-#pragma unroll
-      for (int q = 0; q < KPT; ++q) nkey[q] = nrid[q] = 0u;
-    }
-    auto wait_next = [&]() {
-#pragma unroll
-      for (int q = 0; q < KPT; ++q) {
-        asm volatile("v_mov_b32 %0, %1" : "=v"(mkey[q]) : "v"(nkey[q]));
-        asm volatile("v_mov_b32 %0, %1" : "=v"(mrid[q]) : "v"(nrid[q]));
-      }
-    };
-    {
-      const size_t lo = starts0[bucket] + tile * kTile, hi = starts0[bucket + 1];
-      unsigned dest[KPT];
-#pragma unroll
-      for (int q = 0; q < KPT; ++q) {
-        const size_t idx = lo + static_cast<size_t>(q) * THREADS + threadIdx.x;
-        dest[q] = idx < hi ? jl_pid(ckey[q], parts) & (k2 - 1) : k2;
-      }
-      jl_scatter_tile<1, THREADS, KPT, false>(ckey, crid, dest, k2, parts, k2 - 1, cursors1 + static_cast<size_t>(bucket) * k2,
-                                              reinterpret_cast<unsigned *>(out_pairs), nullptr, s_mem, wait_next);
-    }
-    if (!more) break;
-#pragma unroll
-    for (int q = 0; q < KPT; ++q) {
-      ckey[q] = mkey[q];
-      crid[q] = mrid[q];
-    }
-    vt = nvt;
-    bucket = nbucket;
-    tile = ntile;
-  }
-}
 
 // ---- per-partition build in LDS --------------------------------------------------------------------
 // A partition's rows come either as two columns (the level-0 output, when one level suffices) or as (key, row id)
@@ -1884,270 +1162,24 @@ __global__ __launch_bounds__(kJlThreads) void jl_uprobe_kernel(const unsigned *_
   }
 }
 
-// grid of the level-0 scatter: a multiple of 8 (one slice of workgroups per XCD)
-inline unsigned jl_scatter0_grid(size_t tiles, size_t cap) {
-  static const int forced = [] { const char *e = getenv("DBHIP_JL_SC0_WGS"); return e ? atoi(e) : 0; }();  // experiment knob: workgroups per CU
-  if (forced >= 1 && forced <= 32) cap = static_cast<size_t>(forced) * 256;  // (knob: per CU of a 256-CU chip)
-  size_t g = tiles < cap ? tiles : cap;
-  g = (g + 7) / 8 * 8;
-  return static_cast<unsigned>(g ? g : 8);
-}
-
-inline unsigned jl_grid(size_t items, const DeviceInfo &dev, int per_cu) {
-  const size_t want = (items + kJlThreads - 1) / kJlThreads;
-  const size_t cap = static_cast<size_t>(dev.cus) * per_cu;
-  return static_cast<unsigned>(want < cap ? (want ? want : 1) : cap);
-}
-
-
-// ---- tile shapes of the two scatter levels ---------------------------------------------------------------------------
-// 0: 512 threads x 8 rows = 4096-row tiles (36 KiB + 16 B per bucket of LDS) — the shape every size up to 2^27 rows was
-//    tuned on;  1: 1024 x 8 = 8192 rows;  2 (level 0 only): 1024 x 16 = 16384 rows (128 KiB of LDS: one workgroup per CU).
-// A tile of T rows into nb buckets writes runs of T / nb rows and takes one returning global atomic per bucket: with the
-// 586 x 1024 buckets of a 2^30-row side a 4096-row tile writes 56- and 32-byte runs and one atomic per 7 / 4 rows (level 0
-// at 2.8 TB/s, level 1 at 2.6, against 4.0 / 3.9 at 2^26 rows with 293 x 128 buckets).  DBHIP_JL_T0 / DBHIP_JL_T1 force a
-// shape (experiments; T1 = 2 reads as 1).
-struct JlShape {
-  int t0, t1;
-};
-inline unsigned jl_shape_rows(int id) { return id == 0 ? 4096u : id == 1 ? 8192u : 16384u; }
-inline unsigned jl_shape_threads(int id) { return id == 0 ? 512u : 1024u; }
-inline int jl_env_shape(const char *name) {
-  const char *e = getenv(name);
-  return e && e[0] >= '0' && e[0] <= '2' && !e[1] ? e[0] - '0' : -1;
-}
-inline JlShape jl_shape_for(size_t n, unsigned k1, unsigned k2) {
-  static const int f0 = jl_env_shape("DBHIP_JL_T0"), f1 = jl_env_shape("DBHIP_JL_T1");
-  (void)n;
-  // Measured (radix join, us, t0/t1; same box per size).  Level 1 one tile per workgroup, before it became persistent:
-  // 2^26 rows (293 x 128 buckets) 0/0 1838, 1/1 1862, 2/2 2039; 2^27 (293 x 256) 0/0 3406, 1/1 3502, 2/2 3805; 2^28 (586 x 256)
-  // 0/0 7776, 1/0 7521, 2/0 7261, 2/1 7425, 2/2 8089; 2^29 (586 x 512) 0/0 16214, 2/0 15225, 1/1 15196, 2/1 14567, 2/2 15836;
-  // 2^30 (586 x 1024) 0/0 35256, 2/0 33994, 0/2 33265, 1/2 32852, 2/2 32558.  Persistent level 1: 2^26 x/0 1671, x/1 1703;
-  // 2^27 x/0 3144, x/1 3157; 2^28 2/0 6829, 2/1 6769, 0/1 7181, 1/1 7007; 2^30 2/0 29565, 2/1 26830, 1/1 27381, 0/1 27871.
-  JlShape sh{0, 0};
-  if (k1 >= 512) sh.t0 = 2;
-  if (k2 >= 512) sh.t1 = 1;
-  if (f0 >= 0) sh.t0 = f0;
-  if (f1 >= 0) sh.t1 = f1 > 1 ? 1 : f1;
-  return sh;
-}
-
-// resident workgroups per CU of `kernel` with `lds` bytes of dynamic LDS: asked of the runtime once per (kernel, lds) and
-// host thread, not on every launch
-inline int jl_resident_blocks(const void *kernel, int threads, size_t lds) {
-  thread_local const void *last_kernel = nullptr;
-  thread_local size_t last_lds = 0;
-  thread_local int last_blocks = 0;
-  if (kernel != last_kernel || lds != last_lds || last_blocks < 1) {
-    int blocks = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&blocks, kernel, threads, lds) != hipSuccess || blocks < 1) {
-      (void)hipGetLastError();
-      blocks = 1;
-    }
-    last_kernel = kernel;
-    last_lds = lds;
-    last_blocks = blocks;
-  }
-  return last_blocks;
-}
-
-template <bool RANK, bool RIDS, int THREADS, int KPT, bool DIGITS = false>
-hipError_t jl_launch_scatter0_shape(const DeviceInfo &dev, hipStream_t s, const unsigned *keys, const unsigned *row_ids,
-                                    unsigned long long first_row, size_t n, unsigned parts, unsigned k2_shift, unsigned k1,
-                                    unsigned long long *cursors, unsigned *out_keys, unsigned *out_rids) {
-  constexpr unsigned kTile = THREADS * KPT;
-  const size_t lds = jl_scatter_lds_bytes(k1, kTile, THREADS);
-  auto kernel = jl_scatter0_kernel<RANK, RIDS, THREADS, KPT, DIGITS>;
-  if (lds > 48 * 1024) {
-    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                             static_cast<int>(lds));
-    if (e != hipSuccess) return e;
-  }
-  const size_t tiles = (n + kTile - 1) / kTile;
-  // persistent grid of the workgroups that are resident (round 4: the 4096-row shape ran with eight per CU where its
-  // registers allowed two; held to 80 VGPRs — amdgpu_waves_per_eu(6) — three are, and a grid of exactly those measured
-  // 1.5-2 % of the radix join at 2^26 rows: 1759-1777 -> 1726-1740 us on the same box)
-  const size_t per_cu = static_cast<size_t>(jl_resident_blocks(reinterpret_cast<const void *>(kernel), THREADS, lds));
-  hipLaunchKernelGGL(kernel, dim3(jl_scatter0_grid(tiles, static_cast<size_t>(dev.cus) * per_cu)), dim3(THREADS), lds, s, keys,
-                     row_ids, first_row, n, parts, k2_shift, k1, cursors, out_keys, out_rids);
-  return hipSuccess;
-}
-template <bool RANK>
-hipError_t jl_launch_scatter0(int shape, const DeviceInfo &dev, hipStream_t s, const unsigned *keys, const unsigned *row_ids,
-                              unsigned long long first_row, size_t n, unsigned parts, unsigned k2_shift, unsigned k1,
-                              unsigned long long *cursors, unsigned *out_keys, unsigned *out_rids, bool digits = false) {
-  // digits: pairs into out_keys AND every row's level-1 bucket as a 16-bit column behind out_rids
-  if (digits) {
-    if (RANK) return hipErrorInvalidValue;
-#define JL_SC0D(RIDS, T, K) \
-  jl_launch_scatter0_shape<false, RIDS, T, K, true>(dev, s, keys, row_ids, first_row, n, parts, k2_shift, k1, cursors, out_keys, out_rids)
-    if (row_ids) return shape == 0 ? JL_SC0D(true, 512, 8) : shape == 1 ? JL_SC0D(true, 1024, 8) : JL_SC0D(true, 1024, 16);
-    return shape == 0 ? JL_SC0D(false, 512, 8) : shape == 1 ? JL_SC0D(false, 1024, 8) : JL_SC0D(false, 1024, 16);
-#undef JL_SC0D
-  }
-#define JL_SC0(RIDS, T, K) \
-  jl_launch_scatter0_shape<RANK, RIDS, T, K>(dev, s, keys, row_ids, first_row, n, parts, k2_shift, k1, cursors, out_keys, out_rids)
-  if (row_ids) {
-    if (RANK) return hipErrorInvalidValue;  // (the rank-level partition numbers its rows itself)
-    return shape == 0 ? JL_SC0(!RANK, 512, 8) : shape == 1 ? JL_SC0(!RANK, 1024, 8) : JL_SC0(!RANK, 1024, 16);
-  }
-  return shape == 0 ? JL_SC0(false, 512, 8) : shape == 1 ? JL_SC0(false, 1024, 8) : JL_SC0(false, 1024, 16);
-#undef JL_SC0
-}
-
-template <int THREADS, int KPT>
-hipError_t jl_launch_scatter1_shape(hipStream_t s, size_t n, const u32x2 *rows, const unsigned long long *starts0,
-                                    const unsigned long long *tstarts0, unsigned parts, unsigned k1, unsigned k2,
-                                    unsigned long long *cursors1, u32x2 *out, const DeviceInfo &dev) {
-  constexpr unsigned kTile = THREADS * KPT;
-  const size_t lds = jl_scatter_lds_bytes(k2, kTile, THREADS);
-  auto kernel = jl_scatter1p_kernel<THREADS, KPT>;
-  if (lds > 48 * 1024) {
-    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                             static_cast<int>(lds));
-    if (e != hipSuccess) return e;
-  }
-  const int blocks = jl_resident_blocks(reinterpret_cast<const void *>(kernel), THREADS, lds);
-  const size_t vtiles = ((n + kTile - 1) / kTile + k1 + 7) / 8 * 8;  // every bucket's last tile may be ragged
-  size_t grid = static_cast<size_t>(dev.cus) * blocks / 8 * 8;       // the resident workgroups, a whole number per XCD
-  if (grid < 8) grid = 8;
-  if (grid > vtiles) grid = vtiles;
-  hipLaunchKernelGGL(kernel, dim3(static_cast<unsigned>(grid)), dim3(THREADS), lds, s, rows, starts0, tstarts0, parts, k1, k2,
-                     cursors1, out);
-  return hipSuccess;
-}
-inline hipError_t jl_launch_scatter1(int shape, hipStream_t s, size_t n, const u32x2 *rows, const unsigned long long *starts0,
-                                     const unsigned long long *tstarts0, unsigned parts, unsigned k1, unsigned k2,
-                                     unsigned long long *cursors1, u32x2 *out, const DeviceInfo &dev) {
-  return shape == 0 ? jl_launch_scatter1_shape<512, 8>(s, n, rows, starts0, tstarts0, parts, k1, k2, cursors1, out, dev)
-                    : jl_launch_scatter1_shape<1024, 8>(s, n, rows, starts0, tstarts0, parts, k1, k2, cursors1, out, dev);
-}
-
-}  // namespace
-
-namespace {
+// ---- host side (called from join.hip's entry points) ---------------------------------------------------
 struct JlPartitioned {
-  const unsigned *keys, *rids;             // partition-major rows: (key, row id) pairs behind `keys`, rids == nullptr
+  const unsigned *pairs;                   // partition-major (key, row id) pairs
   const unsigned long long *starts;        // parts + 1 offsets
   u32x2 *table;
   unsigned *status;
 };
-}  // namespace
-
-// The one or two scatter levels shared by all joins, for a column of n rows and a partition geometry that may come
-// from ANOTHER column (the radix join partitions the probe side by the build side's geometry): level-0 output in
-// rows_a, level-1 output (k2 > 1) in rows_b, offsets in `meta` (jl_meta_bytes(k1, parts) bytes).
-int jl_partition_side(const unsigned *keys, const unsigned *row_ids, size_t n, unsigned parts, unsigned k1, unsigned k2,
-                      unsigned log2_k2, u32x2 *rows_a, u32x2 *rows_b, unsigned long long *meta, size_t meta_bytes,
-                      hipStream_t s, const DeviceInfo &dev, const unsigned **out_pairs,
-                      const unsigned long long **out_starts) {
-  // meta: counts0g[G*k1] | cursors0g[G*k1] | starts0[k1+1] | tile_starts0[k1+1] | counts1[K] | starts1[K+1] | cursors1[K]
-  unsigned long long *counts0 = meta;
-  unsigned long long *cursors0 = counts0 + static_cast<size_t>(kJlGroups) * k1;
-  unsigned long long *starts0 = cursors0 + static_cast<size_t>(kJlGroups) * k1;
-  unsigned long long *tstarts0 = starts0 + k1 + 1;
-  unsigned long long *counts1 = tstarts0 + k1 + 1;
-  unsigned long long *starts1 = counts1 + parts;
-  unsigned long long *cursors1 = starts1 + parts + 1;
-
-  const hipError_t e = fill_async(meta, 0, meta_bytes, s);
-  if (e != hipSuccess) return static_cast<int>(e);
-  // scratch of the fused histogram: 256 rows of `parts` counters, in the level-1 output region while it is still unused
-  // (it holds 8n bytes; 1 KiB per partition is enough whenever a partition averages >= 128 rows)
-  unsigned *fused_scratch = (k2 > 1 && n * 8 >= static_cast<size_t>(kJlGroups) * kJlFusedWgPerGroup * parts * sizeof(unsigned))
-                                ? reinterpret_cast<unsigned *>(rows_b) : nullptr;
-
-  // both levels write (key, row id) as ONE 8-byte element: a run of r rows is 8r contiguous bytes instead of two
-  // runs of 4r (the scatters are bound by partially written lines: level 1 went 330 -> 254 us at 2^26 rows when it
-  // switched, level 0 followed once the level-1 histogram read pairs instead of a keys-only column)
-  const unsigned k2_shift = log2_k2;
-  const JlShape shape = jl_shape_for(n, k1, k2);
-  const size_t group_rows = jl_group_rows(n, jl_shape_rows(shape.t0));
-  // two levels and at most 32768 partitions: both histograms from one read of the keys (wgcnt scratch: the level-1
-  // output region, written only later by the level-1 scatter)
-  // (8192..32768 partitions = 2^24..2^26 rows: level below it the two plain histograms are as fast, 2^22 rows: 77 vs 80 us)
-  const bool fused = k2 > 1 && parts >= 8192 && parts <= kJlFusedMaxParts && fused_scratch != nullptr;
-  // 32768 < parts <= 81920 (2^27-row shards and a quarter more): the same with two 16-bit counters per LDS word (jl_hist_fused16_kernel)
-#ifdef DBHIP_JL_NO_FUSED16  // A/B knob: the two plain histograms for these sizes, as in round 2
-  const bool fused16 = false;
-#else
-  const bool fused16 = !fused && k2 > 1 && kJlFusedMaxParts != 0 && parts > kJlFusedMaxParts && parts <= kJlFused16MaxParts &&
-                       fused_scratch != nullptr;
-#endif
-  if (fused16) {
-    const size_t lds = static_cast<size_t>(parts / 2) * sizeof(unsigned);
-    const hipError_t ea = hipFuncSetAttribute(reinterpret_cast<const void *>(jl_hist_fused16_kernel),
-                                              hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds));
-    if (ea != hipSuccess) return static_cast<int>(ea);
-    hipLaunchKernelGGL(jl_hist_fused16_kernel, dim3(kJlGroups * kJlFusedWgPerGroup), dim3(kJlFusedThreads), lds, s, keys, n,
-                       group_rows, parts, log2_k2, k1, fused_scratch, counts0, counts1);
-    const unsigned red_grid = (parts / 2 + 255) / 256 + (kJlGroups * kJlFusedWgPerGroup * k1 + 3) / 4;
-    hipLaunchKernelGGL(jl_hist_reduce16_kernel, dim3(red_grid), dim3(256), 0, s, fused_scratch, parts, k1, k2, counts0, counts1);
-  } else if (fused) {
-    const hipError_t ea = hipFuncSetAttribute(reinterpret_cast<const void *>(jl_hist_fused_kernel),
-                                              hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(parts * sizeof(unsigned)));
-    if (ea != hipSuccess) return static_cast<int>(ea);
-    hipLaunchKernelGGL(jl_hist_fused_kernel, dim3(kJlGroups * kJlFusedWgPerGroup), dim3(kJlFusedThreads),
-                       parts * sizeof(unsigned), s, keys, n, group_rows, parts, fused_scratch);
-    const unsigned red_grid = (parts + 255) / 256 + (kJlGroups * kJlFusedWgPerGroup * k1 + 3) / 4;
-    hipLaunchKernelGGL(jl_hist_reduce_kernel, dim3(red_grid), dim3(256), 0, s, fused_scratch, parts, k1, k2, counts0, counts1);
-  } else {
-    hipLaunchKernelGGL(jl_hist0_kernel<false>, dim3(kJlGroups * kJlHistWgPerGroup), dim3(kJlThreads),
-                       k1 * sizeof(unsigned), s, keys, n, group_rows, parts, k2_shift, k1, counts0);
-  }
-  hipLaunchKernelGGL(jl_offsets0_kernel, dim3(1), dim3(1024), 0, s, counts0, k1, jl_shape_rows(shape.t1), cursors0, starts0,
-                     tstarts0, static_cast<unsigned long long *>(nullptr));
-  // A level-1 histogram of its own (more partitions than the fused ones count: sides of more than 1.47e8 rows): level 0
-  // writes every row's level-1 bucket as a 16-bit column into the level-1 output region — unused until the level-1
-  // scatter writes it, like the fused histograms' scratch — and the histogram reads those 2 bytes per row instead of
-  // the 8-byte pairs: 2^30 x 2^30 26.7-26.8 -> 25.5-25.6 ms, same box (DBHIP_JL_DIGITS=0: the pairs, for A/B runs).
-  // Not below 8192 partitions, where the plain histograms run as well: those sides are a few hundred us as they are.
-  static const bool digits_on = [] { const char *v = getenv("DBHIP_JL_DIGITS"); return !(v && v[0] == '0'); }();
-  const bool digits = digits_on && k2 > 1 && k2 <= 65536 && !fused && !fused16 && parts > kJlFused16MaxParts;
-  {
-    const hipError_t es = jl_launch_scatter0<false>(shape.t0, dev, s, keys, row_ids, 0ull, n, parts, k2_shift, k1, cursors0,
-                                                    reinterpret_cast<unsigned *>(rows_a),
-                                                    digits ? reinterpret_cast<unsigned *>(rows_b) : static_cast<unsigned *>(nullptr), digits);
-    if (es != hipSuccess) return static_cast<int>(es);
-  }
-  *out_pairs = reinterpret_cast<const unsigned *>(rows_a);
-  *out_starts = starts0;
-  if (k2 > 1) {
-    if (digits)
-      hipLaunchKernelGGL(jl_hist1d_kernel, dim3(k1 * kJlHist1WgPerBucket), dim3(kJlThreads), k2 * sizeof(unsigned), s,
-                         reinterpret_cast<const unsigned short *>(rows_b), starts0, k2, counts1);
-    else if (!fused && !fused16)
-      hipLaunchKernelGGL(jl_hist1_kernel, dim3(k1 * kJlHist1WgPerBucket), dim3(kJlThreads), k2 * sizeof(unsigned), s,
-                         rows_a, starts0, parts, k2, counts1);
-    hipLaunchKernelGGL(jl_offsets1_kernel, dim3(k1), dim3(kJlThreads), 0, s, counts1, starts0, k1, k2, starts1,
-                       cursors1);
-    // (one tile per workgroup; a persistent grid with the next tile's rows prefetched — what helps the level-0
-    //  scatter — measured the same here: a workgroup that ends after its stores never waits for them.  Round 3: a
-    //  precomputed {bucket, tile} map in place of the workgroup's binary search over tile_starts — eight dependent
-    //  loads in front of its row loads — measured the same as well (partition of 2^26 rows 610 vs 615 us), and so did
-    //  the tile shapes 512x16 / 512x4 / 1024x4 once more (723 / 661 / 699 us against 610).)
-    const hipError_t e1 = jl_launch_scatter1(shape.t1, s, n, rows_a, starts0, tstarts0, parts, k1, k2, cursors1, rows_b, dev);
-    if (e1 != hipSuccess) return static_cast<int>(e1);
-    *out_pairs = reinterpret_cast<const unsigned *>(rows_b);
-    *out_starts = starts1;
-  }
-  return launch_status();
-}
-
-namespace {
 // the build side of the one-to-many / unique-key joins, laid out by jl_layout(n): fills `out`
 int jl_partition_rows(const unsigned *build_keys, const unsigned *row_ids, size_t n, void *workspace, hipStream_t s,
                       const DeviceInfo &dev, const JlLayout &L, JlPartitioned *out) {
   char *base = static_cast<char *>(workspace);
   const hipError_t e = fill_async(base, 0, kWsHeader, s);
   if (e != hipSuccess) return static_cast<int>(e);
-  out->rids = nullptr;
   out->table = reinterpret_cast<u32x2 *>(base + L.table_off);
   out->status = reinterpret_cast<unsigned *>(base);
-  return jl_partition_side(build_keys, row_ids, n, L.parts, L.k1, L.k2, L.log2_k2,
-                           reinterpret_cast<u32x2 *>(base + L.keys_a_off), reinterpret_cast<u32x2 *>(base + L.keys_b_off),
-                           reinterpret_cast<unsigned long long *>(base + L.meta_off), L.meta_bytes, s, dev, &out->keys,
-                           &out->starts);
+  return jl_partition_side(build_keys, row_ids, n, L, reinterpret_cast<u32x2 *>(base + L.pairs_a_off),
+                           reinterpret_cast<u32x2 *>(base + L.pairs_b_off),
+                           reinterpret_cast<unsigned long long *>(base + L.meta_off), s, dev, &out->pairs, &out->starts);
 }
 
 size_t jl_build_lds_bytes() { return 2 * static_cast<size_t>(kJlSubSlots) * sizeof(unsigned); }
@@ -2155,90 +1187,91 @@ bool jl_no_giants() {  // DBHIP_JL_NO_GIANTS=1: every partition through the per-
   static const bool off = [] { const char *v = getenv("DBHIP_JL_NO_GIANTS"); return v && v[0] == '1'; }();
   return off;
 }
-// Resident workgroups per CU of a persistent kernel, as the runtime computes it from the kernel's REGISTERS as well as
-// its LDS (round 4: the build kernels were launched with four 512-thread workgroups per CU — what their 24 KiB of LDS
-// allow — while their 73-79 VGPRs allow six waves per SIMD, i.e. three: a quarter of the statically dealt partitions
-// belonged to workgroups that only started when the first ones had finished).  `env`: experiment knob, workgroups per CU.
-template <class Kernel>
-unsigned jl_resident_per_cu(Kernel kernel, int threads, size_t lds, const char *env, unsigned fallback) {
-  const char *e = getenv(env);
-  const int forced = e ? atoi(e) : 0;
-  if (forced >= 1 && forced <= 32) return static_cast<unsigned>(forced);
-  int blocks = 0;
-  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&blocks, kernel, threads, lds) != hipSuccess || blocks < 1) {
-    (void)hipGetLastError();
-    return fallback;
-  }
-  return static_cast<unsigned>(blocks);
-}
+
+// The launches behind the partition step, for the one-to-many build (kMatch = false: sub-tables published to `table`)
+// and the radix join's fused build + probe (kMatch = true): the build kernel over every partition by ticket, then — from
+// the size where giant partitions are looked for (max_giants != 0, join_common.hpp) — jl_giant_count / jl_giant_ids,
+// which all workgroups share and whose tail builds the spilled partitions the build kernel listed; below that size the
+// build kernel's workgroup builds a spilled partition itself, at once.  `pairs`, `starts`: the partitioned build side.
 template <bool kMatch>
-unsigned jl_build_grid(unsigned parts, const DeviceInfo &dev) {
-  static const unsigned per_cu = jl_resident_per_cu(jl_build_kernel<kMatch, false>, kJlBuildThreads, jl_build_lds_bytes(),
-                                                    kMatch ? "DBHIP_JL_MATCH_WGS" : "DBHIP_JL_BUILD_WGS", 3u);
-  const size_t cap = static_cast<size_t>(dev.cus) * per_cu;
-  return static_cast<unsigned>(parts < cap ? parts : cap);
+int jl_launch_build(const unsigned *pairs, const unsigned long long *starts, u32x2 *table, unsigned parts, size_t n_build,
+                    size_t n_probe, unsigned max_giants, void *giant_area, void *spill_area, unsigned *ids, unsigned *status,
+                    const JlMatchArgs &match, hipStream_t s, const DeviceInfo &dev) {
+  const size_t build_lds = jl_build_lds_bytes();
+  const void *listing = reinterpret_cast<const void *>(jl_build_kernel<kMatch, false>);
+  const void *inlined = reinterpret_cast<const void *>(jl_build_kernel<kMatch, true>);
+  hipError_t e = hipFuncSetAttribute(listing, hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(build_lds));
+  if (e == hipSuccess && (kMatch || !max_giants))
+    e = hipFuncSetAttribute(inlined, hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(build_lds));
+  if (e != hipSuccess) return static_cast<int>(e);
+  // giant partitions — radix join: a giant build OR probe side — are left out by the build kernel, listed, then counted
+  // and filled (radix join: into scratch sub-tables, and probed) by the two launches of their own
+  JlGiants giants{nullptr, 0u, ~0ull, ~0ull, 0u};
+  if (max_giants && !jl_no_giants()) {
+    giants.base = static_cast<unsigned *>(giant_area);
+    giants.max = max_giants;
+    giants.rows = jl_giant_rows(n_build);
+    if (kMatch) giants.probe_rows = jl_giant_rows(n_probe);
+    giants.with_tables = kMatch ? 1u : 0u;
+    e = fill_async(giants.base, 0, jl_giant_header_bytes(max_giants), s);
+    if (e != hipSuccess) return static_cast<int>(e);
+  }
+  if (kMatch) {
+    // the spilled-partition list and the pool cursor belong to this match, not to the partitioned sides: a second match
+    // on the same sides would list every spilled partition again (two workgroups building one table) and allocate on
+    // from the pool.  (The spill directory needs no clear: the build kernel writes every partition's entry.)
+    static_assert(kJlHdrSpillPool == kJlHdrSpilled + 1, "header words 34 and 35 are cleared together");
+    e = fill_async(status + kJlHdrSpilled, 0, 2 * sizeof(unsigned), s);
+    if (e != hipSuccess) return static_cast<int>(e);
+  }
+  const JlSpill spill = jl_spill_of(spill_area, parts, n_build);
+  const unsigned pos_bits = jl_pos_bits(n_build);
+  const unsigned *no_rids = nullptr;  // (the kernels' row-id column parameter: both scatter levels write pairs)
+  // as many workgroups as are RESIDENT (DBHIP_JL_BUILD_WGS / DBHIP_JL_MATCH_WGS: experiments)
+  const size_t cap = static_cast<size_t>(dev.cus) * jl_resident_per_cu(listing, kJlBuildThreads, build_lds,
+                                                                       kMatch ? "DBHIP_JL_MATCH_WGS" : "DBHIP_JL_BUILD_WGS", 3u);
+  const unsigned build_grid = static_cast<unsigned>(parts < cap ? parts : cap);
+  if (max_giants) {
+    hipLaunchKernelGGL((jl_build_kernel<kMatch, false>), dim3(build_grid), dim3(kJlBuildThreads), build_lds, s, pairs, no_rids,
+                       starts, table, parts, static_cast<unsigned>(n_build), pos_bits, ids, status, match, giants, spill.area);
+    const unsigned grid = static_cast<unsigned>(dev.cus) * (2048 / kJlGiantThreads);
+    if (giants.max)
+      hipLaunchKernelGGL(jl_giant_count_kernel, dim3(grid), dim3(kJlGiantThreads), 0, s, reinterpret_cast<const u32x2 *>(pairs),
+                         starts, table, pos_bits, giants, status, spill);
+    hipLaunchKernelGGL(jl_giant_ids_kernel, dim3(grid), dim3(kJlGiantThreads), 0, s, reinterpret_cast<const u32x2 *>(pairs),
+                       starts, table, giants, ids, status, match, pos_bits, spill);
+  } else {
+    hipLaunchKernelGGL((jl_build_kernel<kMatch, true>), dim3(build_grid), dim3(kJlBuildThreads), build_lds, s, pairs, no_rids,
+                       starts, table, parts, static_cast<unsigned>(n_build), pos_bits, ids, status, match, giants, spill.area);
+  }
+  return launch_status();
 }
 }  // namespace
 
-// ---- host side (called from join.hip's entry points) ---------------------------------------------------
 int join_lds_build(const unsigned *build_keys, const unsigned *row_ids, size_t n, unsigned *ids, void *workspace,
                    hipStream_t s, const DeviceInfo &dev) {
   const JlLayout L = jl_layout(n);
   JlPartitioned p;
   const int rc = jl_partition_rows(build_keys, row_ids, n, workspace, s, dev, L, &p);
   if (rc != 0) return rc;
-  const size_t build_lds = jl_build_lds_bytes();
-  const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(jl_build_kernel<false, false>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(build_lds));
-  if (e != hipSuccess) return static_cast<int>(e);
-  // giant partitions (join_common.hpp): listed by the build kernel, counted and filled by two launches of their own
-  JlGiants giants{nullptr, 0u, ~0ull, ~0ull, 0u};
-  if (L.max_giants && !jl_no_giants()) {
-    giants.base = reinterpret_cast<unsigned *>(static_cast<char *>(workspace) + L.giant_off);
-    giants.max = L.max_giants;
-    giants.rows = jl_giant_rows(n);
-    const hipError_t eg = fill_async(giants.base, 0, jl_giant_header_bytes(L.max_giants), s);
-    if (eg != hipSuccess) return static_cast<int>(eg);
-  }
-  // spilled partitions (more distinct keys than a sub-table has slots): from the size where the giants' launches exist
-  // they are listed and built at the end of jl_giant_ids_kernel; below it the build kernel's workgroup does it at once
-  const JlSpill spill = jl_spill_of(static_cast<char *>(workspace) + L.spill_off, L.parts, n);
+  char *base = static_cast<char *>(workspace);
   const JlMatchArgs no_match{nullptr, nullptr, nullptr, nullptr, nullptr};
-  if (L.max_giants) {
-    hipLaunchKernelGGL((jl_build_kernel<false, false>), dim3(jl_build_grid<false>(L.parts, dev)), dim3(kJlBuildThreads), build_lds, s,
-                       p.keys, p.rids, p.starts, p.table, L.parts, static_cast<unsigned>(n), jl_pos_bits(n), ids, p.status,
-                       no_match, giants, spill.area);
-    const unsigned grid = static_cast<unsigned>(dev.cus) * (2048 / kJlGiantThreads);
-    if (giants.max)
-      hipLaunchKernelGGL(jl_giant_count_kernel, dim3(grid), dim3(kJlGiantThreads), 0, s, reinterpret_cast<const u32x2 *>(p.keys),
-                         p.starts, p.table, jl_pos_bits(n), giants, p.status, spill);
-    hipLaunchKernelGGL(jl_giant_ids_kernel, dim3(grid), dim3(kJlGiantThreads), 0, s, reinterpret_cast<const u32x2 *>(p.keys),
-                       p.starts, p.table, giants, ids, p.status, no_match, jl_pos_bits(n), spill);
-  } else {
-    const hipError_t e2 = hipFuncSetAttribute(reinterpret_cast<const void *>(jl_build_kernel<false, true>),
-                                              hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(build_lds));
-    if (e2 != hipSuccess) return static_cast<int>(e2);
-    hipLaunchKernelGGL((jl_build_kernel<false, true>), dim3(jl_build_grid<false>(L.parts, dev)), dim3(kJlBuildThreads), build_lds, s,
-                       p.keys, p.rids, p.starts, p.table, L.parts, static_cast<unsigned>(n), jl_pos_bits(n), ids, p.status,
-                       no_match, giants, spill.area);
-  }
-  return launch_status();
+  return jl_launch_build<false>(p.pairs, p.starts, p.table, L.parts, n, 0, L.max_giants, base + L.giant_off, base + L.spill_off,
+                                ids, p.status, no_match, s, dev);
 }
 
 // ---- radix join: both sides partitioned with the build side's geometry, one fused build + probe launch -----------
 // workspace: header | build side: pairs a, pairs b, meta | probe side: pairs a, pairs b, meta
 namespace {
-struct JrLayout {
-  unsigned parts, k1, k2, log2_k2, max_giants;
-  size_t meta_bytes, b_a, b_b, b_meta, p_a, p_b, p_meta, giant_off, spill_off, total;
+struct JrLayout : JlGeometry {
+  unsigned max_giants;
+  size_t b_a, b_b, b_meta, p_a, p_b, p_meta, giant_off, spill_off, total;
 };
 JrLayout jr_layout(size_t n_build, size_t n_probe) {
-  const JlLayout G = jl_layout(n_build, kJrRowsPerPart);
   JrLayout L;
-  L.parts = G.parts; L.k1 = G.k1; L.k2 = G.k2; L.log2_k2 = G.log2_k2;
-  L.meta_bytes = G.meta_bytes;
+  static_cast<JlGeometry &>(L) = jl_geometry(n_build, kJrRowsPerPart);
   const size_t cb = align_up((n_build ? n_build : 1) * 8, kWsAlign), cp = align_up((n_probe ? n_probe : 1) * 8, kWsAlign);
-  const size_t mb = align_up(L.meta_bytes, kWsAlign);
+  const size_t mb = align_up(jl_meta(L).bytes(), kWsAlign);
   L.b_a = kWsHeader;
   L.b_b = L.b_a + cb;
   L.b_meta = L.b_b + (L.k2 > 1 ? cb : 0);
@@ -2254,11 +1287,8 @@ JrLayout jr_layout(size_t n_build, size_t n_probe) {
 // where a partitioned side ended up is a pure function of the sizes: no state is kept between the calls
 void jr_side(const JrLayout &L, char *base, bool probe, const unsigned **pairs, const unsigned long long **starts) {
   const size_t a = probe ? L.p_a : L.b_a, b = probe ? L.p_b : L.b_b, m = probe ? L.p_meta : L.b_meta;
-  unsigned long long *meta = reinterpret_cast<unsigned long long *>(base + m);
-  unsigned long long *starts0 = meta + 2 * static_cast<size_t>(kJlGroups) * L.k1;
-  unsigned long long *starts1 = starts0 + 2 * (static_cast<size_t>(L.k1) + 1) + L.parts;
   *pairs = reinterpret_cast<const unsigned *>(base + (L.k2 > 1 ? b : a));
-  *starts = L.k2 > 1 ? starts1 : starts0;
+  *starts = reinterpret_cast<const unsigned long long *>(base + m) + jl_meta_starts(L);
 }
 }  // namespace
 
@@ -2278,11 +1308,10 @@ int join_radix_partition(int probe_side, const unsigned *keys, const unsigned *r
   }
   const unsigned *pairs;
   const unsigned long long *starts;
-  return jl_partition_side(keys, row_ids, n, L.parts, L.k1, L.k2, L.log2_k2,
-                           reinterpret_cast<u32x2 *>(base + (probe_side ? L.p_a : L.b_a)),
+  return jl_partition_side(keys, row_ids, n, L, reinterpret_cast<u32x2 *>(base + (probe_side ? L.p_a : L.b_a)),
                            reinterpret_cast<u32x2 *>(base + (probe_side ? L.p_b : L.b_b)),
-                           reinterpret_cast<unsigned long long *>(base + (probe_side ? L.p_meta : L.b_meta)), L.meta_bytes, s,
-                           dev, &pairs, &starts);
+                           reinterpret_cast<unsigned long long *>(base + (probe_side ? L.p_meta : L.b_meta)), s, dev, &pairs,
+                           &starts);
 }
 
 int join_radix_match(size_t n_build, size_t n_probe, unsigned *ids, unsigned *out_rid, unsigned *out_pos, unsigned *out_cnt,
@@ -2293,50 +1322,10 @@ int join_radix_match(size_t n_build, size_t n_probe, unsigned *ids, unsigned *ou
   const unsigned long long *bs, *ps;
   jr_side(L, base, false, &bp, &bs);
   jr_side(L, base, true, &pp, &ps);
-  const size_t build_lds = jl_build_lds_bytes();
-  hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(jl_build_kernel<true, false>),
-                                     hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(build_lds));
-  if (e == hipSuccess)
-    e = hipFuncSetAttribute(reinterpret_cast<const void *>(jl_build_kernel<true, true>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                            static_cast<int>(build_lds));
-  if (e != hipSuccess) return static_cast<int>(e);
-  // partitions with a giant build OR probe side (join_common.hpp): left out by the fused kernel, listed, then built into
-  // scratch sub-tables (jl_giant_count / jl_giant_ids) and probed (second half of jl_giant_ids) by all workgroups together
-  JlGiants giants{nullptr, 0u, ~0ull, ~0ull, 0u};
-  if (L.max_giants && !jl_no_giants()) {
-    giants.base = reinterpret_cast<unsigned *>(base + L.giant_off);
-    giants.max = L.max_giants;
-    giants.rows = jl_giant_rows(n_build);
-    giants.probe_rows = jl_giant_rows(n_probe);
-    giants.with_tables = 1u;
-    const hipError_t eg = fill_async(giants.base, 0, jl_giant_header_bytes(L.max_giants), s);
-    if (eg != hipSuccess) return static_cast<int>(eg);
-  }
   const JlMatchArgs match{reinterpret_cast<const u32x2 *>(pp), ps, out_rid, out_pos, out_cnt};
-  unsigned *status = reinterpret_cast<unsigned *>(base);
-  // the spilled-partition list and the pool cursor belong to this match, not to the partitioned sides: a second match
-  // on the same sides would list every spilled partition again (two workgroups building one table) and allocate on
-  // from the pool.  (The spill directory needs no clear: the build kernel writes every partition's entry.)
-  static_assert(kJlHdrSpillPool == kJlHdrSpilled + 1, "header words 34 and 35 are cleared together");
-  e = fill_async(status + kJlHdrSpilled, 0, 2 * sizeof(unsigned), s);
-  if (e != hipSuccess) return static_cast<int>(e);
-  const JlSpill spill = jl_spill_of(base + L.spill_off, L.parts, n_build);
-  if (L.max_giants) {
-    hipLaunchKernelGGL((jl_build_kernel<true, false>), dim3(jl_build_grid<true>(L.parts, dev)), dim3(kJlBuildThreads), build_lds, s, bp,
-                       static_cast<const unsigned *>(nullptr), bs, static_cast<u32x2 *>(nullptr), L.parts,
-                       static_cast<unsigned>(n_build), jl_pos_bits(n_build), ids, status, match, giants, spill.area);
-    const unsigned grid = static_cast<unsigned>(dev.cus) * (2048 / kJlGiantThreads);
-    if (giants.max)
-      hipLaunchKernelGGL(jl_giant_count_kernel, dim3(grid), dim3(kJlGiantThreads), 0, s, reinterpret_cast<const u32x2 *>(bp), bs,
-                         static_cast<u32x2 *>(nullptr), jl_pos_bits(n_build), giants, status, spill);
-    hipLaunchKernelGGL(jl_giant_ids_kernel, dim3(grid), dim3(kJlGiantThreads), 0, s, reinterpret_cast<const u32x2 *>(bp), bs,
-                       static_cast<u32x2 *>(nullptr), giants, ids, status, match, jl_pos_bits(n_build), spill);
-  } else {
-    hipLaunchKernelGGL((jl_build_kernel<true, true>), dim3(jl_build_grid<true>(L.parts, dev)), dim3(kJlBuildThreads), build_lds, s, bp,
-                       static_cast<const unsigned *>(nullptr), bs, static_cast<u32x2 *>(nullptr), L.parts,
-                       static_cast<unsigned>(n_build), jl_pos_bits(n_build), ids, status, match, giants, spill.area);
-  }
-  return launch_status();
+  // (no table is published: the giants' sub-tables live in their scratch)
+  return jl_launch_build<true>(bp, bs, static_cast<u32x2 *>(nullptr), L.parts, n_build, n_probe, L.max_giants, base + L.giant_off,
+                               base + L.spill_off, ids, reinterpret_cast<unsigned *>(base), match, s, dev);
 }
 
 // unique-key payload join: `build_vals` ride through the partition in the row-id column
@@ -2346,8 +1335,8 @@ int ujoin_lds_build(const unsigned *build_keys, const unsigned *build_vals, size
   JlPartitioned p;
   const int rc = jl_partition_rows(build_keys, build_vals, n, workspace, s, dev, L, &p);
   if (rc != 0) return rc;
-  hipLaunchKernelGGL(jl_ubuild_kernel, dim3(L.parts), dim3(kJlBuildThreads), 0, s, p.keys, p.rids, p.starts, p.table,
-                     p.status, jl_spill_of(static_cast<char *>(workspace) + L.spill_off, L.parts, n));
+  hipLaunchKernelGGL(jl_ubuild_kernel, dim3(L.parts), dim3(kJlBuildThreads), 0, s, p.pairs, static_cast<const unsigned *>(nullptr),
+                     p.starts, p.table, p.status, jl_spill_of(static_cast<char *>(workspace) + L.spill_off, L.parts, n));
   return launch_status();
 }
 
@@ -2356,7 +1345,8 @@ int ujoin_lds_probe(const unsigned *probe_keys, const unsigned *probe_vals, size
                     const DeviceInfo &dev) {
   const JlLayout L = jl_layout(n_build);
   const u32x2 *table = reinterpret_cast<const u32x2 *>(static_cast<const char *>(workspace) + L.table_off);
-  static const int uprobe_wgs = static_cast<int>(jl_resident_per_cu(jl_uprobe_kernel, kJlThreads, 0, "DBHIP_JL_UPROBE_WGS", 4u));
+  const int uprobe_wgs = static_cast<int>(jl_resident_per_cu(reinterpret_cast<const void *>(jl_uprobe_kernel), kJlThreads, 0,
+                                                             "DBHIP_JL_UPROBE_WGS", 4u));
   hipLaunchKernelGGL(jl_uprobe_kernel, dim3(jl_grid(n_probe, dev, uprobe_wgs)), dim3(kJlThreads), 0, s, probe_keys, probe_vals,
                      n_probe, table, L.parts, out_key, out_bval, out_pval,
                      jl_spill_of(const_cast<char *>(static_cast<const char *>(workspace)) + L.spill_off, L.parts, n_build));
@@ -2371,68 +1361,11 @@ int join_lds_probe(const unsigned *probe_keys, size_t n_probe, const void *works
   // eight per CU — two rounds of workgroups — the kernel's time depended on how the second round happened to fill in
   // (round 4, same box, 2^26 rows: 2 per CU 1767-1838 us, 4: 1553-1572, 6: 1692-1713, 8: 1566 for one build of this
   // kernel and 1708 for another whose loop was the same instructions; 16: 1566 / 1625).  DBHIP_JL_PROBE_WGS: experiments.
-  static const int wgs_per_cu = static_cast<int>(jl_resident_per_cu(jl_probe_kernel, kJlThreads, 0, "DBHIP_JL_PROBE_WGS", 4u));
+  const int wgs_per_cu = static_cast<int>(jl_resident_per_cu(reinterpret_cast<const void *>(jl_probe_kernel), kJlThreads, 0,
+                                                             "DBHIP_JL_PROBE_WGS", 4u));
   char *ws = const_cast<char *>(static_cast<const char *>(workspace));
   hipLaunchKernelGGL(jl_probe_kernel, dim3(jl_grid(n_probe, dev, wgs_per_cu)), dim3(kJlThreads), 0, s, probe_keys, n_probe,
                      table, L.parts, jl_pos_bits(n_build), out_pos, out_cnt, jl_spill_of(ws + L.spill_off, L.parts, n_build));
-  return launch_status();
-}
-
-// how many of `keys` do NOT belong to bucket `rank` of `parts` under the rank hash (validator of the exchange's routing)
-__global__ __launch_bounds__(kJlThreads) void jl_route_check_kernel(const unsigned *__restrict__ keys, size_t n,
-                                                                    unsigned parts, unsigned rank,
-                                                                    unsigned long long *result) {
-  __shared__ unsigned s_bad;
-  if (threadIdx.x == 0) s_bad = 0;
-  __syncthreads();
-  const size_t stride = static_cast<size_t>(gridDim.x) * kJlThreads;
-  unsigned bad = 0;
-  for (size_t i = static_cast<size_t>(blockIdx.x) * kJlThreads + threadIdx.x; i < n; i += stride)
-    bad += jl_rank_of(keys[i], parts) != rank;
-  bad = wave_reduce_add(bad);
-  if ((threadIdx.x & (kWave - 1)) == kWave - 1 && bad) atomicAdd(&s_bad, bad);
-  __syncthreads();
-  if (threadIdx.x == 0 && s_bad) atomicAdd(result, static_cast<unsigned long long>(s_bad));
-}
-
-int jl_route_check(const unsigned *keys, size_t n, unsigned parts, unsigned rank, unsigned long long *result,
-                   hipStream_t s, const DeviceInfo &dev) {
-  const hipError_t e = fill_async(result, 0, sizeof(unsigned long long), s);
-  if (e != hipSuccess) return static_cast<int>(e);
-  if (n == 0) return DBHIP_OK;
-  hipLaunchKernelGGL(jl_route_check_kernel, dim3(jl_grid(n, dev, 8)), dim3(kJlThreads), 0, s, keys, n, parts, rank, result);
-  return launch_status();
-}
-
-// ---- stand-alone level-0 partition (multi-GPU join: bucket = destination rank) ------------------------
-// 2^27 rows into 8 buckets: histogram 158 us + scatter 566 us (into 2 buckets: 285 + 700 us — the LDS atomics of a
-// wave land on very few addresses).  Counting and ranking by ballot in wave-uniform registers instead (16 unrolled
-// bucket tests per key) was measured at 324 + 794 us and dropped.
-size_t jl_partition_workspace_bytes(unsigned parts) {
-  return align_up(kWsHeader + sizeof(unsigned long long) * ((2 * static_cast<size_t>(kJlGroups) + 2) * parts + 2),
-                  kWsAlign);
-}
-
-int jl_partition(const unsigned *keys, size_t n, unsigned long long first_row, unsigned parts, unsigned *out_keys,
-                 unsigned *out_rids, unsigned long long *out_counts, void *workspace, hipStream_t s,
-                 const DeviceInfo &dev) {
-  char *base = static_cast<char *>(workspace);
-  unsigned long long *meta = reinterpret_cast<unsigned long long *>(base + kWsHeader);
-  unsigned long long *counts0 = meta;
-  unsigned long long *cursors0 = counts0 + static_cast<size_t>(kJlGroups) * parts;
-  unsigned long long *starts0 = cursors0 + static_cast<size_t>(kJlGroups) * parts;
-  unsigned long long *tstarts0 = starts0 + parts + 1;
-  hipError_t e = fill_async(base, 0, jl_partition_workspace_bytes(parts), s);
-  if (e != hipSuccess) return static_cast<int>(e);
-  hipLaunchKernelGGL(jl_hist0_kernel<true>, dim3(kJlGroups * kJlHistWgPerGroup), dim3(kJlThreads),
-                     parts * sizeof(unsigned), s, keys, n, jl_group_rows(n, kJlTile), parts, 0u, parts, counts0);
-  hipLaunchKernelGGL(jl_offsets0_kernel, dim3(1), dim3(1024), 0, s, counts0, parts, static_cast<unsigned>(kJlTile), cursors0,
-                     starts0, tstarts0, out_counts);
-  if (n) {
-    e = jl_launch_scatter0<true>(0, dev, s, keys, static_cast<const unsigned *>(nullptr), first_row, n, parts, 0u, parts,
-                                 cursors0, out_keys, out_rids);
-    if (e != hipSuccess) return static_cast<int>(e);
-  }
   return launch_status();
 }
 

@@ -5,9 +5,9 @@
 //   dbhip_pjoin_partition_u32   splits a local column shard into `parts` destination buckets by
 //                               fmix32(key * 0x9E3779B1 + c) (Murmur3 finaliser of an affine image of the key,
 //                               multiply-shift range reduction, so any part count balances) — a hash
-//                               independent of the one the local join partitions by (jl_rank_of, join_lds.hip)
+//                               independent of the one the local join partitions by (jl_rank_of, partition.hpp)
 //                               — and tags every key with its GLOBAL row id.  It is the level-0 partition of the LDS join
-//                               (join_lds.hip: per-group histogram, bucket/group cursors, LDS-staged
+//                               (partition.hip: per-group histogram, bucket/group cursors, LDS-staged
 //                               scatter that writes runs) with bucket = destination rank.  Order
 //                               inside a bucket is not defined (the join does not need it).
 //   dbhip_gather_u32            out[i] = table[idx[i]].

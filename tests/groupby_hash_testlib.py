@@ -1,9 +1,10 @@
-"""Test-only helpers for the hash group-by (dbhip_groupby_hash_u32, csrc/groupby_hash.hip): its hashes and the radix
-partition geometry restated in numpy, inputs constructed against them (one named case per branch of the kernel file),
-and exact references.  Numpy only: the CPU tests check the constructions, the GPU tests run them.  Never imported by
-the product."""
+"""Test-only helpers for the hash group-by (dbhip_groupby_hash_u32, csrc/groupby_hash.hip): its hashes restated in
+numpy (the radix partition geometry is join_testlib's restatement), inputs constructed against them (one named case per
+branch of the kernel file), and exact references.  Numpy only: the CPU tests check the constructions, the GPU tests run
+them.  Never imported by the product."""
 import numpy as np
 
+from tests import join_testlib as jt
 from tests.pjoin_testlib import fmix32
 
 M32 = 0xFFFFFFFF
@@ -16,9 +17,6 @@ LDS_MAX_GROUPS = 4096              # kGbhLdsMaxGroups: path a up to this bound
 PROBE = 64                         # kGbhProbe: LDS steps before a row goes to the global table
 CROWD = 16                         # kGbhCrowd: lanes of a wave on one key that are summed before the add
 GIANT_ROWS = 32768                 # kGbhGiantRows: a partition above this is sliced
-ROWS_PER_PART = 2048               # join_common.hpp kJlRowsPerPart
-FUSED_MAX_PARTS = 32768            # join_lds.hip DBHIP_JL_FUSED_MAX_PARTS
-FUSED16_MAX_PARTS = 80 * 1024      # join_lds.hip kJlFused16MaxParts
 WS_ALIGN = WS_HEADER = 256         # dbhip_common.hpp kWsAlign, kWsHeader
 
 
@@ -39,7 +37,7 @@ def _mixed(keys):
 
 
 def pid(keys, parts):
-    """partition of each key: join_lds.hip jl_pid, (fmix32(key) * parts) >> 32"""
+    """partition of each key: partition.hpp jl_pid, (fmix32(key) * parts) >> 32"""
     return ((fmix32(np.asarray(keys, dtype=np.uint32)) * np.uint64(parts)) >> np.uint64(32)).astype(np.int64)
 
 
@@ -59,35 +57,14 @@ def global_home(keys, slots):
 
 
 def part_layout(n):
-    """(parts, k1, k2) of path b's partition step: join_common.hpp jl_layout(n) with kJlRowsPerPart rows per partition"""
-    want = min(max(1, -(-n // ROWS_PER_PART)), 1 << 20)
-    lg = (want - 1).bit_length()
-    if want <= 1024:
-        log2_k2 = 0
-    else:
-        lgs = lg - 1 if (1 << lg) != want else lg
-        log2_k2 = lgs // 2
-    k2 = 1 << log2_k2
-    k1 = -(-want // k2)
-    while k1 > 1024:
-        k2 *= 2
-        k1 = -(-want // k2)
-    return k1 * k2, k1, k2
+    """(parts, k1, k2) of path b's partition step: partition.hpp jl_geometry(n) with kJlRowsPerPart rows per partition"""
+    return jt.layout(n, jt.JL_ROWS_PER_PART)
 
 
 def hist_variant(n, digits=True):
-    """which histogram jl_partition_side (join_lds.hip) runs for path b at n rows: 'one level', 'plain', 'fused',
+    """which histogram jl_partition_side (partition.hip) runs for path b at n rows: 'one level', 'plain', 'fused',
     'fused16' or 'digits' (the 16-bit digit column; DBHIP_JL_DIGITS=0 turns it back into 'plain')"""
-    parts, _, k2 = part_layout(n)
-    if k2 == 1:
-        return "one level"
-    if 8192 <= parts <= FUSED_MAX_PARTS:
-        return "fused"
-    if FUSED_MAX_PARTS < parts <= FUSED16_MAX_PARTS:
-        return "fused16"
-    if digits and parts > FUSED16_MAX_PARTS and k2 <= 65536:
-        return "digits"
-    return "plain"
+    return jt.side_plan(n, n, jt.JL_ROWS_PER_PART, digits=digits)[3]
 
 
 def workspace_bytes(n, max_groups):

@@ -1,8 +1,8 @@
 """Test-only helpers for the one-to-many joins (ops.HashJoin, ops.RadixJoin): keys constructed against the partition
-hash of join_lds.hip, the partition counts of join_common.hpp restated, and the checks every join test applies.
-Never imported by the product."""
+hash of partition.hpp, its geometry and side plan restated (the one restatement under tests/: the group-by's helpers
+call it), and the checks every join test applies.  torch is imported where a helper needs it, so the numpy-only
+helpers can use the restatement.  Never imported by the product."""
 import numpy as np
-import torch
 
 from oracle import pyoracle as po
 from tests.pjoin_testlib import fmix32
@@ -10,11 +10,12 @@ from tests.pjoin_testlib import fmix32
 
 def dev(a):
     """uint32 numpy column -> int32 tensor on the GPU (same bits)"""
+    import torch
     return torch.from_numpy(np.ascontiguousarray(a, dtype=np.uint32).view(np.int32)).cuda()
 
 
 def keys_of_partition_of(parts, partition, how_many):
-    """the first `how_many` keys >= 1 that the partition hash (join_lds.hip jl_pid: the high bits of fmix32(key) * parts)
+    """the first `how_many` keys >= 1 that the partition hash (partition.hpp jl_pid: the high bits of fmix32(key) * parts)
     puts into `partition` of `parts`"""
     cand = np.arange(1, 1 + how_many * parts * 2, dtype=np.uint64)
     mine = cand[(fmix32(cand) * np.uint64(parts)) >> np.uint64(32) == partition][:how_many]
@@ -22,15 +23,15 @@ def keys_of_partition_of(parts, partition, how_many):
     return mine.astype(np.uint32)
 
 
-JL_ROWS_PER_PART = 2048  # join_common.hpp kJlRowsPerPart: the hash and unique joins (and the group-by's path b)
+JL_ROWS_PER_PART = 2048  # join_common.hpp kJlRowsPerPart: the hash and unique joins and the group-by's path b
 JR_ROWS_PER_PART = 1792  # kJrRowsPerPart: the radix join
-FUSED_MAX_PARTS = 32768  # join_lds.hip kJlFusedMaxParts
+FUSED_MAX_PARTS = 32768  # partition.hpp kJlFusedMaxParts
 FUSED16_MAX_PARTS = 80 * 1024  # kJlFused16MaxParts
 HIST_ROWS = 64 * 4  # kJlGroups x kJlFusedWgPerGroup: the rows of the fused histograms' scratch
 
 
 def layout(n_build, rows_per_part):
-    """(parts, k1, k2) of join_common.hpp jl_layout(n_build, rows_per_part) with DBHIP_JL_K2_BIAS = 0"""
+    """(parts, k1, k2) of partition.hpp jl_geometry(n_build, rows_per_part) with DBHIP_JL_K2_BIAS = 0"""
     want = min(max(1, -(-int(n_build) // rows_per_part)), 1 << 20)
     lg = (want - 1).bit_length()  # ceil(log2(want))
     if want <= 1024:
@@ -46,7 +47,7 @@ def layout(n_build, rows_per_part):
 
 
 def shape_for(k1, k2, t0=None, t1=None):
-    """join_lds.hip jl_shape_for: the tile shape ids (t0, t1) of the two scatter levels, DBHIP_JL_T0 / DBHIP_JL_T1 forced
+    """the tile shapes of partition.hpp jl_side_plan: the shape ids (t0, t1) of the two scatter levels, DBHIP_JL_T0 / DBHIP_JL_T1 forced
     when given (t1 = 2 reads as 1)"""
     s0 = 2 if k1 >= 512 else 0
     s1 = 1 if k2 >= 512 else 0
@@ -58,7 +59,7 @@ def shape_for(k1, k2, t0=None, t1=None):
 
 
 def side_plan(n_side, n_build, rows_per_part, t0=None, t1=None, digits=True):
-    """what join_lds.hip jl_partition_side does with a column of n_side rows laid out by the geometry of n_build rows
+    """partition.hpp jl_side_plan: what jl_partition_side does with a column of n_side rows laid out by the geometry of n_build rows
     (the radix join partitions its probe side with the build side's): -> (parts, k1, k2, variant, t0, t1).  variant is
     the histogram it runs — 'one level', 'plain', 'fused', 'fused16' or 'digits' — including the fused histograms' need
     for scratch: 256 rows of `parts` counters in the level-1 output region of 8 * n_side bytes, i.e. n_side >= 128 *
@@ -100,6 +101,7 @@ GUARD_WORDS = 16
 def guarded(n, offset_words, fill, device="cuda"):
     """-> (base, view): an int32 column of n words that starts `offset_words` 4-byte words after a 16-byte boundary, in
     a fresh allocation (torch's: 512-byte aligned) whose other words — at least GUARD_WORDS on each side — hold `fill`"""
+    import torch
     base = torch.full((GUARD_WORDS + offset_words + n + GUARD_WORDS,), fill, dtype=torch.int32, device=device)
     assert base.data_ptr() % 16 == 0
     view = base[GUARD_WORDS + offset_words: GUARD_WORDS + offset_words + n]
@@ -112,7 +114,7 @@ def assert_guards(base, view, fill):
     at = (view.data_ptr() - base.data_ptr()) // 4
     assert at >= GUARD_WORDS and base.numel() - at - view.numel() >= GUARD_WORDS
     for part, where in ((base[:at], "in front of"), (base[at + view.numel():], "behind")):
-        bad = torch.nonzero(part != fill)
+        bad = (part != fill).nonzero()
         assert bad.numel() == 0, f"{bad.numel()} guard words {where} the column overwritten"
 
 

@@ -17,7 +17,7 @@ def fmix32(k: np.ndarray) -> np.ndarray:
 
 
 def dest_of(keys: np.ndarray, parts: int) -> np.ndarray:
-    """(fmix32(key * 0x9E3779B1 + 0x7F4A7C15) * parts) >> 32, as jl_rank_of in csrc/join_lds.hip: a hash independent
+    """(fmix32(key * 0x9E3779B1 + 0x7F4A7C15) * parts) >> 32, as jl_rank_of in csrc/partition.hpp: a hash independent
     of the one the local join partitions by"""
     pre = (keys.astype(np.uint64) * np.uint64(0x9E3779B1) + np.uint64(0x7F4A7C15)) & np.uint64(0xFFFFFFFF)
     return ((fmix32(pre) * np.uint64(parts)) >> np.uint64(32)).astype(np.int64)

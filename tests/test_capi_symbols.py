@@ -41,6 +41,39 @@ def test_workspace_queries_need_no_gpu():
     assert lib.dbhip_ujoin_workspace_bytes(1000) >= 2 * 2048 * 4
 
 
+WORKSPACE_SIZES = (0, 1, 2048, 2049, 65535, 65536, (1 << 18) - 1, 1 << 18, 1 << 21, (1 << 21) + 1, (1 << 24) + 5, 1 << 26,
+                   (1 << 26) + 1, 81920 * 2048, 81920 * 2048 + 1, 1 << 30, 1 << 31)
+
+
+def _workspace_table(lib):
+    """every workspace query whose answer depends on the partitioner's geometry or meta array, at the row counts where
+    the code changes branch: one or two scatter levels, giants on or off, each histogram variant, the row limit"""
+    table = {}
+    for n in WORKSPACE_SIZES:
+        row = {"join": lib.dbhip_join_workspace_bytes(n), "ujoin": lib.dbhip_ujoin_workspace_bytes(n),
+               "radix n x n": lib.dbhip_join_radix_workspace_bytes(n, n),
+               "radix n x n/3+1": lib.dbhip_join_radix_workspace_bytes(n, n // 3 + 1),
+               "groupby_hash any": lib.dbhip_groupby_hash_workspace_bytes(n, 0),
+               "groupby_hash 4096": lib.dbhip_groupby_hash_workspace_bytes(n, 4096)}
+        for parts in (1, 8, 1024):  # 1024: pjoin.hip kPjMaxParts, the largest allowed
+            row[f"pjoin_partition {parts}"] = lib.dbhip_pjoin_partition_workspace_bytes(n, parts)
+        table[str(n)] = row
+    return table
+
+
+def test_workspace_sizes_are_those_of_the_undivided_partitioner():
+    """tests/golden/workspace_bytes.json: what the library answered before the partitioner became a unit of its own
+    (csrc/partition.hip, one description of its meta array) — recorded from a CPU build of that commit with
+    _workspace_table; a caller's allocation must neither grow nor fall short"""
+    import json
+    want = json.loads((ROOT / "tests" / "golden" / "workspace_bytes.json").read_text())
+    assert sorted(want) == sorted(str(n) for n in WORKSPACE_SIZES)
+    got = _workspace_table(_capi.lib())
+    assert all(row["join"] > 0 and row["pjoin_partition 1024"] > 0 for row in got.values())  # real sizes, not refusals
+    for n in want:
+        assert got[n] == want[n], n
+
+
 def test_argument_errors_are_reported_without_a_device():
     lib = _capi.lib()
     # null pointers / bad sizes are rejected on the host before any HIP call
@@ -75,24 +108,57 @@ def test_join_partition_geometry_for_every_row_count(layout_tool):
     assert r.returncode == 0 and "join layout ok" in r.stdout, r.stdout[-2000:]
 
 
-def test_side_plan_restates_the_compiled_geometry(layout_tool):
-    """tests/join_testlib.side_plan's (parts, k1, k2) against jl_layout as compiled, at every size the layout tests use
-    and +-3 rows around the partition counts where the histogram variant changes (8192: fused, 32768: fused16, 81920:
-    the digit column), for both rows per partition; and the variants and tile shapes the layout tests rely on"""
+def _compiled_plans(layout_tool, pairs, env=None):
+    """join_layout_check with "n_side:n_build" arguments -> {(n_side, n_build, rows per partition): ((parts, k1, k2,
+    variant, t0, t1) as compiled, the meta array's word offsets and total)}"""
+    import os
     import subprocess
+    r = subprocess.run([str(layout_tool)] + [f"{a}:{b}" for a, b in pairs], capture_output=True, text=True, timeout=300,
+                       env=dict(os.environ, **(env or {})))
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
+    lines = r.stdout.split("\n")[:-1]
+    assert len(lines) == 2 * len(pairs)
+    out = {}
+    for line in lines:
+        f = line.split()
+        n_side, n_build, rows, parts, k1, k2 = map(int, f[:6])
+        out[(n_side, n_build, rows)] = ((parts, k1, k2, f[6].replace("_", " "), int(f[7]), int(f[8])), tuple(map(int, f[9:])))
+    assert len(out) == len(lines)
+    return out
+
+
+def test_side_plan_restates_the_compiled_geometry(layout_tool):
+    """tests/join_testlib.side_plan — (parts, k1, k2) AND the histogram variant and tile shapes — against jl_layout and
+    jl_side_plan (csrc/partition.hpp) as compiled, at every size the layout tests use, at the probe sides of the radix
+    join laid out by ANOTHER column's geometry (with and without the fused histograms' scratch), and +-3 rows around the
+    partition counts where the histogram variant changes (8192: fused, 32768: fused16, 81920: the digit column), for both
+    rows per partition; under the forced tile shapes and DBHIP_JL_DIGITS=0 too; and the variants and tile shapes the layout
+    tests rely on.  The meta array's size as compiled is the one groupby_hash_testlib.workspace_bytes assumes."""
     from tests import join_testlib as jt
     per_part = (jt.JL_ROWS_PER_PART, jt.JR_ROWS_PER_PART)
     sizes = set(jt.layout_sizes())
     for parts in (8192, 32768, 81920):
         for rows in per_part:
             sizes.update(parts * rows + d for d in range(-3, 4))
-    r = subprocess.run([str(layout_tool)] + [str(n) for n in sorted(sizes)], capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
-    lines = r.stdout.split("\n")[:-1]
-    assert len(lines) == 2 * len(sizes)
-    for line in lines:
-        n, rows, parts, k1, k2 = map(int, line.split())
-        assert (rows in per_part) and jt.side_plan(n, n, rows)[:3] == (parts, k1, k2), line
+    pairs = {(n, n) for n in sizes}
+    for n, radix, _ in jt.LAYOUT_TABLE:
+        large, small = jt.radix_probe_sizes(n)
+        pairs.update(((large, n), (small, n), (128 * radix[0] - 1, n), (128 * radix[0], n)))
+    pairs.add((jt.HEADLINE_PROBE, jt.HEADLINE_BUILD))
+    pairs = sorted(pairs)
+    compiled = _compiled_plans(layout_tool, pairs)
+    assert len(compiled) == 2 * len(pairs)
+    for (n_side, n_build, rows), (plan, meta) in compiled.items():
+        assert (rows in per_part) and jt.side_plan(n_side, n_build, rows) == plan, (n_side, n_build, rows, plan)
+        parts, k1 = plan[:2]
+        assert meta[-1] == (2 * 64 + 2) * k1 + 2 + 3 * parts + 1 and list(meta) == sorted(set(meta)) and meta[0] == 0
+    forced = [(1 << 20, 1 << 20), ((1 << 26) + 5, (1 << 26) + 5), (170_000_001, 170_000_001), (jt.HEADLINE_PROBE, jt.HEADLINE_BUILD)]
+    for t0, t1 in ((0, 2), (1, 0), (None, 1), (2, None)):
+        env = {k: str(v) for k, v in (("DBHIP_JL_T0", t0), ("DBHIP_JL_T1", t1)) if v is not None}
+        for (n_side, n_build, rows), (plan, _) in _compiled_plans(layout_tool, forced, env).items():
+            assert jt.side_plan(n_side, n_build, rows, t0, t1) == plan, (t0, t1, n_side, n_build, rows, plan)
+    for (n_side, n_build, rows), (plan, _) in _compiled_plans(layout_tool, forced, {"DBHIP_JL_DIGITS": "0"}).items():
+        assert jt.side_plan(n_side, n_build, rows, digits=False) == plan, (n_side, n_build, rows, plan)
     # the variant changes exactly there (parts is a multiple of k2 = 64 below 2^26 rows: 8128 partitions, then 8192)
     for rows in per_part:
         for last, below, above in ((8128, "plain", "fused"), (32768, "fused", "fused16"), (81920, "fused16", "digits")):

@@ -1,6 +1,6 @@
-"""The first call of a family in a process, captured.  join_lds.hip, groupby.hip and groupby_hash.hip set function
-attributes and ask for occupancies on first use (join_lds.hip caches the answer per host thread); the warm-up run in
-front of every other capture of this suite hides whether those calls are legal inside a capture and size the same grid
+"""The first call of a family in a process, captured.  partition.hip, join_lds.hip, groupby.hip and groupby_hash.hip set
+function attributes and ask for occupancies on first use (partition.hpp jl_resident_per_cu caches the answer per host
+thread); the warm-up run in front of every other capture of this suite hides whether those calls are legal inside a capture and size the same grid
 there.  Each test starts a fresh child process, loads the code object with one reduce, and runs one family of
 tests/test_gpu_graph_paths.py with graph_testlib.FIRST_CAPTURE set: no eager call of the family before the capture, every
 replay checked against the oracle, and the eager twin runs only after the last replay.  One child per family, one after

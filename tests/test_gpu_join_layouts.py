@@ -1,5 +1,5 @@
 """The joins on columns that do not start on a 16-byte boundary, at every histogram variant of the partition step
-(join_lds.hip jl_partition_side: one level, plain, fused, fused16, the digit column), at every forced tile shape, at
+(partition.hip jl_partition_side: one level, plain, fused, fused16, the digit column), at every forced tile shape, at
 the geometry of the 2^30 join, and in the engine's sub-joins, which start at arbitrary row counts.
 
 Every input and output column is a view `offset` words past a 16-byte boundary with guard words around it

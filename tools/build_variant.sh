@@ -3,7 +3,7 @@
 #   tools/build_variant.sh <tag> "<extra hipcc flags>" [files...]     -> dwarf_bench_amd/_lib/variants/libdbhip_<tag>.so
 set -euo pipefail
 tag="$1"; flags="$2"; shift 2
-files="${*:-join_lds join pjoin}"
+files="${*:-partition join_lds join pjoin}"
 root="$(cd "$(dirname "$0")/.." && pwd)"
 lib="$root/dwarf_bench_amd/_lib"; out="$lib/variants/$tag"
 mkdir -p "$out"
