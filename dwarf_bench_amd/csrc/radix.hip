@@ -23,6 +23,17 @@
 //      2^24 keys, dominated by look-back waits between tiles in flight; same finding as in scan.hip.)
 //   4. rs_finalize       copies tmp -> keys when an odd number of passes ran.
 //
+// Key-value sort and argsort (dbhip_radix_sort_pairs_*): the same launch path (radix_sort_impl) with a second 32-bit
+// column that travels with the keys.  Steps 1 and 2, rs_chunk_hist and rs_chunk_scan read keys only and are launched as
+// they are; the three kernels that MOVE data have an rsp_ twin that owns a second LDS tile for the values and runs the
+// same tile body with PAIRS set.  The ranking (rs_rank_rows: stable, both rank modes, the crowded-digit switch) and the
+// order tripwire are the keys-only sort's; a stable LSD sort of (key, value) pairs has exactly one answer.  Argsort
+// (vals_are_row_ids): the FIRST EXECUTED pass — known on the device only: every earlier pass has its skip flag set —
+// makes the value from the row position instead of loading it; when no pass executes, rsp_finalize writes 0..n-1.  The
+// header is the keys-only one: the flag is derived from the plan's skip flags.  The fault hook DBHIP_RS_INJECT_UNSTABLE
+// is compiled into the keys-only kernels alone.  Bytes per executed pass: 4n (chunk histogram) + 8n + 8n (scatter) =
+// 20n, argsort's first executed pass 16n.
+//
 // Round 3, measured and NOT kept (commit 790ed71 holds the code; same-box A/B at 2^24 full-range keys, round 2's
 // library beside it: 8-bit 203.8 us, 4-bit 361.1 us):
 //   * 4-bit passes that read their keys ONCE: the scatter of pass k counts every key's next digit d' against the key's
@@ -578,15 +589,70 @@ __device__ __forceinline__ void rs_rank_rows(const unsigned (&key)[kRsKpt], unsi
   }
 }
 
+// Digit owners (thread d < radix owns digit d): the waves' counts of a tile in s_cnt become wave-exclusive offsets in
+// place.  Returns the tile-local exclusive offset of the thread's digit, tile_count = the tile's keys of that digit.
+// Holds a barrier: called by the whole workgroup, with the ranking's counters complete.  (tid, lane and wave are the
+// caller's: derived from threadIdx.x again in here, the callers' address arithmetic compiles to other instructions.)
+template <int BITS>
+__device__ __forceinline__ unsigned rs_digit_offsets(unsigned tid, unsigned lane, unsigned wave, unsigned (*s_cnt)[1 << BITS],
+                                                     unsigned *s_wsum, unsigned &tile_count) {
+  constexpr int kRadix = 1 << BITS;
+  tile_count = 0;
+  if (tid < kRadix) {
+#pragma unroll
+    for (int w = 0; w < kRsWaves; ++w) {
+      const unsigned c = s_cnt[w][tid];
+      s_cnt[w][tid] = tile_count;
+      tile_count += c;
+    }
+  }
+  const unsigned incl = wave_inclusive_scan(tile_count);
+  if (lane == kWave - 1) s_wsum[wave] = incl;
+  __syncthreads();
+  unsigned dexcl = incl - tile_count;
+  for (unsigned w = 0; w < wave; ++w) dexcl += s_wsum[w];
+  return dexcl;
+}
+
+// Test hook of the keys-only sort (DBHIP_RS_INJECT_UNSTABLE; uniform): thread 0 swaps the first neighbours among the
+// re-ordered tile's `valid` keys — looking no further than position `cap` — that share the digit and differ below it.
+// Holds a barrier.
+template <int BITS>
+__device__ __forceinline__ void rs_inject_unstable(unsigned *s_keys, unsigned valid, unsigned cap, int shift, unsigned xor_mask,
+                                                   unsigned low_mask) {
+  constexpr int kRadix = 1 << BITS;
+  if (threadIdx.x == 0)
+    for (unsigned p = 0; p + 1 < valid && p < cap; ++p) {
+      const unsigned a = s_keys[p] ^ xor_mask, b = s_keys[p + 1] ^ xor_mask;
+      if ((((a ^ b) >> shift) & (kRadix - 1)) == 0 && ((a ^ b) & low_mask) != 0) {
+        const unsigned t = s_keys[p];
+        s_keys[p] = s_keys[p + 1];
+        s_keys[p + 1] = t;
+        break;
+      }
+    }
+  __syncthreads();
+}
+
+__device__ __forceinline__ bool rs_first_executed(const RsHeader *hdr, int pass) {
+  bool first = true;
+  for (int q = 0; q < pass; ++q) first = first && hdr->pass[q].skip != 0;
+  return first;
+}
+
 // ---- per pass, kernel 3: stable scatter of every chunk -------------------------------------------------
 // One tile of the scatter: stable rank inside each wave, digit offsets across waves, re-order through LDS, write out
 // in digit order.  FULL = the tile holds kRsTile keys: no per-key bounds checks (the kernel is VALU-bound — about 100
-// vector instructions per 64 keys, 80 % of the issue slots at 2^24 keys by the SQ counters).
-template <int BITS, bool FULL, bool ARANK>
-__device__ __forceinline__ unsigned rs_scatter_tile(const unsigned *__restrict__ src, unsigned *__restrict__ dst,
-                                                size_t tile_base, unsigned valid_in_tile, int shift, unsigned xor_mask,
-                                                bool inject, unsigned &running, unsigned (*s_cnt)[1 << BITS], unsigned *s_dexcl,
-                                                unsigned *s_goff, unsigned *s_wsum, unsigned *s_keys) {
+// vector instructions per 64 keys, 80 % of the issue slots at 2^24 keys by the SQ counters).  PAIRS = a value travels
+// with every key (vsrc -> vdst through s_vals; all three null without it); `flag` is uniform: keys-only the fault hook,
+// pairs "make the values from the row positions" (argsort's first executed pass).
+template <int BITS, bool FULL, bool ARANK, bool PAIRS>
+__device__ __forceinline__ unsigned rs_scatter_tile(const unsigned *__restrict__ src, const unsigned *__restrict__ vsrc,
+                                                    unsigned *__restrict__ dst, unsigned *__restrict__ vdst,
+                                                    size_t tile_base, unsigned valid_in_tile, int shift, unsigned xor_mask,
+                                                    bool flag, unsigned &running, unsigned (*s_cnt)[1 << BITS],
+                                                    unsigned *s_dexcl, unsigned *s_goff, unsigned *s_wsum, unsigned *s_keys,
+                                                    unsigned *s_vals) {
   constexpr int kRadix = 1 << BITS;
   const unsigned tid = threadIdx.x, lane = tid & (kWave - 1), wave = tid / kWave;
   const unsigned wave_first = wave * kRsWaveKeys + lane;
@@ -605,20 +671,8 @@ __device__ __forceinline__ unsigned rs_scatter_tile(const unsigned *__restrict__
   __syncthreads();
 
   // ---- digit owners: counts across waves -> wave-exclusive offsets, tile totals
-  unsigned tile_count = 0;
-  if (tid < kRadix) {
-#pragma unroll
-    for (int w = 0; w < kRsWaves; ++w) {
-      const unsigned c = s_cnt[w][tid];
-      s_cnt[w][tid] = tile_count;
-      tile_count += c;
-    }
-  }
-  const unsigned incl = wave_inclusive_scan(tile_count);
-  if (lane == kWave - 1) s_wsum[wave] = incl;
-  __syncthreads();
-  unsigned dexcl = incl - tile_count;
-  for (unsigned w = 0; w < wave; ++w) dexcl += s_wsum[w];
+  unsigned tile_count;
+  const unsigned dexcl = rs_digit_offsets<BITS>(tid, lane, wave, s_cnt, s_wsum, tile_count);
   if (tid < kRadix) {
     s_dexcl[tid] = dexcl;
     s_goff[tid] = running - dexcl;
@@ -626,29 +680,36 @@ __device__ __forceinline__ unsigned rs_scatter_tile(const unsigned *__restrict__
   }
   __syncthreads();
 
-  // ---- re-order the tile by digit in LDS
+  // ---- the values, loaded late (argsort's first executed pass: the row position).  They are not live while the tile
+  // is ranked.  (Requested one barrier earlier, so that the loads fly during the digit owners' scan, the ballot-ranking
+  // scatter needs 16 bytes of scratch at its 128 VGPRs.)
+  unsigned val[PAIRS ? kRsKpt : 1];
+  if constexpr (PAIRS) {
+#pragma unroll
+    for (int j = 0; j < kRsKpt; ++j) {
+      const unsigned idx = wave_first + j * kWave;
+      if (flag)
+        val[j] = static_cast<unsigned>(tile_base) + idx;
+      else
+        val[j] = (FULL || idx < valid_in_tile) ? vsrc[tile_base + idx] : 0u;
+    }
+  }
+
+  // ---- re-order the tile by digit in LDS (both columns to the same position)
 #pragma unroll
   for (int j = 0; j < kRsKpt; ++j) {
     if (FULL || wave_first + j * kWave < valid_in_tile) {
       const unsigned d = ((key[j] ^ xor_mask) >> shift) & (kRadix - 1);
-      s_keys[s_dexcl[d] + s_cnt[wave][d] + rank[j]] = key[j];
+      const unsigned pos = s_dexcl[d] + s_cnt[wave][d] + rank[j];
+      s_keys[pos] = key[j];
+      if constexpr (PAIRS) s_vals[pos] = val[j];
     }
   }
   __syncthreads();
 
   const unsigned low_mask = shift + BITS >= 32 ? 0xFFFFFFFFu : (1u << (shift + BITS)) - 1u;
-  if (inject) {  // test hook (uniform): swap the first neighbours that share the digit and differ below it
-    if (tid == 0)
-      for (unsigned p = 0; p + 1 < valid_in_tile && p < 4096; ++p) {
-        const unsigned a = s_keys[p] ^ xor_mask, b = s_keys[p + 1] ^ xor_mask;
-        if ((((a ^ b) >> shift) & (kRadix - 1)) == 0 && ((a ^ b) & low_mask) != 0) {
-          const unsigned t = s_keys[p];
-          s_keys[p] = s_keys[p + 1];
-          s_keys[p + 1] = t;
-          break;
-        }
-      }
-    __syncthreads();
+  if constexpr (!PAIRS) {
+    if (flag) rs_inject_unstable<BITS>(s_keys, valid_in_tile, 4096u, shift, xor_mask, low_mask);
   }
 
   // ---- write out in digit order: consecutive lanes -> consecutive addresses inside a digit run
@@ -658,6 +719,8 @@ __device__ __forceinline__ unsigned rs_scatter_tile(const unsigned *__restrict__
     const unsigned p = k * kRsThreads + tid;
     if (FULL || p < valid_in_tile) {
       const unsigned kk = s_keys[p];
+      unsigned vv = 0;
+      if constexpr (PAIRS) vv = s_vals[p];
       const unsigned kx = kk ^ xor_mask;
       // the tile as it now lies in LDS must be sorted by its low (shift + BITS) bits (stable ranking, here and in every
       // earlier pass): my left neighbour's may not exceed mine.  The neighbour's key comes over DPP (wave_shr:1; lane 0
@@ -666,7 +729,9 @@ __device__ __forceinline__ unsigned rs_scatter_tile(const unsigned *__restrict__
       const unsigned left = __builtin_amdgcn_update_dpp(0u, mine, 0x138, 0xf, 0xf, false);
       bad |= left > mine ? 1u : 0u;
       const unsigned d = (kx >> shift) & (kRadix - 1);
-      dst[s_goff[d] + p] = kk;
+      const unsigned at = s_goff[d] + p;
+      dst[at] = kk;
+      if constexpr (PAIRS) vdst[at] = vv;
     }
   }
   // (Round 4 measured what comparing the pairs the DPP compare cannot see — last key of a 64-key row against the first of
@@ -678,6 +743,11 @@ __device__ __forceinline__ unsigned rs_scatter_tile(const unsigned *__restrict__
   return bad;
 }
 
+// One workgroup per chunk, tile by tile.  The two kernels below keep a body each: moved into one device function behind
+// both names (tried as forced and as ordinary inline, with and without __restrict__ on its parameters, with the running
+// offsets owned by the kernel or by the function) the same statements compile to other instructions — the function is
+// optimised on flat pointers before it is inlined, the kernel body on global ones, and the tile loop's trip count and the
+// update of `running` end up elsewhere — and this is where the sort's time goes.
 template <int BITS, bool ARANK>
 __global__ __launch_bounds__(kRsThreads, DBHIP_RS_WPE) void rs_chunk_scatter_kernel(unsigned *keys, unsigned *tmp, size_t n,
                                                                          int pass, unsigned xor_mask,
@@ -735,11 +805,69 @@ __global__ __launch_bounds__(kRsThreads, DBHIP_RS_WPE) void rs_chunk_scatter_ker
     const size_t tile_base = tile * kRsTile;
     const unsigned valid_in_tile = static_cast<unsigned>(n - tile_base < kRsTile ? n - tile_base : kRsTile);
     if (valid_in_tile == kRsTile)  // every tile but the input's last one
-      bad |= rs_scatter_tile<BITS, true, ARANK>(src, dst, tile_base, valid_in_tile, shift, xor_mask, inject != 0 && tile == 0,
-                                                running, s_cnt, s_dexcl, s_goff, s_wsum, s_keys);
+      bad |= rs_scatter_tile<BITS, true, ARANK, false>(src, nullptr, dst, nullptr, tile_base, valid_in_tile, shift, xor_mask,
+                                                       inject != 0 && tile == 0, running, s_cnt, s_dexcl, s_goff, s_wsum,
+                                                       s_keys, nullptr);
     else
-      bad |= rs_scatter_tile<BITS, false, ARANK>(src, dst, tile_base, valid_in_tile, shift, xor_mask, inject != 0 && tile == 0,
-                                                 running, s_cnt, s_dexcl, s_goff, s_wsum, s_keys);
+      bad |= rs_scatter_tile<BITS, false, ARANK, false>(src, nullptr, dst, nullptr, tile_base, valid_in_tile, shift, xor_mask,
+                                                        inject != 0 && tile == 0, running, s_cnt, s_dexcl, s_goff, s_wsum,
+                                                        s_keys, nullptr);
+  }
+  if (bad) atomicOr(&hdr->status, DBHIP_DEV_RANK_ORDER);
+}
+
+// rs_chunk_scatter_kernel with the values: a second LDS tile (s_vals, 32 KiB: 74 KiB per workgroup, two workgroups per CU
+// as in the keys-only scatter), and argsort's first executed pass makes its values instead of loading them
+template <int BITS, bool ARANK>
+__global__ __launch_bounds__(kRsThreads, DBHIP_RS_WPE) void rsp_chunk_scatter_kernel(
+    unsigned *keys, unsigned *vals, unsigned *tmp, unsigned *vtmp, size_t n, int pass, unsigned xor_mask, unsigned row_ids,
+    RsHeader *hdr, const unsigned *__restrict__ offsets, const unsigned *__restrict__ bases, size_t tiles_per_chunk,
+    size_t num_chunks) {
+  constexpr int kRadix = 1 << BITS;
+  __shared__ unsigned s_cnt[kRsWaves][kRadix];
+  __shared__ unsigned s_dexcl[kRadix];
+  __shared__ unsigned s_goff[kRadix];
+  __shared__ unsigned s_wsum[kRsWaves];
+  __shared__ unsigned s_keys[kRsTile];
+  __shared__ unsigned s_vals[kRsTile];
+
+  const RsPass plan = hdr->pass[pass];
+  if (plan.skip) return;  // uniform over the grid
+  const bool make_ids = row_ids != 0 && rs_first_executed(hdr, pass);  // uniform over the grid
+  const unsigned *__restrict__ src = plan.src_is_tmp ? tmp : keys;
+  const unsigned *__restrict__ vsrc = plan.src_is_tmp ? vtmp : vals;
+  unsigned *__restrict__ dst = plan.src_is_tmp ? keys : tmp;
+  unsigned *__restrict__ vdst = plan.src_is_tmp ? vals : vtmp;
+  const int shift = pass * BITS;
+
+  const unsigned tid = threadIdx.x;
+  const size_t per_xcd = (num_chunks + 7) / 8;  // XCD-aware chunk order, as in rs_chunk_scatter_kernel
+  const size_t chunk = (blockIdx.x % 8u) * per_xcd + blockIdx.x / 8u;
+  if (chunk >= num_chunks || blockIdx.x / 8u >= per_xcd) return;
+  const size_t first_tile = chunk * tiles_per_chunk;
+  const size_t total_tiles = (n + kRsTile - 1) / kRsTile;
+  size_t last_tile = first_tile + tiles_per_chunk;
+  last_tile = last_tile < total_tiles ? last_tile : total_tiles;
+  unsigned running = 0;
+  if (tid < kRadix) {
+    if (bases) {
+      running = bases[pass * kRsMaxRadix + tid];
+      const unsigned *row = offsets + static_cast<size_t>(tid) * rs_row_stride(num_chunks);
+      for (size_t c = 0; c < chunk; ++c) running += row[c];
+    } else {
+      running = offsets[static_cast<size_t>(tid) * rs_row_stride(num_chunks) + chunk];
+    }
+  }
+  unsigned bad = 0;
+  for (size_t tile = first_tile; tile < last_tile; ++tile) {
+    const size_t tile_base = tile * kRsTile;
+    const unsigned valid_in_tile = static_cast<unsigned>(n - tile_base < kRsTile ? n - tile_base : kRsTile);
+    if (valid_in_tile == kRsTile)
+      bad |= rs_scatter_tile<BITS, true, ARANK, true>(src, vsrc, dst, vdst, tile_base, valid_in_tile, shift, xor_mask, make_ids,
+                                                      running, s_cnt, s_dexcl, s_goff, s_wsum, s_keys, s_vals);
+    else
+      bad |= rs_scatter_tile<BITS, false, ARANK, true>(src, vsrc, dst, vdst, tile_base, valid_in_tile, shift, xor_mask, make_ids,
+                                                       running, s_cnt, s_dexcl, s_goff, s_wsum, s_keys, s_vals);
   }
   if (bad) atomicOr(&hdr->status, DBHIP_DEV_RANK_ORDER);
 }
@@ -794,20 +922,8 @@ __global__ __launch_bounds__(kRsThreads, DBHIP_RS_WPE) void rs_single_tile_kerne
     unsigned rank[kRsKpt];
     rs_rank_rows<BITS, true, ARANK>(key, rank, s_cnt[wave], wave_first, n, shift, xor_mask);
     __syncthreads();
-    unsigned tile_count = 0;
-    if (tid < kRadix) {
-#pragma unroll
-      for (int w = 0; w < kRsWaves; ++w) {
-        const unsigned c = s_cnt[w][tid];
-        s_cnt[w][tid] = tile_count;
-        tile_count += c;
-      }
-    }
-    const unsigned incl = wave_inclusive_scan(tile_count);
-    if (lane == kWave - 1) s_wsum[wave] = incl;
-    __syncthreads();
-    unsigned dexcl = incl - tile_count;
-    for (unsigned w = 0; w < wave; ++w) dexcl += s_wsum[w];
+    unsigned tile_count;
+    const unsigned dexcl = rs_digit_offsets<BITS>(tid, lane, wave, s_cnt, s_wsum, tile_count);
     if (tid < kRadix) s_dexcl[tid] = dexcl;
     __syncthreads();
 #pragma unroll
@@ -818,19 +934,7 @@ __global__ __launch_bounds__(kRsThreads, DBHIP_RS_WPE) void rs_single_tile_kerne
       }
     }
     __syncthreads();
-    if (inject) {  // test hook (uniform), as in rs_scatter_tile: swap the first neighbours that share the digit and differ below it
-      if (tid == 0)
-        for (unsigned p = 0; p + 1 < n; ++p) {
-          const unsigned a = s_keys[p] ^ xor_mask, b = s_keys[p + 1] ^ xor_mask;
-          if ((((a ^ b) >> shift) & (kRadix - 1)) == 0 && ((a ^ b) & low_mask) != 0) {
-            const unsigned t = s_keys[p];
-            s_keys[p] = s_keys[p + 1];
-            s_keys[p + 1] = t;
-            break;
-          }
-        }
-      __syncthreads();
-    }
+    if (inject) rs_inject_unstable<BITS>(s_keys, n, ~0u, shift, xor_mask, low_mask);  // test hook (uniform)
 #pragma unroll
     for (int j = 0; j < kRsKpt; ++j) {
       const unsigned idx = wave_first + j * kWave;
@@ -848,260 +952,10 @@ __global__ __launch_bounds__(kRsThreads, DBHIP_RS_WPE) void rs_single_tile_kerne
   }
 }
 
-__global__ __launch_bounds__(kRsThreads) void rs_finalize_kernel(unsigned *__restrict__ keys,
-                                                                 const unsigned *__restrict__ tmp,
-                                                                 size_t n, const RsHeader *hdr) {
-  if (!hdr->final_in_tmp) return;
-  const size_t stride = static_cast<size_t>(gridDim.x) * kRsThreads;
-  const size_t n4 = n / 4;
-  const u32x4 *s4 = reinterpret_cast<const u32x4 *>(tmp);
-  u32x4 *d4 = reinterpret_cast<u32x4 *>(keys);
-  for (size_t i = static_cast<size_t>(blockIdx.x) * kRsThreads + threadIdx.x; i < n4; i += stride)
-    d4[i] = s4[i];
-  if (blockIdx.x == 0 && threadIdx.x < (n & 3)) keys[n4 * 4 + threadIdx.x] = tmp[n4 * 4 + threadIdx.x];
-}
-
-template <int BITS>
-int radix_sort_impl(unsigned *keys, unsigned *tmp, size_t n, unsigned xor_mask, void *workspace,
-                    hipStream_t s, const DeviceInfo &dev) {
-  constexpr int kPasses = 32 / BITS;
-  constexpr int kRadix = 1 << BITS;
-  const RsGeometry g = rs_geometry(n, BITS);
-  char *base = static_cast<char *>(workspace);
-  RsHeader *hdr = reinterpret_cast<RsHeader *>(base);
-  unsigned *totals = reinterpret_cast<unsigned *>(base + kRsTotalsOff);
-  unsigned *bases = reinterpret_cast<unsigned *>(base + kRsBasesOff);
-  unsigned *counts = reinterpret_cast<unsigned *>(base + kRsCountsOff);
-
-  const bool arank = rank_by_lds_atomics();
-  const unsigned inject = rank_fault_injection();
-  if (n <= static_cast<size_t>(kRsTile)) {  // one tile: one workgroup, one launch (+ the status word)
-    const hipError_t e0 = fill_async(workspace, 0, kWsHeader, s);
-    if (e0 != hipSuccess) return static_cast<int>(e0);
-    if (arank)
-      hipLaunchKernelGGL((rs_single_tile_kernel<BITS, true>), dim3(1), dim3(kRsThreads), 0, s, keys,
-                         static_cast<unsigned>(n), xor_mask, &hdr->status, rank_fault_injection());
-    else
-      hipLaunchKernelGGL((rs_single_tile_kernel<BITS, false>), dim3(1), dim3(kRsThreads), 0, s, keys,
-                         static_cast<unsigned>(n), xor_mask, &hdr->status, rank_fault_injection());
-    return launch_status();
-  }
-  hipError_t e = fill_async(workspace, 0, kRsCountsOff, s);  // header + totals (+ bases)
-  if (e != hipSuccess) return static_cast<int>(e);
-
-  const size_t want = (n / 4 + kRsThreads - 1) / kRsThreads;
-  const size_t cap = static_cast<size_t>(dev.cus) * 4;
-  const unsigned hgrid = static_cast<unsigned>(want < cap ? (want ? want : 1) : cap);
-  const size_t hist_groups = (g.chunks + rs_hist_cpw<BITS>() - 1) / rs_hist_cpw<BITS>();
-  const unsigned hist_grid = static_cast<unsigned>(hist_groups < cap ? hist_groups : cap);
-  hipLaunchKernelGGL((rs_histogram_kernel<BITS>), dim3(hist_grid), dim3(kRsThreads), 0, s, keys, n,
-                     xor_mask, totals, counts, g.tiles_per_chunk, g.chunks);
-  hipLaunchKernelGGL((rs_plan_kernel<BITS>), dim3(1), dim3(kRsThreads), 0, s, n, hdr, totals, bases);
-  const unsigned cgrid = static_cast<unsigned>(g.chunks);
-  const bool fused_scan = g.chunks <= kRsFusedScanChunks;
-  for (int p = 0; p < kPasses; ++p) {
-    if (p > 0)  // pass 0's chunk counts came with the up-front histogram
-      hipLaunchKernelGGL((rs_chunk_hist_kernel<BITS>), dim3((cgrid + rs_hist_cpw<BITS>() - 1) / rs_hist_cpw<BITS>()), dim3(kRsThreads), 0, s, keys, tmp, n, p, xor_mask,
-                         hdr, counts, g.tiles_per_chunk, g.chunks);
-    if (!fused_scan)
-      hipLaunchKernelGGL((rs_chunk_scan_kernel<BITS>), dim3(kRadix), dim3(kRsThreads), 0, s, p, hdr, bases, counts,
-                         g.chunks);
-    const unsigned *fused_bases = fused_scan ? bases : static_cast<const unsigned *>(nullptr);
-    if (arank)
-      hipLaunchKernelGGL((rs_chunk_scatter_kernel<BITS, true>), dim3((cgrid + 7) / 8 * 8), dim3(kRsThreads), 0, s, keys,
-                         tmp, n, p, xor_mask, hdr, counts, fused_bases, inject, g.tiles_per_chunk, g.chunks);
-    else
-      hipLaunchKernelGGL((rs_chunk_scatter_kernel<BITS, false>), dim3((cgrid + 7) / 8 * 8), dim3(kRsThreads), 0, s, keys,
-                         tmp, n, p, xor_mask, hdr, counts, fused_bases, inject, g.tiles_per_chunk, g.chunks);
-  }
-  hipLaunchKernelGGL(rs_finalize_kernel, dim3(hgrid), dim3(kRsThreads), 0, s, keys, tmp, n, hdr);
-  return launch_status();
-}
-
-int radix_sort_entry(unsigned *keys, unsigned *tmp, size_t n, int radix_bits, unsigned xor_mask,
-                     void *workspace, size_t workspace_bytes, dbhip_stream_t stream) {
-  if (radix_bits != 4 && radix_bits != 8) return DBHIP_EINVAL;
-  if (n >= (1ull << 32)) return DBHIP_EINVAL;  // 32-bit offsets
-  if (n == 0) {  // nothing to sort; a workspace that was passed still gets a clean status word
-    if (workspace && ws_ok(workspace, workspace_bytes, kWsHeader))
-      return static_cast<int>(fill_async(workspace, 0, kWsHeader, as_stream(stream)));
-    return DBHIP_OK;
-  }
-  if (!keys || !tmp) return DBHIP_EINVAL;
-  if ((reinterpret_cast<uintptr_t>(keys) | reinterpret_cast<uintptr_t>(tmp)) & 15u) return DBHIP_EINVAL;  // dbhip.h: 16-byte aligned
-  if (!ws_ok(workspace, workspace_bytes, dbhip_radix_sort_workspace_bytes(n, radix_bits)))
-    return DBHIP_EWORKSPACE;
-  const DeviceInfo &dev = current_device_info();
-  if (!dev.ok) return DBHIP_ENODEVICE;
-  return radix_bits == 8
-             ? radix_sort_impl<8>(keys, tmp, n, xor_mask, workspace, as_stream(stream), dev)
-             : radix_sort_impl<4>(keys, tmp, n, xor_mask, workspace, as_stream(stream), dev);
-}
-
-// ---- key-value sort and argsort (dbhip_radix_sort_pairs_*) ------------------------------------------------------------
-// The same passes with a second 32-bit column that travels with the keys.  The up-front histogram, the plan, the chunk
-// histogram and the chunk scan read keys only and are launched as they are; the three kernels that MOVE data have a
-// pairs variant below.  The ranking is the keys-only sort's (rs_rank_rows: stable, both rank modes, the crowded-digit
-// switch), so is the order tripwire; a stable LSD sort of (key, value) pairs has exactly one answer.
-//   * values are not live while a tile is ranked: they are loaded once the digit offsets are known, right before the
-//     re-order, and go through a second LDS tile (s_vals, 32 KiB: 74 KiB per workgroup, two workgroups per CU as in
-//     the keys-only scatter) to the position their key takes.  (Requested one barrier earlier, so that the loads fly
-//     during the digit owners' scan, the ballot-ranking scatter needs 16 bytes of scratch at its 128 VGPRs.)
-//   * argsort (vals_are_row_ids): the FIRST EXECUTED pass — known on the device only: every earlier pass has its skip
-//     flag set — makes the value from the row position instead of loading it; when no pass executes the finalize
-//     kernel writes 0..n-1.  The header is the keys-only one: the flag is derived from the plan's skip flags.
-// Bytes per executed pass: 4n (chunk histogram) + 8n + 8n (scatter) = 20n, argsort's first executed pass 16n.
-__device__ __forceinline__ bool rs_first_executed(const RsHeader *hdr, int pass) {
-  bool first = true;
-  for (int q = 0; q < pass; ++q) first = first && hdr->pass[q].skip != 0;
-  return first;
-}
-
-template <int BITS, bool FULL, bool ARANK>
-__device__ __forceinline__ unsigned rsp_scatter_tile(const unsigned *__restrict__ src, const unsigned *__restrict__ vsrc,
-                                                     unsigned *__restrict__ dst, unsigned *__restrict__ vdst,
-                                                     size_t tile_base, unsigned valid_in_tile, int shift, unsigned xor_mask,
-                                                     bool make_ids, unsigned &running, unsigned (*s_cnt)[1 << BITS],
-                                                     unsigned *s_dexcl, unsigned *s_goff, unsigned *s_wsum, unsigned *s_keys,
-                                                     unsigned *s_vals) {
-  constexpr int kRadix = 1 << BITS;
-  const unsigned tid = threadIdx.x, lane = tid & (kWave - 1), wave = tid / kWave;
-  const unsigned wave_first = wave * kRsWaveKeys + lane;
-  unsigned key[kRsKpt];
-#pragma unroll
-  for (int j = 0; j < kRsKpt; ++j) {
-    const unsigned idx = wave_first + j * kWave;
-    key[j] = (FULL || idx < valid_in_tile) ? src[tile_base + idx] : 0xFFFFFFFFu;
-  }
-  for (int i = tid; i < kRsWaves * kRadix; i += kRsThreads) (&s_cnt[0][0])[i] = 0;
-  __syncthreads();
-
-  unsigned rank[kRsKpt];
-  rs_rank_rows<BITS, !FULL, ARANK>(key, rank, s_cnt[wave], wave_first, valid_in_tile, shift, xor_mask);
-  __syncthreads();
-
-  unsigned tile_count = 0;
-  if (tid < kRadix) {
-#pragma unroll
-    for (int w = 0; w < kRsWaves; ++w) {
-      const unsigned c = s_cnt[w][tid];
-      s_cnt[w][tid] = tile_count;
-      tile_count += c;
-    }
-  }
-  const unsigned incl = wave_inclusive_scan(tile_count);
-  if (lane == kWave - 1) s_wsum[wave] = incl;
-  __syncthreads();
-  unsigned dexcl = incl - tile_count;
-  for (unsigned w = 0; w < wave; ++w) dexcl += s_wsum[w];
-  if (tid < kRadix) {
-    s_dexcl[tid] = dexcl;
-    s_goff[tid] = running - dexcl;
-    running += tile_count;
-  }
-  __syncthreads();
-
-  // ---- the values, loaded late (argsort's first executed pass: the row position)
-  unsigned val[kRsKpt];
-#pragma unroll
-  for (int j = 0; j < kRsKpt; ++j) {
-    const unsigned idx = wave_first + j * kWave;
-    if (make_ids)
-      val[j] = static_cast<unsigned>(tile_base) + idx;
-    else
-      val[j] = (FULL || idx < valid_in_tile) ? vsrc[tile_base + idx] : 0u;
-  }
-
-  // ---- re-order the tile by digit in LDS, both columns to the same position
-#pragma unroll
-  for (int j = 0; j < kRsKpt; ++j) {
-    if (FULL || wave_first + j * kWave < valid_in_tile) {
-      const unsigned d = ((key[j] ^ xor_mask) >> shift) & (kRadix - 1);
-      const unsigned pos = s_dexcl[d] + s_cnt[wave][d] + rank[j];
-      s_keys[pos] = key[j];
-      s_vals[pos] = val[j];
-    }
-  }
-  __syncthreads();
-
-  // ---- write out in digit order: two coalesced stores per position; the order check of rs_scatter_tile
-  const unsigned low_mask = shift + BITS >= 32 ? 0xFFFFFFFFu : (1u << (shift + BITS)) - 1u;
-  unsigned bad = 0;
-#pragma unroll
-  for (int k = 0; k < kRsKpt; ++k) {
-    const unsigned p = k * kRsThreads + tid;
-    if (FULL || p < valid_in_tile) {
-      const unsigned kk = s_keys[p];
-      const unsigned vv = s_vals[p];
-      const unsigned kx = kk ^ xor_mask;
-      const unsigned mine = kx & low_mask;
-      const unsigned left = __builtin_amdgcn_update_dpp(0u, mine, 0x138, 0xf, 0xf, false);
-      bad |= left > mine ? 1u : 0u;
-      const unsigned d = (kx >> shift) & (kRadix - 1);
-      const unsigned at = s_goff[d] + p;
-      dst[at] = kk;
-      vdst[at] = vv;
-    }
-  }
-  __syncthreads();
-  return bad;
-}
-
-template <int BITS, bool ARANK>
-__global__ __launch_bounds__(kRsThreads, DBHIP_RS_WPE) void rsp_chunk_scatter_kernel(
-    unsigned *keys, unsigned *vals, unsigned *tmp, unsigned *vtmp, size_t n, int pass, unsigned xor_mask, unsigned row_ids,
-    RsHeader *hdr, const unsigned *__restrict__ offsets, const unsigned *__restrict__ bases, size_t tiles_per_chunk,
-    size_t num_chunks) {
-  constexpr int kRadix = 1 << BITS;
-  __shared__ unsigned s_cnt[kRsWaves][kRadix];
-  __shared__ unsigned s_dexcl[kRadix];
-  __shared__ unsigned s_goff[kRadix];
-  __shared__ unsigned s_wsum[kRsWaves];
-  __shared__ unsigned s_keys[kRsTile];
-  __shared__ unsigned s_vals[kRsTile];
-
-  const RsPass plan = hdr->pass[pass];
-  if (plan.skip) return;  // uniform over the grid
-  const bool make_ids = row_ids != 0 && rs_first_executed(hdr, pass);  // uniform over the grid
-  const unsigned *__restrict__ src = plan.src_is_tmp ? tmp : keys;
-  const unsigned *__restrict__ vsrc = plan.src_is_tmp ? vtmp : vals;
-  unsigned *__restrict__ dst = plan.src_is_tmp ? keys : tmp;
-  unsigned *__restrict__ vdst = plan.src_is_tmp ? vals : vtmp;
-  const int shift = pass * BITS;
-
-  const unsigned tid = threadIdx.x;
-  const size_t per_xcd = (num_chunks + 7) / 8;  // XCD-aware chunk order, as in rs_chunk_scatter_kernel
-  const size_t chunk = (blockIdx.x % 8u) * per_xcd + blockIdx.x / 8u;
-  if (chunk >= num_chunks || blockIdx.x / 8u >= per_xcd) return;
-  const size_t first_tile = chunk * tiles_per_chunk;
-  const size_t total_tiles = (n + kRsTile - 1) / kRsTile;
-  size_t last_tile = first_tile + tiles_per_chunk;
-  last_tile = last_tile < total_tiles ? last_tile : total_tiles;
-  unsigned running = 0;
-  if (tid < kRadix) {
-    if (bases) {
-      running = bases[pass * kRsMaxRadix + tid];
-      const unsigned *row = offsets + static_cast<size_t>(tid) * rs_row_stride(num_chunks);
-      for (size_t c = 0; c < chunk; ++c) running += row[c];
-    } else {
-      running = offsets[static_cast<size_t>(tid) * rs_row_stride(num_chunks) + chunk];
-    }
-  }
-  unsigned bad = 0;
-  for (size_t tile = first_tile; tile < last_tile; ++tile) {
-    const size_t tile_base = tile * kRsTile;
-    const unsigned valid_in_tile = static_cast<unsigned>(n - tile_base < kRsTile ? n - tile_base : kRsTile);
-    if (valid_in_tile == kRsTile)
-      bad |= rsp_scatter_tile<BITS, true, ARANK>(src, vsrc, dst, vdst, tile_base, valid_in_tile, shift, xor_mask, make_ids,
-                                                 running, s_cnt, s_dexcl, s_goff, s_wsum, s_keys, s_vals);
-    else
-      bad |= rsp_scatter_tile<BITS, false, ARANK>(src, vsrc, dst, vdst, tile_base, valid_in_tile, shift, xor_mask, make_ids,
-                                                  running, s_cnt, s_dexcl, s_goff, s_wsum, s_keys, s_vals);
-  }
-  if (bad) atomicOr(&hdr->status, DBHIP_DEV_RANK_ORDER);
-}
-
-// n <= one tile: both columns stay in registers between the passes of one workgroup (rs_single_tile_kernel with values)
+// n <= one tile: both columns stay in registers between the passes of one workgroup (rs_single_tile_kernel with values).
+// A body of its own: as one device function behind both kernel names the two compile to the same number of instructions,
+// registers and LDS bytes but not to the same text, and the same-box A/B at 2^13 keys (profiles/r09_sort_ab.txt) did not
+// stay inside the parent's spread.
 template <int BITS, bool ARANK>
 __global__ __launch_bounds__(kRsThreads, DBHIP_RS_WPE) void rsp_single_tile_kernel(unsigned *keys, unsigned *vals, unsigned n,
                                                                                    unsigned xor_mask, unsigned row_ids,
@@ -1152,20 +1006,8 @@ __global__ __launch_bounds__(kRsThreads, DBHIP_RS_WPE) void rsp_single_tile_kern
     unsigned rank[kRsKpt];
     rs_rank_rows<BITS, true, ARANK>(key, rank, s_cnt[wave], wave_first, n, shift, xor_mask);
     __syncthreads();
-    unsigned tile_count = 0;
-    if (tid < kRadix) {
-#pragma unroll
-      for (int w = 0; w < kRsWaves; ++w) {
-        const unsigned c = s_cnt[w][tid];
-        s_cnt[w][tid] = tile_count;
-        tile_count += c;
-      }
-    }
-    const unsigned incl = wave_inclusive_scan(tile_count);
-    if (lane == kWave - 1) s_wsum[wave] = incl;
-    __syncthreads();
-    unsigned dexcl = incl - tile_count;
-    for (unsigned w = 0; w < wave; ++w) dexcl += s_wsum[w];
+    unsigned tile_count;
+    const unsigned dexcl = rs_digit_offsets<BITS>(tid, lane, wave, s_cnt, s_wsum, tile_count);
     if (tid < kRadix) s_dexcl[tid] = dexcl;
     __syncthreads();
 #pragma unroll
@@ -1197,6 +1039,19 @@ __global__ __launch_bounds__(kRsThreads, DBHIP_RS_WPE) void rsp_single_tile_kern
       vals[idx] = val[j];
     }
   }
+}
+
+__global__ __launch_bounds__(kRsThreads) void rs_finalize_kernel(unsigned *__restrict__ keys,
+                                                                 const unsigned *__restrict__ tmp,
+                                                                 size_t n, const RsHeader *hdr) {
+  if (!hdr->final_in_tmp) return;
+  const size_t stride = static_cast<size_t>(gridDim.x) * kRsThreads;
+  const size_t n4 = n / 4;
+  const u32x4 *s4 = reinterpret_cast<const u32x4 *>(tmp);
+  u32x4 *d4 = reinterpret_cast<u32x4 *>(keys);
+  for (size_t i = static_cast<size_t>(blockIdx.x) * kRsThreads + threadIdx.x; i < n4; i += stride)
+    d4[i] = s4[i];
+  if (blockIdx.x == 0 && threadIdx.x < (n & 3)) keys[n4 * 4 + threadIdx.x] = tmp[n4 * 4 + threadIdx.x];
 }
 
 // both columns tmp -> result when an odd number of passes ran; argsort with no executed pass: vals = 0..n-1
@@ -1231,9 +1086,16 @@ __global__ __launch_bounds__(kRsThreads) void rsp_finalize_kernel(unsigned *__re
   }
 }
 
+// the key-value sort's second column; a keys-only sort passes none
+struct RsValues {
+  unsigned *vals, *vtmp;
+  unsigned row_ids;  // argsort: the values are made on the device, `vals` is written only
+};
+
+// Both sorts: `v` decides the kernel at the three launches that move data, every other launch is the same.
 template <int BITS>
-int radix_sort_pairs_impl(unsigned *keys, unsigned *vals, unsigned *tmp, unsigned *vtmp, size_t n, unsigned xor_mask,
-                          unsigned row_ids, void *workspace, hipStream_t s, const DeviceInfo &dev) {
+int radix_sort_impl(unsigned *keys, unsigned *tmp, const RsValues *v, size_t n, unsigned xor_mask, void *workspace,
+                    hipStream_t s, const DeviceInfo &dev) {
   constexpr int kPasses = 32 / BITS;
   constexpr int kRadix = 1 << BITS;
   const RsGeometry g = rs_geometry(n, BITS);
@@ -1244,18 +1106,23 @@ int radix_sort_pairs_impl(unsigned *keys, unsigned *vals, unsigned *tmp, unsigne
   unsigned *counts = reinterpret_cast<unsigned *>(base + kRsCountsOff);
 
   const bool arank = rank_by_lds_atomics();
-  if (n <= static_cast<size_t>(kRsTile)) {
+  const auto single_keys = arank ? rs_single_tile_kernel<BITS, true> : rs_single_tile_kernel<BITS, false>;
+  const auto single_pairs = arank ? rsp_single_tile_kernel<BITS, true> : rsp_single_tile_kernel<BITS, false>;
+  const auto scatter_keys = arank ? rs_chunk_scatter_kernel<BITS, true> : rs_chunk_scatter_kernel<BITS, false>;
+  const auto scatter_pairs = arank ? rsp_chunk_scatter_kernel<BITS, true> : rsp_chunk_scatter_kernel<BITS, false>;
+  const unsigned inject = rank_fault_injection();
+  if (n <= static_cast<size_t>(kRsTile)) {  // one tile: one workgroup, one launch (+ the status word)
     const hipError_t e0 = fill_async(workspace, 0, kWsHeader, s);
     if (e0 != hipSuccess) return static_cast<int>(e0);
-    if (arank)
-      hipLaunchKernelGGL((rsp_single_tile_kernel<BITS, true>), dim3(1), dim3(kRsThreads), 0, s, keys, vals,
-                         static_cast<unsigned>(n), xor_mask, row_ids, &hdr->status);
+    if (v)
+      hipLaunchKernelGGL(single_pairs, dim3(1), dim3(kRsThreads), 0, s, keys, v->vals, static_cast<unsigned>(n), xor_mask,
+                         v->row_ids, &hdr->status);
     else
-      hipLaunchKernelGGL((rsp_single_tile_kernel<BITS, false>), dim3(1), dim3(kRsThreads), 0, s, keys, vals,
-                         static_cast<unsigned>(n), xor_mask, row_ids, &hdr->status);
+      hipLaunchKernelGGL(single_keys, dim3(1), dim3(kRsThreads), 0, s, keys, static_cast<unsigned>(n), xor_mask,
+                         &hdr->status, inject);
     return launch_status();
   }
-  hipError_t e = fill_async(workspace, 0, kRsCountsOff, s);
+  hipError_t e = fill_async(workspace, 0, kRsCountsOff, s);  // header + totals (+ bases)
   if (e != hipSuccess) return static_cast<int>(e);
 
   const size_t want = (n / 4 + kRsThreads - 1) / kRsThreads;
@@ -1263,52 +1130,54 @@ int radix_sort_pairs_impl(unsigned *keys, unsigned *vals, unsigned *tmp, unsigne
   const unsigned hgrid = static_cast<unsigned>(want < cap ? (want ? want : 1) : cap);
   const size_t hist_groups = (g.chunks + rs_hist_cpw<BITS>() - 1) / rs_hist_cpw<BITS>();
   const unsigned hist_grid = static_cast<unsigned>(hist_groups < cap ? hist_groups : cap);
-  hipLaunchKernelGGL((rs_histogram_kernel<BITS>), dim3(hist_grid), dim3(kRsThreads), 0, s, keys, n, xor_mask, totals,
-                     counts, g.tiles_per_chunk, g.chunks);
+  hipLaunchKernelGGL((rs_histogram_kernel<BITS>), dim3(hist_grid), dim3(kRsThreads), 0, s, keys, n,
+                     xor_mask, totals, counts, g.tiles_per_chunk, g.chunks);
   hipLaunchKernelGGL((rs_plan_kernel<BITS>), dim3(1), dim3(kRsThreads), 0, s, n, hdr, totals, bases);
   const unsigned cgrid = static_cast<unsigned>(g.chunks);
   const bool fused_scan = g.chunks <= kRsFusedScanChunks;
   for (int p = 0; p < kPasses; ++p) {
-    if (p > 0)
-      hipLaunchKernelGGL((rs_chunk_hist_kernel<BITS>), dim3((cgrid + rs_hist_cpw<BITS>() - 1) / rs_hist_cpw<BITS>()),
-                         dim3(kRsThreads), 0, s, keys, tmp, n, p, xor_mask, hdr, counts, g.tiles_per_chunk, g.chunks);
+    if (p > 0)  // pass 0's chunk counts came with the up-front histogram
+      hipLaunchKernelGGL((rs_chunk_hist_kernel<BITS>), dim3((cgrid + rs_hist_cpw<BITS>() - 1) / rs_hist_cpw<BITS>()), dim3(kRsThreads), 0, s, keys, tmp, n, p, xor_mask,
+                         hdr, counts, g.tiles_per_chunk, g.chunks);
     if (!fused_scan)
       hipLaunchKernelGGL((rs_chunk_scan_kernel<BITS>), dim3(kRadix), dim3(kRsThreads), 0, s, p, hdr, bases, counts,
                          g.chunks);
     const unsigned *fused_bases = fused_scan ? bases : static_cast<const unsigned *>(nullptr);
-    if (arank)
-      hipLaunchKernelGGL((rsp_chunk_scatter_kernel<BITS, true>), dim3((cgrid + 7) / 8 * 8), dim3(kRsThreads), 0, s, keys,
-                         vals, tmp, vtmp, n, p, xor_mask, row_ids, hdr, counts, fused_bases, g.tiles_per_chunk, g.chunks);
+    if (v)
+      hipLaunchKernelGGL(scatter_pairs, dim3((cgrid + 7) / 8 * 8), dim3(kRsThreads), 0, s, keys, v->vals, tmp, v->vtmp, n, p,
+                         xor_mask, v->row_ids, hdr, counts, fused_bases, g.tiles_per_chunk, g.chunks);
     else
-      hipLaunchKernelGGL((rsp_chunk_scatter_kernel<BITS, false>), dim3((cgrid + 7) / 8 * 8), dim3(kRsThreads), 0, s, keys,
-                         vals, tmp, vtmp, n, p, xor_mask, row_ids, hdr, counts, fused_bases, g.tiles_per_chunk, g.chunks);
+      hipLaunchKernelGGL(scatter_keys, dim3((cgrid + 7) / 8 * 8), dim3(kRsThreads), 0, s, keys, tmp, n, p, xor_mask, hdr,
+                         counts, fused_bases, inject, g.tiles_per_chunk, g.chunks);
   }
-  hipLaunchKernelGGL(rsp_finalize_kernel, dim3(hgrid), dim3(kRsThreads), 0, s, keys, vals, tmp, vtmp, n, row_ids, kPasses,
-                     hdr);
+  if (v)
+    hipLaunchKernelGGL(rsp_finalize_kernel, dim3(hgrid), dim3(kRsThreads), 0, s, keys, v->vals, tmp, v->vtmp, n, v->row_ids,
+                       kPasses, hdr);
+  else
+    hipLaunchKernelGGL(rs_finalize_kernel, dim3(hgrid), dim3(kRsThreads), 0, s, keys, tmp, n, hdr);
   return launch_status();
 }
 
-int radix_sort_pairs_entry(unsigned *keys, unsigned *vals, unsigned *tmp, unsigned *vtmp, size_t n, int radix_bits,
-                           unsigned xor_mask, int vals_are_row_ids, void *workspace, size_t workspace_bytes,
-                           dbhip_stream_t stream) {
+int radix_sort_entry(unsigned *keys, unsigned *tmp, const RsValues *v, size_t n, int radix_bits, unsigned xor_mask,
+                     void *workspace, size_t workspace_bytes, dbhip_stream_t stream) {
   if (radix_bits != 4 && radix_bits != 8) return DBHIP_EINVAL;
   if (n >= (1ull << 32)) return DBHIP_EINVAL;  // 32-bit offsets and row ids
-  if (n == 0) {
+  if (n == 0) {  // nothing to sort; a workspace that was passed still gets a clean status word
     if (workspace && ws_ok(workspace, workspace_bytes, kWsHeader))
       return static_cast<int>(fill_async(workspace, 0, kWsHeader, as_stream(stream)));
     return DBHIP_OK;
   }
-  if (!keys || !vals || !tmp || !vtmp) return DBHIP_EINVAL;
-  if ((reinterpret_cast<uintptr_t>(keys) | reinterpret_cast<uintptr_t>(vals) | reinterpret_cast<uintptr_t>(tmp) |
-       reinterpret_cast<uintptr_t>(vtmp)) & 15u)
-    return DBHIP_EINVAL;  // dbhip.h: 16-byte aligned
-  if (!ws_ok(workspace, workspace_bytes, dbhip_radix_sort_pairs_workspace_bytes(n, radix_bits))) return DBHIP_EWORKSPACE;
+  if (!keys || !tmp || (v && (!v->vals || !v->vtmp))) return DBHIP_EINVAL;
+  uintptr_t addr = reinterpret_cast<uintptr_t>(keys) | reinterpret_cast<uintptr_t>(tmp);
+  if (v) addr |= reinterpret_cast<uintptr_t>(v->vals) | reinterpret_cast<uintptr_t>(v->vtmp);
+  if (addr & 15u) return DBHIP_EINVAL;  // dbhip.h: 16-byte aligned
+  if (!ws_ok(workspace, workspace_bytes, dbhip_radix_sort_workspace_bytes(n, radix_bits)))  // the same for both sorts
+    return DBHIP_EWORKSPACE;
   const DeviceInfo &dev = current_device_info();
   if (!dev.ok) return DBHIP_ENODEVICE;
-  const unsigned row_ids = vals_are_row_ids ? 1u : 0u;
   return radix_bits == 8
-             ? radix_sort_pairs_impl<8>(keys, vals, tmp, vtmp, n, xor_mask, row_ids, workspace, as_stream(stream), dev)
-             : radix_sort_pairs_impl<4>(keys, vals, tmp, vtmp, n, xor_mask, row_ids, workspace, as_stream(stream), dev);
+             ? radix_sort_impl<8>(keys, tmp, v, n, xor_mask, workspace, as_stream(stream), dev)
+             : radix_sort_impl<4>(keys, tmp, v, n, xor_mask, workspace, as_stream(stream), dev);
 }
 
 }  // namespace
@@ -1355,13 +1224,13 @@ extern "C" int dbhip_radix_sort_prepare(dbhip_stream_t stream) {
 
 extern "C" int dbhip_radix_sort_u32(uint32_t *keys, uint32_t *tmp, size_t n, int radix_bits,
                                     void *workspace, size_t workspace_bytes, dbhip_stream_t stream) {
-  return radix_sort_entry(keys, tmp, n, radix_bits, 0u, workspace, workspace_bytes, stream);
+  return radix_sort_entry(keys, tmp, nullptr, n, radix_bits, 0u, workspace, workspace_bytes, stream);
 }
 
 extern "C" int dbhip_radix_sort_i32(int32_t *keys, int32_t *tmp, size_t n, int radix_bits,
                                     void *workspace, size_t workspace_bytes, dbhip_stream_t stream) {
   // signed order = unsigned order with the sign bit flipped (applied on the fly, keys unchanged)
-  return radix_sort_entry(reinterpret_cast<unsigned *>(keys), reinterpret_cast<unsigned *>(tmp), n,
+  return radix_sort_entry(reinterpret_cast<unsigned *>(keys), reinterpret_cast<unsigned *>(tmp), nullptr, n,
                           radix_bits, 0x80000000u, workspace, workspace_bytes, stream);
 }
 
@@ -1373,13 +1242,14 @@ extern "C" size_t dbhip_radix_sort_pairs_workspace_bytes(size_t n, int radix_bit
 extern "C" int dbhip_radix_sort_pairs_u32(uint32_t *keys, uint32_t *vals, uint32_t *tmp_keys, uint32_t *tmp_vals, size_t n,
                                           int radix_bits, int vals_are_row_ids, void *workspace, size_t workspace_bytes,
                                           dbhip_stream_t stream) {
-  return radix_sort_pairs_entry(keys, vals, tmp_keys, tmp_vals, n, radix_bits, 0u, vals_are_row_ids, workspace,
-                                workspace_bytes, stream);
+  const RsValues v{vals, tmp_vals, vals_are_row_ids ? 1u : 0u};
+  return radix_sort_entry(keys, tmp_keys, &v, n, radix_bits, 0u, workspace, workspace_bytes, stream);
 }
 
 extern "C" int dbhip_radix_sort_pairs_i32(int32_t *keys, uint32_t *vals, int32_t *tmp_keys, uint32_t *tmp_vals, size_t n,
                                           int radix_bits, int vals_are_row_ids, void *workspace, size_t workspace_bytes,
                                           dbhip_stream_t stream) {
-  return radix_sort_pairs_entry(reinterpret_cast<unsigned *>(keys), vals, reinterpret_cast<unsigned *>(tmp_keys), tmp_vals,
-                                n, radix_bits, 0x80000000u, vals_are_row_ids, workspace, workspace_bytes, stream);
+  const RsValues v{vals, tmp_vals, vals_are_row_ids ? 1u : 0u};
+  return radix_sort_entry(reinterpret_cast<unsigned *>(keys), reinterpret_cast<unsigned *>(tmp_keys), &v, n, radix_bits,
+                          0x80000000u, workspace, workspace_bytes, stream);
 }

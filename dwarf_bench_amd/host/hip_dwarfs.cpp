@@ -332,10 +332,7 @@ void DPLScanHip::_run(const size_t n, Meter &meter) { run_scan("DPLScanHip", n, 
 // =====================================================================================================
 void RadixHip::_run(const size_t n, Meter &meter) {
   const RunOptions &opts = meter.opts();
-  const int bits = [] {
-    const char *e = std::getenv("DWARF_BENCH_RADIX_BITS");
-    return (e && std::atoi(e) == 4) ? 4 : 8;
-  }();
+  const int bits = digit_bits();
   DevBuf<int32_t> src(n), keys(n), tmp(n);
   const size_t ws_bytes = dbhip_radix_sort_workspace_bytes(n, bits);
   DevBuf<unsigned char> ws(ws_bytes);
@@ -374,6 +371,10 @@ void RadixHip::_run(const size_t n, Meter &meter) {
     record(meter, n, std::move(result), ok, "incorrect results");  // sort/radix.cpp:61
   }
 }
+int RadixHip::digit_bits() {
+  const char *e = std::getenv("DWARF_BENCH_RADIX_BITS");
+  return (e && std::atoi(e) == 4) ? 4 : 8;
+}
 void RadixHip::init(const RunOptions &opts) {
   HipDwarf::init(opts);
   // optional calibration, outside every timed region: pins the sort's ranking to what the device-side self-test of
@@ -387,10 +388,7 @@ void RadixHip::init(const RunOptions &opts) {
 void RadixPairsHip::_run(const size_t n, Meter &meter) {
   const RunOptions &opts = meter.opts();
   if (n >= (static_cast<size_t>(1) << 32)) fail("RadixPairsHip: fewer than 2^32 rows");
-  const int bits = [] {
-    const char *e = std::getenv("DWARF_BENCH_RADIX_BITS");
-    return (e && std::atoi(e) == 4) ? 4 : 8;
-  }();
+  const int bits = digit_bits();
   DevBuf<int32_t> src(n), keys(n), tmp(n);
   DevBuf<uint32_t> perm(n), tmp_perm(n);
   const size_t ws_bytes = dbhip_radix_sort_pairs_workspace_bytes(n, bits);
@@ -432,10 +430,6 @@ void RadixPairsHip::_run(const size_t n, Meter &meter) {
     }
     record(meter, n, std::move(result), ok, "incorrect results");
   }
-}
-void RadixPairsHip::init(const RunOptions &opts) {
-  HipDwarf::init(opts);
-  (void)dbhip_radix_sort_prepare(nullptr);  // as RadixHip::init
 }
 
 // =====================================================================================================

@@ -31,9 +31,10 @@ struct DPLScanHip : HipDwarf {
   void _run(size_t buf_size, Meter &meter) override;
 };
 struct RadixHip : HipDwarf {
-  RadixHip() : HipDwarf("RadixHip") {}
+  explicit RadixHip(const std::string &name = "RadixHip") : HipDwarf(name) {}
   void init(const RunOptions &opts) override;  // HipDwarf::init, then dbhip_radix_sort_prepare
   void _run(size_t buf_size, Meter &meter) override;
+  static int digit_bits();  // DWARF_BENCH_RADIX_BITS: 4, anything else the tuned 8
 };
 struct GroupByHip : HipDwarf {
   GroupByHip() : HipDwarf("GroupByHip") {}
@@ -102,9 +103,8 @@ struct GroupByHashHip : HipDwarf {  // groupby/groupby.cpp:58-93 (the hash table
 };
 // the argsort (key-value radix sort with row ids as values): registered by populate_sort_pairs_registry() only (the
 // dwarf_bench_sort_pairs CLI); no reference counterpart, the reference sorts keys only
-struct RadixPairsHip : HipDwarf {
-  RadixPairsHip() : HipDwarf("RadixPairsHip") {}
-  void init(const RunOptions &opts) override;  // HipDwarf::init, then dbhip_radix_sort_prepare
+struct RadixPairsHip : RadixHip {  // RadixHip's init and digit width
+  RadixPairsHip() : RadixHip("RadixPairsHip") {}
   void _run(size_t buf_size, Meter &meter) override;
 };
 // the join result as a table of (build row, probe row) pairs (radix join + dbhip_join_pairs_u32): registered by

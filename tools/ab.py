@@ -42,7 +42,7 @@ the contract numbers come from bench.py.
                   (median of 9), each with the tail hint on and off (DBHIP_SLAB_HINT) and the first CAS at the lowest or at a
                   spread empty slot (DBHIP_SLAB_SPREAD 0 / default / 1); every build checked
   xscan [lg]      exclusive scan of 2^lg uint32, aligned (one launch) and offset by one element (three launches)
-  graph           direct launches vs hipGraph replay of sort and join at 2^14..2^20 rows (host wall clock)
+  graph [lg]      direct launches vs hipGraph replay of sort and join at 2^14..2^20 rows, or 2^lg alone (host wall clock)
   launch-join [lg] / launch-sort [lg] / launch-all
                   a few untimed calls and nothing else: the program to put behind `rocprofv3 --kernel-trace --stats` or
                   `--pmc` (tools/pmc_kernel_counters.sh); tools/prof_show.py prints the tables
@@ -819,7 +819,7 @@ def xscan(lg):
               f"{'ok' if ok else 'WRONG'}", flush=True)
 
 
-def graph(_):
+def graph(only):
     import time
 
     def wall(fn, iters=200):
@@ -844,7 +844,7 @@ def graph(_):
             fn()
         return g
 
-    for lg in (14, 16, 18, 20):
+    for lg in ([only] if only else (14, 16, 18, 20)):
         n = 1 << lg
         keys = ops.gen_uniform_u32(n, 1, 0, 2**32 - 1)
         plan = ops.RadixSort(n, 8)

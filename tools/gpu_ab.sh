@@ -17,6 +17,8 @@ case "$what" in
   time)
     for round in 1 2; do for v in "$@"; do
       DBHIP_LIB="$(libof "$v")" timeout -k 10 300 python tools/ab.py "${args[@]}" 2>&1 | grep -v amdgpu.ids
+      rc=${PIPESTATUS[0]}  # a run that failed or hung ends the comparison: nothing more is started on that card
+      [ "$rc" -eq 0 ] || { echo "tools/ab.py ${args[*]} ($v) ended with status $rc: stopping" >&2; exit "$rc"; }
     done; done ;;
   kernels)
     for v in "$@"; do
