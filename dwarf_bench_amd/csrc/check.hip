@@ -10,12 +10,31 @@
 //                                    of src under the filter equals the fingerprint of out[0..out_size).
 //   dbhip_check_sorted_u32           number of descents key[i] > key[i+1] + a commutative multiset fingerprint
 //                                    (sum of mix64(key), sum of keys): sorted and a permutation of the input.
-//   dbhip_check_weighted_sum_u32     sum vals[i] * w(keys[i]) mod 2^32 for two weight functions: a group-by result
-//                                    is right iff the weighted sum over (g, out[g]) equals the one over the rows.
+//   dbhip_check_weighted_sum_u32     sum vals[i] * w(keys[i]) mod 2^32 for two odd weight functions, compared between
+//                                    (g, out[g]) and the rows.  A right group-by result always agrees.  An error confined
+//                                    to one group is always caught (an odd weight is a bijection mod 2^32).  An error
+//                                    spread over several groups is caught unless both weighted differences vanish: a
+//                                    value d moved between two groups shows as d * (w(g1) - w(g2)), the difference of two
+//                                    odd weights is even, so a move of 2^31 is never seen and one with t trailing zero
+//                                    bits loses t + 1 bits in each word (miss rates: include/dbhip.h).
 //   dbhip_check_permutation_u32      ids[] is a permutation of 0..n-1 (bitmap + atomicOr).
 //   dbhip_check_join_u32             per probe row: count == (upper - lower bound of the key in the SORTED build
 //                                    column), the id range is inside the id buffer and its first / last / one
-//                                    pseudo-random id carry the key.
+//                                    pseudo-random id carry the key.  Three ids per row leave most of a long range unread
+//                                    (36 % of the probed id positions on the benchmark's keys), so a second pass over the
+//                                    id buffer counts the neighbours ids[j], ids[j+1] that carry different keys, less the
+//                                    neighbours of the sorted build column that differ.  The bad rows stand in the low
+//                                    half of result[0], that difference mod 2^32 in the high half: neither can cancel the
+//                                    other, so the word is 0 only if no row is bad, whatever ids holds.  With ids a
+//                                    permutation of the build rows the difference is 0 iff every key is ONE run of ids,
+//                                    and a range of the key's multiplicity whose first and last id carry the key then is
+//                                    that run: every id of every probed range is right.  JoinOmnisciHip and JoinPairsHip
+//                                    run dbhip_check_permutation_u32 on ids beside this check and get that statement;
+//                                    ProbeHip and the partitioned join do not, and get the per-row checks plus "as many
+//                                    key runs as keys".  out_pos of a row without a match is not looked at.  Without
+//                                    probe rows nothing is launched and both words are 0.  A build that dropped rows
+//                                    (0xFFFFFFFF as a build key, DBHIP_DEV_KEY_RANGE) leaves ids no permutation: the run
+//                                    count means nothing there.
 //   dbhip_check_ujoin_u32            per probe row of the unique-key join: (key, build payload, probe payload) or
 //                                    the three sentinels, the build side found by binary search.
 //   dbhip_check_distinct_u32         number of i with s[i] >= s[i+1] over a copy s of the keys sorted by
@@ -271,7 +290,22 @@ __global__ __launch_bounds__(kCkThreads) void join_check_kernel(
     }
     if (!ok) ++bad;
   }
-  block_add_u64(bad, result + 0);
+  // every key one run of ids: neighbours of ids that carry different keys, less the neighbours of the sorted build column
+  // that differ.  With ids a permutation the first count is at least the second, and equal iff no key is split; an id
+  // that names no row differs from every neighbour.  The difference goes into the HIGH half of the word (wrap-around
+  // sums: the blocks add up to bad + ((runs - distinct) mod 2^32) * 2^32), so it cannot cancel a bad row whatever ids holds.
+  unsigned long long runs = 0;
+  for (size_t j = static_cast<size_t>(blockIdx.x) * kCkThreads + threadIdx.x; j + 1 < n_build; j += stride) {
+    const unsigned a = ids[j], b = ids[j + 1];
+    bool differ;
+    if (build_keys)
+      differ = a >= n_build || b >= n_build || build_keys[a] != build_keys[b];
+    else
+      differ = gen_value(gen, a) != gen_value(gen, b);
+    runs += differ ? 1ull : 0ull;
+    runs -= sorted_build[j] != sorted_build[j + 1] ? 1ull : 0ull;
+  }
+  block_add_u64(bad + (runs << 32), result + 0);
   block_add_u64(total, result + 1);
 }
 
@@ -426,6 +460,7 @@ extern "C" int dbhip_check_join_u32(const uint32_t *sorted_build_keys, size_t n_
   if (!result || (n_probe && (!probe_keys || !out_pos || !out_count)) || (n_build && (!sorted_build_keys || !ids)))
     return DBHIP_EINVAL;
   if (!build_keys && gen_hi < gen_lo) return DBHIP_EINVAL;
+  if (n_probe >= (1ull << 32) || n_build > (1ull << 32)) return DBHIP_EINVAL;  // both halves of result[0] hold their count
   const DeviceInfo &dev = current_device_info();
   if (!dev.ok) return DBHIP_ENODEVICE;
   hipStream_t s = as_stream(stream);
@@ -433,8 +468,8 @@ extern "C" int dbhip_check_join_u32(const uint32_t *sorted_build_keys, size_t n_
   if (e != hipSuccess) return static_cast<int>(e);
   if (n_probe == 0) return DBHIP_OK;
   const GenSpec gen{gen_seed, static_cast<unsigned long long>(gen_hi) - gen_lo + 1, gen_lo};
-  hipLaunchKernelGGL(join_check_kernel, dim3(ck_grid(n_probe, dev)), dim3(kCkThreads), 0, s, sorted_build_keys, n_build,
-                     probe_keys, n_probe, out_pos, out_count, ids, build_keys, gen,
+  hipLaunchKernelGGL(join_check_kernel, dim3(ck_grid(n_probe > n_build ? n_probe : n_build, dev)), dim3(kCkThreads), 0, s,
+                     sorted_build_keys, n_build, probe_keys, n_probe, out_pos, out_count, ids, build_keys, gen,
                      reinterpret_cast<unsigned long long *>(result));
   return launch_status();
 }

@@ -476,12 +476,28 @@ int dbhip_exclusive_scan_u32(const uint32_t *src, size_t n, uint32_t init, uint3
  *                       pair computed over out[0..out_size) (every element of out passes the same filter).
  *   sorted_u32          result[0] = number of i with key[i] > key[i+1] (signed_order != 0: as int32),
  *                       result[1], result[2] = commutative multiset fingerprint (compare with the input's).
- *   weighted_sum_u32    result[0], result[1] = sum vals[i] * w(keys[i]) mod 2^32 for two weight functions;
- *                       keys == NULL means keys[i] = i (the dense group-by output).
+ *   weighted_sum_u32    result[0], result[1] = sum vals[i] * w(keys[i]) mod 2^32 for two weight functions with odd
+ *                       weights; keys == NULL means keys[i] = i (the dense group-by output).  Compared between a group-by
+ *                       output and its rows: a right output always agrees, an error confined to one group never does
+ *                       (an odd weight is a bijection mod 2^32), and an error spread over several groups is caught unless
+ *                       both weighted differences vanish.  A value d moved from one group to another shows as
+ *                       d * (w(g1) - w(g2)) with an even second factor: d = 2^31 is never seen, and a random multiple d of
+ *                       2^t goes unseen in 0.8 % (t = 24), 12.5 % (t = 28), 50 % (t = 30) of moves among 1000 groups; a
+ *                       random d (t = 0) in none of 200 000 ("What the device-side validators cannot see").
  *   permutation_u32     result[0] = number of entries >= n or seen before (0 iff ids is a permutation of 0..n-1).
  *   join_u32            sorted_build_keys = the build column sorted ascending.  result[0] = number of probe rows
  *                       whose count differs from the key's multiplicity in the build column, whose id range
- *                       leaves the id buffer, or whose first / last / one pseudo-random id does not carry the key;
+ *                       leaves the id buffer, or whose first / last / one id at mix64(7, row) % count does not carry the
+ *                       key (n_probe < 2^32, so the count fills the LOW 32 bits); in the HIGH 32 bits, mod 2^32, the
+ *                       number of j < n_build - 1 where ids[j] and ids[j+1] carry different keys (an id that names no row
+ *                       differs from all) less the number of j where sorted_build_keys[j] != [j+1].  The halves cannot
+ *                       cancel: result[0] == 0 only if no row is bad, whatever ids holds.  The three ids alone leave 36 %
+ *                       of the probed id positions of the benchmark's join unread; with ids a permutation of the build
+ *                       rows (permutation_u32 on ids, which JoinOmnisciHip and JoinPairsHip run beside this check; ProbeHip
+ *                       and the partitioned join do not) the high half is 0 iff every key is one run of ids, which makes
+ *                       every id of every probed range right.  It means nothing after a build that dropped rows
+ *                       (0xFFFFFFFF build keys, DBHIP_DEV_KEY_RANGE).  out_pos of a row without a match is not looked at.
+ *                       n_probe == 0: nothing is launched, both words are 0 whatever n_build is.
  *                       result[1] = sum of all counts.  build_keys != NULL: ids are build row indices and the key
  *                       of id is build_keys[id]; build_keys == NULL: ids are global row ids of a generated column
  *                       and the key of id is gen_lo + mix64(gen_seed, id) % (gen_hi - gen_lo + 1).
@@ -491,10 +507,11 @@ int dbhip_exclusive_scan_u32(const uint32_t *src, size_t n, uint32_t init, uint3
  *   gen_uniform_u32     result[0] = number of i with values[i] != lo + mix64(seed, index_i) % (hi - lo + 1),
  *                       index_i = indices ? indices[i] : first_index + i.
  *   distinct_u32        result[0] = number of i with s[i] >= s[i+1] over a sorted copy s of keys (dbhip_radix_sort_u32 in
- *                       the workspace): 0 iff the keys are distinct.  A group-by output (dbhip_groupby_hash_u32) is right
- *                       iff its keys are distinct, weighted_sum over (out_keys, out_sums) equals weighted_sum over
- *                       (keys, vals), the same holds for (out_keys, out_counts) against a column of ones, and the counts
- *                       sum to n.
+ *                       the workspace): 0 iff the keys are distinct.  A group-by output (dbhip_groupby_hash_u32) is taken
+ *                       as right when its keys are distinct, weighted_sum over (out_keys, out_sums) equals weighted_sum
+ *                       over (keys, vals), the same holds for (out_keys, out_counts) against a column of ones, and the
+ *                       counts sum to n: every right output passes, and a wrong one passes only through the gap of
+ *                       weighted_sum_u32 named above.
  *   sorted_pairs_u32    (n < 2^32) result[0] = number of i < n-1 with (keys_out[i], ids_out[i]) >= (keys_out[i+1],
  *                       ids_out[i+1]), compared lexicographically, keys as int32 when signed_order != 0; result[1] =
  *                       number of i with ids_out[i] >= n or keys_in[ids_out[i]] != keys_out[i].  Both zero iff ids_out is

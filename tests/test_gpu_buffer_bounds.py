@@ -45,6 +45,7 @@ import torch
 
 from oracle import pyoracle as po
 from tests import guard_testlib as gt
+from tests import validator_model as vm
 from tests.cuckoo_model import mix64_np, positions_np
 from tests.guard_testlib import FILLS, ptr
 from tests.pjoin_testlib import dest_of, fmix32
@@ -638,24 +639,7 @@ def test_cuckoo_table_stays_inside_its_workspace(size, hash_kind):
 CHECK_SIZES = [0, 1, 65, 100003]
 
 
-def _host_fingerprint(seq):
-    h = 0
-    for x in seq:
-        h = (h * 0x9E3779B97F4A7C15 + (int(np.uint32(x)) + 1)) & M64
-    return [h, len(seq)]
-
-
-def _sum64(a):
-    with np.errstate(over="ignore"):
-        return int(np.sum(a.astype(np.uint64), dtype=np.uint64)) & M64
-
-
-def _weighted(keys, vals):
-    out = []
-    for salt in (0, 0x9E3779B9):
-        wt = fmix32(keys ^ np.uint32(salt)) | np.uint64(1)
-        out.append(_sum64((vals.astype(np.uint64) * wt) & np.uint64(M32)) & M32)
-    return out
+_host_fingerprint, _sum64, _weighted = vm.fingerprint, vm.sum64, vm.weighted_sum  # the validators' numpy model
 
 
 @pytest.mark.parametrize("n", CHECK_SIZES)

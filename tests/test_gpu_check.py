@@ -13,10 +13,10 @@ import pytest
 import torch
 
 from oracle import pyoracle as po
+from tests import validator_model as vm
 
 pytestmark = pytest.mark.gpu
 M64 = (1 << 64) - 1
-FP_MUL = 0x9E3779B97F4A7C15
 
 
 def _dev(a):
@@ -107,10 +107,7 @@ def test_exclusive_scan_feeds_the_omnisci_positions():
 
 # ---------------------------------------------------------------------------------------------------------------
 def _host_fingerprint(seq):
-    h = 0
-    for x in seq:
-        h = (h * FP_MUL + (int(np.uint32(x)) + 1)) & M64
-    return h, len(seq)
+    return tuple(vm.fingerprint(seq))
 
 
 @pytest.mark.parametrize("n", [0, 1, 63, 64, 65, 1000, 16385, 300007])

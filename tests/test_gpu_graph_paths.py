@@ -30,8 +30,8 @@ from tests.graph_testlib import Buffers, Input, run_family, u32
 from tests.guard_testlib import FILLS, i32, i64
 from tests.pjoin_testlib import dest_of, fmix32
 from tests.slab_model import SlabModel
-from tests.test_gpu_buffer_bounds import (_host_fingerprint, _kernel_would_pack, _packed_case, _sample_rows, _sum64,
-                                          _weighted)
+from tests.test_gpu_buffer_bounds import _kernel_would_pack, _packed_case, _sample_rows, _sum64
+from tests.validator_model import fingerprint as _host_fingerprint, weighted_sum as _weighted
 from tests.test_gpu_workspace_reuse import _crowded, _probe, _unique_crowd
 
 pytestmark = pytest.mark.gpu
