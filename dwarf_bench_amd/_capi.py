@@ -91,6 +91,14 @@ SIGNATURES = {
     "dbhip_check_gen_uniform_u32": (_int, [_vp, _vp, _sz, _u64, _u64, _u32, _u32, _vp, _vp]),
 }
 
+# the same for include/dbhip_topk.h (tests/test_topk_host.py checks this pair)
+TOPK_SIGNATURES = {
+    "dbhip_topk_workspace_bytes": (_sz, [_sz, _sz]),
+    "dbhip_topk_u32": (_int, [_vp, _sz, _sz, _int, _int, _vp, _vp, _vp, _sz, _vp]),
+    "dbhip_topk_i32": (_int, [_vp, _sz, _sz, _int, _int, _vp, _vp, _vp, _sz, _vp]),
+    "dbhip_check_topk_u32": (_int, [_vp, _sz, _vp, _vp, _sz, _int, _int, _vp, _vp]),
+}
+
 _lib = None
 
 
@@ -115,7 +123,7 @@ def lib() -> C.CDLL:
         except Exception:  # pragma: no cover - torch is plumbing, the C++ host layer runs without it
             pass
         handle = C.CDLL(str(_LIB_PATH), mode=C.RTLD_GLOBAL)
-        for name, (res, args) in SIGNATURES.items():
+        for name, (res, args) in {**SIGNATURES, **TOPK_SIGNATURES}.items():
             fn = getattr(handle, name)  # AttributeError if the .so does not export the symbol
             fn.restype = res
             fn.argtypes = args

@@ -71,14 +71,15 @@ def build_hip(force: bool = False) -> Path:
     LIB.mkdir(exist_ok=True)
     out = LIB / "libdbhip.so"
     srcs = sorted(CSRC.glob("*.hip"))
-    deps = srcs + sorted(CSRC.glob("*.hpp")) + [ROOT / "include" / "dbhip.h"]
+    headers = sorted(CSRC.glob("*.hpp")) + [ROOT / "include" / "dbhip.h", ROOT / "include" / "dbhip_topk.h"]
+    deps = srcs + headers
     if force or _stale(out, deps):
         objs = []
         odir = LIB / "obj"
         odir.mkdir(exist_ok=True)
         for s in srcs:
             o = odir / (s.stem + ".o")
-            if force or _stale(o, [s] + sorted(CSRC.glob("*.hpp")) + [ROOT / "include" / "dbhip.h"]):
+            if force or _stale(o, [s] + headers):
                 _run([_hipcc(), f"--offload-arch={ARCH}", "-O3", "-std=c++17", "-fPIC", "-fno-gpu-rdc",
                       "-Wall", "-Wno-unused-function"] + os.environ.get("DBHIP_EXTRA_FLAGS", "").split()
                      + ["-c", s, "-o", o])

@@ -33,6 +33,7 @@
 #include <unordered_map>
 
 #include "../../include/dbhip.h"
+#include "../../include/dbhip_topk.h"
 #include "errors.hpp"
 
 using namespace dbench_errors;
@@ -427,6 +428,62 @@ void RadixPairsHip::_run(const size_t n, Meter &meter) {
             "dbhip_check_sorted_pairs_u32");
       const auto g = chk.get();
       ok = g[0] == 0 && g[1] == 0;
+    }
+    record(meter, n, std::move(result), ok, "incorrect results");
+  }
+}
+
+// =====================================================================================================
+// TopKHip — ORDER BY key LIMIT k (dbhip_topk_i32, sorted output): a uniform full-range column, the timed region is one
+// call that returns keys and row ids of the first k rows.  No reference counterpart.
+void TopKHip::_run(const size_t n, Meter &meter) {
+  const RunOptions &opts = meter.opts();
+  if (n >= (static_cast<size_t>(1) << 32)) fail("TopKHip: fewer than 2^32 rows");
+  const char *ek = std::getenv("DWARF_BENCH_TOPK_K");
+  const size_t k = std::min<size_t>(ek ? static_cast<size_t>(std::strtoull(ek, nullptr, 10)) : 1024, n);
+  const int largest = env_flag("DWARF_BENCH_TOPK_LARGEST") ? 1 : 0;
+  DevBuf<int32_t> src(n), out_keys(k);
+  DevBuf<uint32_t> out_rows(k);
+  const size_t ws_bytes = dbhip_topk_workspace_bytes(n, k);
+  DevBuf<unsigned char> ws(ws_bytes);
+  db_ok(dbhip_gen_uniform_u32(reinterpret_cast<uint32_t *>(src.get()), n, 42, 0, 0, 0xFFFFFFFFu, nullptr), "gen");
+  hip_ok(hipDeviceSynchronize(), "sync");
+  const bool host_check = n <= validate_limit();
+  std::vector<int32_t> expected_keys;
+  std::vector<uint32_t> expected_rows;
+  CheckWords chk;
+  if (host_check) {  // the first k of the (key, row) pairs, as one number each: better key first, equal keys by row
+    const std::vector<int32_t> h = src.to_host(n);
+    const uint32_t mask = largest ? 0x7FFFFFFFu : 0x80000000u;  // signed order as unsigned order of key ^ mask
+    std::vector<uint64_t> pairs(n);
+    for (size_t i = 0; i < n; ++i) pairs[i] = (static_cast<uint64_t>(static_cast<uint32_t>(h[i]) ^ mask) << 32) | i;
+    if (k < n) std::nth_element(pairs.begin(), pairs.begin() + k, pairs.end());
+    std::sort(pairs.begin(), pairs.begin() + k);
+    expected_keys.resize(k);
+    expected_rows.resize(k);
+    for (size_t i = 0; i < k; ++i) {
+      expected_rows[i] = static_cast<uint32_t>(pairs[i]);
+      expected_keys[i] = h[expected_rows[i]];
+    }
+  }
+  Events ev;
+  for (size_t it = 0; it < opts.iterations; ++it) {
+    auto result = std::make_unique<Result>();
+    time_launch(*result, ev, [&] {
+      db_ok(dbhip_topk_i32(src.get(), n, k, largest, 1, out_keys.get(), out_rows.get(), ws.get(), ws_bytes, nullptr),
+            "dbhip_topk_i32");
+    });
+    check_status(ws.get(), "TopKHip");
+    if (inject_fault() && k) poke_xor(out_rows.get() + k / 2, 1u);  // one row id
+    bool ok;
+    if (host_check) {
+      ok = out_keys.to_host(k) == expected_keys && out_rows.to_host(k) == expected_rows;
+    } else {  // include/dbhip_topk.h: no wrong entry, and exactly k - 1 rows in front of the last one
+      db_ok(dbhip_check_topk_u32(reinterpret_cast<uint32_t *>(src.get()), n, reinterpret_cast<uint32_t *>(out_keys.get()),
+                                 out_rows.get(), k, largest, 1, chk.dev(), nullptr),
+            "dbhip_check_topk_u32");
+      const auto g = chk.get();
+      ok = g[0] == 0 && g[1] == (k ? k - 1 : 0);
     }
     record(meter, n, std::move(result), ok, "incorrect results");
   }

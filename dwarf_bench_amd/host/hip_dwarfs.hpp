@@ -114,3 +114,10 @@ struct JoinPairsHip : HipDwarf {
   JoinPairsHip() : HipDwarf("JoinPairsHip") {}
   void _run(size_t buf_size, Meter &meter) override;
 };
+// ORDER BY key LIMIT k (dbhip_topk_i32, include/dbhip_topk.h): registered by populate_topk_registry() only (the
+// dwarf_bench_topk CLI); no reference counterpart.  k: DWARF_BENCH_TOPK_K (default 1024, clipped to the row count),
+// DWARF_BENCH_TOPK_LARGEST=1: the largest keys
+struct TopKHip : HipDwarf {
+  TopKHip() : HipDwarf("TopKHip") {}
+  void _run(size_t buf_size, Meter &meter) override;
+};

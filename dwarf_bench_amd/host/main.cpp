@@ -9,7 +9,8 @@
 // `dwarf_bench_groupby_hash`, the default set plus GroupByHashHip (populate_groupby_hash_registry), and with
 // -DEXPERIMENTAL_SORT_PAIRS `dwarf_bench_sort_pairs`, the default set plus RadixPairsHip (populate_sort_pairs_registry),
 // and with -DEXPERIMENTAL_JOIN_PAIRS `dwarf_bench_join_pairs`, the default set plus JoinPairsHip
-// (populate_join_pairs_registry).
+// (populate_join_pairs_registry), and with -DEXPERIMENTAL_TOPK `dwarf_bench_topk`, the default set plus TopKHip
+// (populate_topk_registry).
 #include <iostream>
 #include <memory>
 #include <sstream>
@@ -53,6 +54,9 @@ int main(int argc, char *argv[]) {
 #endif
 #ifdef EXPERIMENTAL_JOIN_PAIRS
   populate_join_pairs_registry();  // dwarf_bench_join_pairs
+#endif
+#ifdef EXPERIMENTAL_TOPK
+  populate_topk_registry();  // dwarf_bench_topk
 #endif
   Registry *registry = Registry::instance();
 

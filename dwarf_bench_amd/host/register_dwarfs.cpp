@@ -70,3 +70,11 @@ void populate_join_pairs_registry() {
   Registry::instance()->registerd(new JoinPairsHip());
 #endif
 }
+
+// the top-k (dbhip_topk_i32): only the dwarf_bench_topk CLI (main.cpp built with -DEXPERIMENTAL_TOPK) calls this, so the
+// lists of the other six CLIs stay as they are
+void populate_topk_registry() {
+#ifdef HIP_ENABLED
+  Registry::instance()->registerd(new TopKHip());
+#endif
+}

@@ -214,6 +214,70 @@ def radix_argsort_(keys: torch.Tensor, signed: bool = False, radix_bits: int = 8
 
 
 # ---------------------------------------------------------------------------------------------
+# top-k: ORDER BY key LIMIT k (include/dbhip_topk.h)
+# ---------------------------------------------------------------------------------------------
+TOPK_SEGMENT_ROWS = 4096   # DBHIP_TOPK_SEGMENT_ROWS: one wave's rows in the count and write kernels
+TOPK_CHUNK_ROWS = 32768    # DBHIP_TOPK_CHUNK_ROWS: one workgroup's rows there
+
+
+class TopK:
+    """Reusable plan for the first min(k, n) rows of a column by key, ties by row (dbhip_topk_*): owns the workspace and
+    both output columns."""
+
+    def __init__(self, n: int, k: int, device="cuda"):
+        if n < 0 or k < 0:
+            raise ValueError("n and k must not be negative")
+        self.n, self.k, self.m = n, k, min(k, n)
+        self.ws_bytes = _capi.lib().dbhip_topk_workspace_bytes(n, k)
+        if n >= 1 << 32:
+            raise ValueError("top-k takes fewer than 2^32 rows")
+        self.ws = _ws(self.ws_bytes, device)
+        self.ws_bytes = self.ws.numel()
+        self.out_keys = torch.empty(max(self.m, 1), dtype=torch.int32, device=device)
+        self.out_rows = torch.empty(max(self.m, 1), dtype=torch.int32, device=device)
+
+    def launch(self, keys: torch.Tensor, largest: bool = False, signed: bool = False, sorted: bool = True):
+        """Asynchronous on the current stream; nothing is read back.  -> (keys, rows) of the first m = min(k, n) rows,
+        views of the plan's columns (int32 storage; rows are uint32 ids).  sorted: in key order, ties by row; otherwise
+        in ascending row order.  signed=False orders the bits as uint32."""
+        _need(keys, torch.int32, "keys")
+        _need16(keys, "keys")
+        if keys.numel() != self.n:
+            raise ValueError("size mismatch")
+        fn = _capi.lib().dbhip_topk_i32 if signed else _capi.lib().dbhip_topk_u32
+        _capi.check(fn(keys.data_ptr(), self.n, self.k, int(largest), int(sorted), self.out_keys.data_ptr(),
+                       self.out_rows.data_ptr(), self.ws.data_ptr(), self.ws_bytes, _stream()), "topk")
+        return self.out_keys[:self.m], self.out_rows[:self.m]
+
+    def result(self):
+        """-> (keys, rows) of the last launch, after its status word was read (synchronises)"""
+        _check_status(self.ws, "topk")
+        return self.out_keys[:self.m], self.out_rows[:self.m]
+
+
+def topk(keys: torch.Tensor, k: int, largest: bool = False, signed: bool = False, sorted: bool = True):
+    """-> (keys, rows): the first min(k, n) rows by key (smallest, or largest), equal keys by ascending row"""
+    plan = TopK(keys.numel(), k, keys.device)
+    plan.launch(keys, largest, signed, sorted)
+    return plan.result()
+
+
+def check_topk(keys: torch.Tensor, out_keys: torch.Tensor, out_rows: torch.Tensor, largest: bool = False,
+               signed: bool = False):
+    """-> (wrong entries, input rows strictly in front of the last entry) of a SORTED top-k table of k = len(out_keys)
+    entries; the table is right iff this is (0, min(k, n) - 1), or (0, 0) for an empty one"""
+    for t, name in ((keys, "keys"), (out_keys, "out_keys"), (out_rows, "out_rows")):
+        _need(t, torch.int32, name)
+    if out_rows.numel() != out_keys.numel():
+        raise ValueError("size mismatch")
+    res = _result(2, keys.device)
+    _capi.check(_capi.lib().dbhip_check_topk_u32(keys.data_ptr(), keys.numel(), out_keys.data_ptr(), out_rows.data_ptr(),
+                                                 out_keys.numel(), int(largest), int(signed), res.data_ptr(), _stream()),
+                "check_topk_u32")
+    return tuple(_u64(res))
+
+
+# ---------------------------------------------------------------------------------------------
 # dwarf 3: group-by SUM
 # ---------------------------------------------------------------------------------------------
 class GroupBySum:

@@ -10,6 +10,13 @@ the contract numbers come from bench.py.
                   2^lg alone), full-range keys and keys in [1, 10000]; beside them, in the same run, the keys-only sort and
                   torch.sort(stable=True) (which returns 8-byte indices) (median of 9, refresh copy subtracted); every
                   column of every mode checked against torch's stable sort
+  topk [lg]       ORDER BY key LIMIT k at 2^lg rows (default 24): ops.topk (sorted), the argsort route (clone + radix_argsort_ +
+                  slice; the copy belongs to it, the argsort destroys its input) and torch.topk on the same int32 column, in
+                  one process, alternating, REPS (default 5) repetitions of a median of 5 each; k = 1, 64, 1024, 2^16, 2^20, n/2;
+                  uniform full-range keys, keys in [1, 10000], all keys equal, sorted ascending (TOPK_INPUTS=uniform: that one alone); prints every repetition, and
+                  per row the range of each leg; ops.topk's answer checked by dbhip_check_topk_u32 and against the argsort
+  launch-topk [lg] five sorted top-k calls at k = 1024 and five at k = 2^20 on 2^lg uniform rows (default 24), nothing else
+                  (`rocprofv3 --kernel-trace --stats`)
   join-pairs [lg] the join's pair table (dbhip_join_pairs_u32: scan + expansion, one call, capacity given) on the radix join's
                   answer at 2^20 / 2^24 / 2^26 rows a side (or 2^lg alone) with keys in [1, n], and on 2^13 x 2^13 rows of one
                   key (2^26 pairs); beside it the count-only call and, in the same process on the same (ids, pos, cnt), the
@@ -165,6 +172,63 @@ def sort_pairs(lg):
             for r in res:
                 print(f"{TAG:12s} n={n:9d} {name:10s} {r}   torch.sort(stable) {t_torch:8.1f} us", flush=True)
             del keys0, vals0, keys, vals, ref
+
+
+def _topk_columns(n):
+    yield "uniform", ops.gen_uniform_u32(n, 42, 0, 2**32 - 1)
+    yield "[1,10000]", ops.gen_uniform_u32(n, 42, 1, 10000)
+    yield "all equal", torch.full((n,), 12345, dtype=torch.int32, device="cuda")
+    yield "ascending", torch.sort(ops.gen_uniform_u32(n, 42, 0, 2**31 - 1)).values
+
+
+def topk(lg):
+    n = 1 << (lg or 24)
+    reps = int(os.environ.get("REPS", "5"))
+    only = os.environ.get("TOPK_INPUTS")  # e.g. "uniform": that column alone
+    for name, keys in _topk_columns(n):
+        if only and name not in only.split(","):
+            continue
+        srt = ops.RadixSortPairs(n, 8)
+        scratch = torch.empty_like(keys)
+        for k in (1, 64, 1024, 1 << 16, 1 << 20, n // 2):
+            plan = ops.TopK(n, k)
+
+            def select():
+                plan.launch(keys, signed=True)
+
+            def argsort():
+                scratch.copy_(keys)
+                srt.launch(scratch, None, signed=True)  # the answer: scratch[:k], srt.perm[:k]
+
+            def vendor():
+                torch.topk(keys, k, largest=False, sorted=True)
+
+            legs = {"topk": [], "argsort": [], "torch.topk": []}
+            for _ in range(reps):  # alternating
+                legs["topk"].append(median(times(select, 5)))
+                legs["argsort"].append(median(times(argsort, 5)))
+                legs["torch.topk"].append(median(times(vendor, 5)))
+            select()
+            argsort()
+            got_keys, got_rows = plan.result()
+            ok = (ops.check_topk(keys, got_keys, got_rows, signed=True) == (0, k - 1) and torch.equal(got_rows, srt.perm[:k])
+                  and torch.equal(got_keys, scratch[:k]) and ops.workspace_status(srt.ws) == 0)
+            cols = "  ".join(f"{leg} {min(ts):8.1f} .. {max(ts):8.1f} us" for leg, ts in legs.items())
+            verdict = "select wins beyond both ranges" if max(legs["topk"]) < min(legs["argsort"]) else "SELECT DOES NOT WIN"
+            print(f"{TAG:10s} n=2^{lg or 24} {name:10s} k={k:9d}  {cols}  {'ok' if ok else 'WRONG'}  {verdict}   "
+                  + " ".join(f"{leg}:" + "/".join(f"{t:.1f}" for t in ts) for leg, ts in legs.items()), flush=True)
+        del keys, srt, scratch
+
+
+def launch_topk(lg):
+    n = 1 << (lg or 24)
+    keys = ops.gen_uniform_u32(n, 42, 0, 2**32 - 1)
+    for k in (1024, 1 << 20):
+        plan = ops.TopK(n, k)
+        for _ in range(5):
+            plan.launch(keys, signed=True)
+        plan.result()
+    print("ok")
 
 
 def _join_pairs_shapes(lg):
@@ -921,7 +985,7 @@ def launch_all(_):
 MODES = {"radix": radix, "ramp": ramp, "radix-idle": radix_idle, "radix-stream": radix_stream, "radix-alloc": radix_alloc, "radix-offsets": radix_offsets, "radix-sizes": radix_sizes, "graph": graph, "launch-join": launch_join, "launch-sort": launch_sort, "launch-all": launch_all, "scan": scan, "sort": sort, "sort-only": sort_only, "groupby": groupby, "groupby-shapes": groupby_shapes, "groupby-skew": groupby_skew, "sort-shapes": sort_shapes, "join": join, "join-skew": join_skew, "size-sweep": size_sweep, "partition": partition,
          "reduce": reduce, "xscan": xscan, "cuckoo": cuckoo, "slab": slab,
          "groupby-hash": groupby_hash, "sort-pairs": sort_pairs, "launch-sort-pairs": launch_sort_pairs,
-         "join-pairs": join_pairs, "launch-join-pairs": launch_join_pairs}
+         "join-pairs": join_pairs, "launch-join-pairs": launch_join_pairs, "topk": topk, "launch-topk": launch_topk}
 
 if __name__ == "__main__":
     if len(sys.argv) < 2 or sys.argv[1] not in MODES:
