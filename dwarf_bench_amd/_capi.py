@@ -99,6 +99,14 @@ TOPK_SIGNATURES = {
     "dbhip_check_topk_u32": (_int, [_vp, _sz, _vp, _vp, _sz, _int, _int, _vp, _vp]),
 }
 
+# the same for include/dbhip_reduce_by_key.h (tests/test_reduce_by_key_host.py checks this pair)
+REDUCE_BY_KEY_SIGNATURES = {
+    "dbhip_reduce_by_key_workspace_bytes": (_sz, [_sz]),
+    "dbhip_reduce_by_key_u32": (_int, [_vp, _vp, _sz, _int, _vp, _vp, _vp, _vp, _vp, _sz, _vp, _vp, _sz, _vp]),
+    "dbhip_check_reduce_by_key_workspace_bytes": (_sz, [_sz, _sz]),
+    "dbhip_check_reduce_by_key_u32": (_int, [_vp, _vp, _sz, _int, _vp, _vp, _vp, _vp, _vp, _sz, _vp, _vp, _sz, _vp]),
+}
+
 _lib = None
 
 
@@ -123,7 +131,7 @@ def lib() -> C.CDLL:
         except Exception:  # pragma: no cover - torch is plumbing, the C++ host layer runs without it
             pass
         handle = C.CDLL(str(_LIB_PATH), mode=C.RTLD_GLOBAL)
-        for name, (res, args) in {**SIGNATURES, **TOPK_SIGNATURES}.items():
+        for name, (res, args) in {**SIGNATURES, **TOPK_SIGNATURES, **REDUCE_BY_KEY_SIGNATURES}.items():
             fn = getattr(handle, name)  # AttributeError if the .so does not export the symbol
             fn.restype = res
             fn.argtypes = args

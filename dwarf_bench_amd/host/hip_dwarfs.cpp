@@ -33,6 +33,7 @@
 #include <unordered_map>
 
 #include "../../include/dbhip.h"
+#include "../../include/dbhip_reduce_by_key.h"
 #include "../../include/dbhip_topk.h"
 #include "errors.hpp"
 
@@ -1415,6 +1416,60 @@ void GroupByHashHip::_run(const size_t n, Meter &meter) {
       for (uint32_t x : out_counts.to_host(g)) total += x;
       ok = s[0] == want_sums[0] && s[1] == want_sums[1] && c[0] == want_counts[0] && c[1] == want_counts[1] && d[0] == 0 &&
            total == n;
+    }
+    record(meter, n, std::move(result), ok, "Incorrect results");
+  }
+}
+
+// =====================================================================================================
+// GroupBySortedHip — GROUP BY key ORDER BY key with COUNT, 64-bit SUM, MIN, MAX: the stable pairs sort
+// (dbhip_radix_sort_pairs_u32, the values travel with the keys) and dbhip_reduce_by_key_u32 behind it
+// (include/dbhip_reduce_by_key.h).  Keys and values as GroupByHashHip's; the timed region is the sort plus the reduce, the
+// columns are copied afresh outside it (the sort works in place).  Result::valid from dbhip_check_reduce_by_key_u32 on the
+// sorted columns, the sort's own check on the keys, and the number of runs against the bound.  No reference counterpart.
+void GroupBySortedHip::_run(const size_t n, Meter &meter) {
+  const auto &opts = static_cast<const GroupByRunOptions &>(meter.opts());
+  if (n >= (static_cast<size_t>(1) << 32)) fail("GroupBySortedHip: fewer than 2^32 rows");
+  const uint32_t groups = static_cast<uint32_t>(opts.groups_count ? opts.groups_count : 1);
+  const size_t cap = std::max<size_t>(std::min<size_t>(groups, n), 1);
+  DevBuf<uint32_t> src_keys(n), src_vals(n), draw(n), keys(n), vals(n), tmp_keys(n), tmp_vals(n);
+  DevBuf<uint32_t> out_keys(cap), out_counts(cap), out_mins(cap), out_maxs(cap);
+  DevBuf<uint64_t> out_sums(cap), out_runs(1);
+  const size_t sort_bytes = dbhip_radix_sort_pairs_workspace_bytes(n, 8);
+  const size_t ws_bytes = dbhip_reduce_by_key_workspace_bytes(n);
+  const size_t cws_bytes = dbhip_check_reduce_by_key_workspace_bytes(n, cap);
+  DevBuf<unsigned char> sort_ws(sort_bytes), ws(ws_bytes), cws(cws_bytes);
+  db_ok(dbhip_gen_uniform_u32(src_vals.get(), n, 43, 0, 1, 10000, nullptr), "gen vals");
+  db_ok(dbhip_gen_uniform_u32(draw.get(), n, 42, 0, 0, groups - 1, nullptr), "gen draw");
+  db_ok(dbhip_gen_uniform_at_u32(src_keys.get(), draw.get(), n, 44, 0, 0xFFFFFFFFu, nullptr), "gen keys");
+  hip_ok(hipDeviceSynchronize(), "sync");
+  CheckWords chk;
+  Events ev;
+  for (size_t it = 0; it < opts.iterations; ++it) {
+    hip_ok(hipMemcpy(keys.get(), src_keys.get(), n * sizeof(uint32_t), hipMemcpyDeviceToDevice), "refresh");  // not timed
+    hip_ok(hipMemcpy(vals.get(), src_vals.get(), n * sizeof(uint32_t), hipMemcpyDeviceToDevice), "refresh");
+    auto result = std::make_unique<Result>();
+    time_launch(*result, ev, [&] {
+      db_ok(dbhip_radix_sort_pairs_u32(keys.get(), vals.get(), tmp_keys.get(), tmp_vals.get(), n, 8, 0, sort_ws.get(),
+                                       sort_bytes, nullptr),
+            "dbhip_radix_sort_pairs_u32");
+      db_ok(dbhip_reduce_by_key_u32(keys.get(), vals.get(), n, 0, out_keys.get(), out_counts.get(), out_sums.get(),
+                                    out_mins.get(), out_maxs.get(), cap, out_runs.get(), ws.get(), ws_bytes, nullptr),
+            "dbhip_reduce_by_key_u32");
+    });
+    if (n) check_status(sort_ws.get(), "GroupBySortedHip");
+    if (n) check_status(ws.get(), "GroupBySortedHip");
+    const size_t runs = n ? static_cast<size_t>(out_runs.to_host(1)[0]) : 0;
+    if (inject_fault() && runs) poke_xor(out_sums.get() + runs / 2, 1u);  // the low word of one sum
+    bool ok = runs <= cap;
+    if (ok) {  // sorted keys (so equal keys are one run), and the table is the reduce of the sorted columns
+      db_ok(dbhip_check_sorted_u32(keys.get(), n, 0, chk.dev(), nullptr), "dbhip_check_sorted_u32");
+      const auto srt = chk.get();
+      db_ok(dbhip_check_reduce_by_key_u32(keys.get(), vals.get(), n, 0, out_keys.get(), out_counts.get(), out_sums.get(),
+                                          out_mins.get(), out_maxs.get(), runs, chk.dev(), cws.get(), cws_bytes, nullptr),
+            "dbhip_check_reduce_by_key_u32");
+      const auto g = chk.get();
+      ok = srt[0] == 0 && g[0] == 0 && g[1] == 0 && g[2] == g[3];
     }
     record(meter, n, std::move(result), ok, "Incorrect results");
   }

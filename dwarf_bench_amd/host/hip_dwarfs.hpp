@@ -121,3 +121,10 @@ struct TopKHip : HipDwarf {
   TopKHip() : HipDwarf("TopKHip") {}
   void _run(size_t buf_size, Meter &meter) override;
 };
+// GROUP BY key ORDER BY key with COUNT, 64-bit SUM, MIN, MAX: the stable pairs sort and dbhip_reduce_by_key_u32
+// (include/dbhip_reduce_by_key.h); registered by populate_groupby_sorted_registry() only (the dwarf_bench_groupby_sorted
+// CLI); no reference counterpart.  --groups_count as GroupByHashHip
+struct GroupBySortedHip : HipDwarf {
+  GroupBySortedHip() : HipDwarf("GroupBySortedHip") {}
+  void _run(size_t buf_size, Meter &meter) override;
+};

@@ -10,7 +10,8 @@
 // -DEXPERIMENTAL_SORT_PAIRS `dwarf_bench_sort_pairs`, the default set plus RadixPairsHip (populate_sort_pairs_registry),
 // and with -DEXPERIMENTAL_JOIN_PAIRS `dwarf_bench_join_pairs`, the default set plus JoinPairsHip
 // (populate_join_pairs_registry), and with -DEXPERIMENTAL_TOPK `dwarf_bench_topk`, the default set plus TopKHip
-// (populate_topk_registry).
+// (populate_topk_registry), and with -DEXPERIMENTAL_GROUPBY_SORTED `dwarf_bench_groupby_sorted`, the default set plus
+// GroupBySortedHip (populate_groupby_sorted_registry).
 #include <iostream>
 #include <memory>
 #include <sstream>
@@ -57,6 +58,9 @@ int main(int argc, char *argv[]) {
 #endif
 #ifdef EXPERIMENTAL_TOPK
   populate_topk_registry();  // dwarf_bench_topk
+#endif
+#ifdef EXPERIMENTAL_GROUPBY_SORTED
+  populate_groupby_sorted_registry();  // dwarf_bench_groupby_sorted
 #endif
   Registry *registry = Registry::instance();
 

@@ -78,3 +78,11 @@ void populate_topk_registry() {
   Registry::instance()->registerd(new TopKHip());
 #endif
 }
+
+// the sort-based group-by (dbhip_radix_sort_pairs_u32 + dbhip_reduce_by_key_u32): only the dwarf_bench_groupby_sorted CLI
+// (main.cpp built with -DEXPERIMENTAL_GROUPBY_SORTED) calls this, so the lists of the other seven CLIs stay as they are
+void populate_groupby_sorted_registry() {
+#ifdef HIP_ENABLED
+  Registry::instance()->registerd(new GroupBySortedHip());
+#endif
+}

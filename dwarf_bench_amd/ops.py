@@ -278,6 +278,113 @@ def check_topk(keys: torch.Tensor, out_keys: torch.Tensor, out_rows: torch.Tenso
 
 
 # ---------------------------------------------------------------------------------------------
+# reduce by key: one row per run of equal adjacent keys; behind the pairs sort, GROUP BY key ORDER BY key
+# (include/dbhip_reduce_by_key.h)
+# ---------------------------------------------------------------------------------------------
+REDUCE_BY_KEY_SEGMENT_ROWS = 4096   # DBHIP_REDUCE_BY_KEY_SEGMENT_ROWS: one wave's rows in the count and reduce kernels
+REDUCE_BY_KEY_CHUNK_ROWS = 32768    # DBHIP_REDUCE_BY_KEY_CHUNK_ROWS: one workgroup's rows there
+
+
+class ReduceByKey:
+    """Reusable plan for COUNT, 64-bit SUM, MIN and MAX per run of equal adjacent keys (dbhip_reduce_by_key_u32): owns the
+    workspace, the five output columns of `capacity` entries and the run counter.  capacity = 0: the count-only call."""
+
+    def __init__(self, n: int, capacity: int, device="cuda"):
+        if n < 0 or capacity < 0:
+            raise ValueError("n and capacity must not be negative")
+        if n >= 1 << 32:
+            raise ValueError("reduce_by_key takes fewer than 2^32 rows")
+        self.n, self.capacity = n, capacity
+        self.ws_bytes = _capi.lib().dbhip_reduce_by_key_workspace_bytes(n)
+        self.ws = _ws(self.ws_bytes, device)
+        self.ws_bytes = self.ws.numel()
+        cap = max(capacity, 1)
+        self.keys = torch.empty(cap, dtype=torch.int32, device=device)
+        self.counts = torch.empty(cap, dtype=torch.int32, device=device)
+        self.sums = torch.empty(cap, dtype=torch.int64, device=device)
+        self.mins = torch.empty(cap, dtype=torch.int32, device=device)
+        self.maxs = torch.empty(cap, dtype=torch.int32, device=device)
+        self.runs = torch.zeros(1, dtype=torch.int64, device=device)
+
+    def launch(self, keys: torch.Tensor, vals: torch.Tensor | None, signed: bool = False) -> None:
+        """Asynchronous on the current stream; nothing is read back (graph-capturable).  signed: the values are int32
+        (sign-extended sums, signed min and max).  vals=None: keys and counts only."""
+        _need(keys, torch.int32, "keys")
+        _need16(keys, "keys")
+        if vals is not None:
+            _need(vals, torch.int32, "vals")
+            _need16(vals, "vals")
+        if keys.numel() != self.n or (vals is not None and vals.numel() != self.n):
+            raise ValueError("size mismatch")
+        some = self.capacity > 0
+        with_vals = some and vals is not None
+        _capi.check(_capi.lib().dbhip_reduce_by_key_u32(
+            keys.data_ptr(), vals.data_ptr() if with_vals else None, self.n, int(signed),
+            self.keys.data_ptr() if some else None, self.counts.data_ptr() if some else None,
+            self.sums.data_ptr() if with_vals else None, self.mins.data_ptr() if with_vals else None,
+            self.maxs.data_ptr() if with_vals else None, self.capacity, self.runs.data_ptr(), self.ws.data_ptr(),
+            self.ws_bytes, _stream()), "reduce_by_key_u32")
+        self._with_vals = with_vals
+
+    def result(self):
+        """-> (keys, counts, sums, mins, maxs) of the last launch, cut to the number of runs (sums: int64 bit patterns;
+        the three value columns are None after a launch without vals); raises on a device status (more runs than
+        capacity: DBHIP_DEV_TABLE_FULL; self.runs still holds the number)."""
+        _check_status(self.ws, "reduce_by_key_u32")
+        r = min(int(self.runs.item()), self.capacity)
+        if not self._with_vals:
+            return self.keys[:r], self.counts[:r], None, None, None
+        return self.keys[:r], self.counts[:r], self.sums[:r], self.mins[:r], self.maxs[:r]
+
+
+def reduce_by_key(keys: torch.Tensor, vals: torch.Tensor, signed: bool = False, capacity: int | None = None):
+    """One row per run of equal adjacent keys -> (keys, counts, sums, mins, maxs), cut to the number of runs.  capacity:
+    a bound on the number of runs (None: a count-only call finds it first)."""
+    if capacity is None:
+        count = ReduceByKey(keys.numel(), 0, keys.device)
+        count.launch(keys, None)
+        _check_status(count.ws, "reduce_by_key_u32")
+        capacity = int(count.runs.item())
+    plan = ReduceByKey(keys.numel(), capacity, keys.device)
+    plan.launch(keys, vals, signed)
+    return plan.result()
+
+
+def groupby_sorted(keys: torch.Tensor, vals: torch.Tensor, signed: bool = False, signed_keys: bool = False):
+    """GROUP BY keys ORDER BY keys: -> (distinct keys ascending, COUNT(*), SUM(vals) as int64, MIN(vals), MAX(vals)).  Copies
+    both columns, sorts the copies with the stable pairs sort (the values travel with the keys) and reduces the runs.
+    signed: the values are int32; signed_keys: the keys ascend as int32."""
+    _need(keys, torch.int32, "keys")
+    _need(vals, torch.int32, "vals")
+    if keys.numel() != vals.numel():
+        raise ValueError("size mismatch")
+    k, v = keys.clone(), vals.clone()
+    radix_sort_pairs_(k, v, signed=signed_keys)
+    return reduce_by_key(k, v, signed=signed)
+
+
+def check_reduce_by_key(keys: torch.Tensor, vals: torch.Tensor, out_keys: torch.Tensor, out_counts: torch.Tensor,
+                        out_sums: torch.Tensor, out_mins: torch.Tensor, out_maxs: torch.Tensor, signed: bool = False):
+    """-> the four words of dbhip_check_reduce_by_key_u32; the table is right iff the first two are 0 and the last two
+    are equal"""
+    for t, name in ((keys, "keys"), (vals, "vals"), (out_keys, "out_keys"), (out_counts, "out_counts"),
+                    (out_mins, "out_mins"), (out_maxs, "out_maxs")):
+        _need(t, torch.int32, name)
+    _need(out_sums, torch.int64, "out_sums")
+    runs = out_keys.numel()
+    if keys.numel() != vals.numel() or any(t.numel() != runs for t in (out_counts, out_sums, out_mins, out_maxs)):
+        raise ValueError("size mismatch")
+    ws_bytes = _capi.lib().dbhip_check_reduce_by_key_workspace_bytes(keys.numel(), runs)
+    ws = _ws(ws_bytes, keys.device)
+    res = _result(4, keys.device)
+    _capi.check(_capi.lib().dbhip_check_reduce_by_key_u32(
+        keys.data_ptr(), vals.data_ptr(), keys.numel(), int(signed), out_keys.data_ptr(), out_counts.data_ptr(),
+        out_sums.data_ptr(), out_mins.data_ptr(), out_maxs.data_ptr(), runs, res.data_ptr(), ws.data_ptr(), ws.numel(),
+        _stream()), "check_reduce_by_key_u32")
+    return tuple(_u64(res))
+
+
+# ---------------------------------------------------------------------------------------------
 # dwarf 3: group-by SUM
 # ---------------------------------------------------------------------------------------------
 class GroupBySum:

@@ -17,6 +17,15 @@ the contract numbers come from bench.py.
                   per row the range of each leg; ops.topk's answer checked by dbhip_check_topk_u32 and against the argsort
   launch-topk [lg] five sorted top-k calls at k = 1024 and five at k = 2^20 on 2^lg uniform rows (default 24), nothing else
                   (`rocprofv3 --kernel-trace --stats`)
+  groupby-sorted [lg] dbhip_reduce_by_key_u32 at 2^lg rows (default 24).  Part 1, sorted input (R = 1, 64, 2^16, 2^20, n runs, and half the
+                  rows in one run with the rest distinct): ReduceByKey.launch with all five aggregates against
+                  torch.unique_consecutive(return_inverse, return_counts) + scatter_add_ on int64 + scatter_reduce_ amin / amax, in
+                  one process, alternating, REPS (default 5) repetitions of a median of 5; beside it the time of (12n + 24R)
+                  bytes at 8 TB/s.  Part 2, the same keys shuffled: copy + pairs sort + reduce (ops.groupby_sorted's launches)
+                  against GroupByHash.launch (wrapping SUM and COUNT, unordered) and torch.unique(return_inverse,
+                  return_counts) + the same scatters.  Every answer checked by dbhip_check_reduce_by_key_u32
+  launch-groupby-sorted [lg] five reduce calls each on sorted keys with 64, 2^20 and n runs at 2^lg rows, nothing else
+                  (`rocprofv3 --kernel-trace --stats`)
   join-pairs [lg] the join's pair table (dbhip_join_pairs_u32: scan + expansion, one call, capacity given) on the radix join's
                   answer at 2^20 / 2^24 / 2^26 rows a side (or 2^lg alone) with keys in [1, n], and on 2^13 x 2^13 rows of one
                   key (2^26 pairs); beside it the count-only call and, in the same process on the same (ids, pos, cnt), the
@@ -227,6 +236,106 @@ def launch_topk(lg):
         plan = ops.TopK(n, k)
         for _ in range(5):
             plan.launch(keys, signed=True)
+        plan.result()
+    print("ok")
+
+
+def _sorted_key_shapes(n):
+    """(name, sorted keys, R)"""
+    rows = torch.arange(n, dtype=torch.int64, device="cuda")
+    for r in (1, 64, 1 << 16, 1 << 20, n):
+        if r <= n:
+            yield f"R={r}", (rows * r // n).to(torch.int32), r
+    half = torch.where(rows < n // 2, torch.zeros_like(rows), rows - n // 2 + 1).to(torch.int32)
+    yield "half+distinct", half, n - n // 2 + 1
+
+
+def _torch_aggregates(inverse, groups, vals64, vals):
+    sums = torch.zeros(groups, dtype=torch.int64, device="cuda").scatter_add_(0, inverse, vals64)
+    mins = torch.full((groups,), 2**31 - 1, dtype=torch.int32, device="cuda").scatter_reduce_(0, inverse, vals, "amin")
+    maxs = torch.full((groups,), -2**31, dtype=torch.int32, device="cuda").scatter_reduce_(0, inverse, vals, "amax")
+    return sums, mins, maxs
+
+
+def groupby_sorted(lg):
+    n = 1 << (lg or 24)
+    reps = int(os.environ.get("REPS", "5"))
+    vals = ops.gen_uniform_u32(n, 43, 1, 10000)
+    vals64 = vals.to(torch.int64)
+
+    def report(part, name, R, legs, ok, model=None):
+        cols = "  ".join(f"{leg} {min(ts):9.1f} .. {max(ts):9.1f} us" for leg, ts in legs.items())
+        extra = f"  model {model:7.1f} us" if model else ""
+        print(f"{TAG:10s} {part} n=2^{lg or 24} {name:14s} runs={R:9d}  {cols}{extra}  {'ok' if ok else 'WRONG'}   "
+              + " ".join(f"{leg}:" + "/".join(f"{t:.1f}" for t in ts) for leg, ts in legs.items()), flush=True)
+
+    for name, keys, R in _sorted_key_shapes(n):
+        plan = ops.ReduceByKey(n, R)
+
+        def reduce():
+            plan.launch(keys, vals)
+
+        def vendor():
+            u, inv, cnt = torch.unique_consecutive(keys, return_inverse=True, return_counts=True)
+            return (u, cnt) + _torch_aggregates(inv, u.numel(), vals64, vals)
+
+        legs = {"reduce_by_key": [], "torch": []}
+        for _ in range(reps):  # alternating
+            legs["reduce_by_key"].append(median(times(reduce, 5)))
+            legs["torch"].append(median(times(vendor, 5)))
+        reduce()
+        got = plan.result()
+        words = ops.check_reduce_by_key(keys, vals, *got)
+        u, cnt, sums, mins, maxs = vendor()
+        ok = (words[0] == 0 and words[1] == 0 and words[2] == words[3] and got[0].numel() == R and torch.equal(got[0], u)
+              and torch.equal(got[1].to(torch.int64), cnt) and torch.equal(got[2], sums) and torch.equal(got[3], mins)
+              and torch.equal(got[4], maxs))
+        report("sorted  ", name, R, legs, ok, model=(12 * n + 24 * R) / 8e12 * 1e6)
+        del plan, got, u, cnt, sums, mins, maxs
+
+        # part 2: the same groups in no order
+        shuffled = keys[torch.randperm(n, device="cuda")]
+        srt = ops.RadixSortPairs(n, 8)
+        plan = ops.ReduceByKey(n, R)
+        hashed = ops.GroupByHash(n, R)
+        k2, v2 = torch.empty_like(shuffled), torch.empty_like(vals)
+
+        def sort_route():
+            k2.copy_(shuffled)
+            v2.copy_(vals)
+            srt.launch(k2, v2)
+            plan.launch(k2, v2)
+
+        def hash_route():
+            hashed.launch(shuffled, vals)
+
+        def vendor2():
+            u, inv, cnt = torch.unique(shuffled, return_inverse=True, return_counts=True)
+            return (u, cnt) + _torch_aggregates(inv, u.numel(), vals64, vals)
+
+        legs = {"groupby_sorted": [], "groupby_hash": [], "torch": []}
+        for _ in range(reps):
+            legs["groupby_sorted"].append(median(times(sort_route, 5)))
+            legs["groupby_hash"].append(median(times(hash_route, 5)))
+            legs["torch"].append(median(times(vendor2, 5)))
+        sort_route()
+        got = plan.result()
+        words = ops.check_reduce_by_key(k2, v2, *got)
+        ok = (words[0] == 0 and words[1] == 0 and words[2] == words[3] and got[0].numel() == R
+              and ops.workspace_status(srt.ws) == 0 and ops.check_sorted(k2)[0] == 0)
+        report("unsorted", name, R, legs, ok)
+        del plan, srt, hashed, shuffled, k2, v2, got
+
+
+def launch_groupby_sorted(lg):
+    n = 1 << (lg or 24)
+    vals = ops.gen_uniform_u32(n, 43, 1, 10000)
+    for name, keys, R in _sorted_key_shapes(n):
+        if R not in (64, 1 << 20, n):
+            continue
+        plan = ops.ReduceByKey(n, R)
+        for _ in range(5):
+            plan.launch(keys, vals)
         plan.result()
     print("ok")
 
@@ -985,7 +1094,8 @@ def launch_all(_):
 MODES = {"radix": radix, "ramp": ramp, "radix-idle": radix_idle, "radix-stream": radix_stream, "radix-alloc": radix_alloc, "radix-offsets": radix_offsets, "radix-sizes": radix_sizes, "graph": graph, "launch-join": launch_join, "launch-sort": launch_sort, "launch-all": launch_all, "scan": scan, "sort": sort, "sort-only": sort_only, "groupby": groupby, "groupby-shapes": groupby_shapes, "groupby-skew": groupby_skew, "sort-shapes": sort_shapes, "join": join, "join-skew": join_skew, "size-sweep": size_sweep, "partition": partition,
          "reduce": reduce, "xscan": xscan, "cuckoo": cuckoo, "slab": slab,
          "groupby-hash": groupby_hash, "sort-pairs": sort_pairs, "launch-sort-pairs": launch_sort_pairs,
-         "join-pairs": join_pairs, "launch-join-pairs": launch_join_pairs, "topk": topk, "launch-topk": launch_topk}
+         "join-pairs": join_pairs, "launch-join-pairs": launch_join_pairs, "topk": topk, "launch-topk": launch_topk,
+         "groupby-sorted": groupby_sorted, "launch-groupby-sorted": launch_groupby_sorted}
 
 if __name__ == "__main__":
     if len(sys.argv) < 2 or sys.argv[1] not in MODES:
