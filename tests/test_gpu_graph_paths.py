@@ -25,6 +25,7 @@ from oracle import pyoracle as po
 from tests import graph_testlib as gl
 from tests import groupby_hash_testlib as gh
 from tests import join_testlib as jt
+from tests import sort_pass_testlib as sp
 from tests.cuckoo_model import CuckooModel, mix64_np, murmur3_x86_32_np
 from tests.graph_testlib import Buffers, Input, run_family, u32
 from tests.guard_testlib import FILLS, i32, i64
@@ -150,7 +151,11 @@ def test_exclusive_scan_three_launch_path(n, place):
 # ---- sorts ----------------------------------------------------------------------------------------------------------------
 def _sort_inputs(n, pairs):
     full = po.gen_uniform_u32(n, 1, 0, M32)
-    cols = [(full, "full range"), (po.gen_uniform_u32(n, 2, 1, 10000), "keys in [1, 10000]: skipped passes"),
+    # behind the captured run (pass 0 executed): pass 0 skipped, then executed again with the passes between the two
+    # ends skipped (tests/sort_pass_testlib.py: exactly the bytes of the mask vary, the others hold a constant)
+    cols = [(full, "full range"), (sp.keys_for(0x00FF0000, n, 5, sp.BASE_NEG), "only byte 2 varies: pass 0 skipped"),
+            (sp.keys_for(0xFF0000FF, n, 6, sp.BASE), "bytes 0 and 3 vary"),
+            (po.gen_uniform_u32(n, 2, 1, 10000), "keys in [1, 10000]: skipped passes"),
             (np.full(n, 0x80000007, np.uint32), "all keys equal: no pass runs"),
             (np.sort(po.gen_uniform_u32(n, 3, 0, M32)), "already sorted"), (po.gen_uniform_u32(n, 4, 0, M32), "full range")]
     return [Input([k] + ([po.gen_uniform_u32(n, 10 + i, 0, M32)] if pairs else []), name=name)
