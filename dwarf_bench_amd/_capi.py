@@ -107,6 +107,14 @@ REDUCE_BY_KEY_SIGNATURES = {
     "dbhip_check_reduce_by_key_u32": (_int, [_vp, _vp, _sz, _int, _vp, _vp, _vp, _vp, _vp, _sz, _vp, _vp, _sz, _vp]),
 }
 
+# the same for include/dbhip_scan_by_key.h (tests/test_scan_by_key_host.py checks this pair)
+SCAN_BY_KEY_SIGNATURES = {
+    "dbhip_scan_by_key_workspace_bytes": (_sz, [_sz]),
+    "dbhip_scan_by_key_u32": (_int, [_vp, _vp, _sz, _int, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "dbhip_check_scan_by_key_workspace_bytes": (_sz, [_sz]),
+    "dbhip_check_scan_by_key_u32": (_int, [_vp, _vp, _sz, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+}
+
 _lib = None
 
 
@@ -131,7 +139,8 @@ def lib() -> C.CDLL:
         except Exception:  # pragma: no cover - torch is plumbing, the C++ host layer runs without it
             pass
         handle = C.CDLL(str(_LIB_PATH), mode=C.RTLD_GLOBAL)
-        for name, (res, args) in {**SIGNATURES, **TOPK_SIGNATURES, **REDUCE_BY_KEY_SIGNATURES}.items():
+        for name, (res, args) in {**SIGNATURES, **TOPK_SIGNATURES, **REDUCE_BY_KEY_SIGNATURES,
+                                   **SCAN_BY_KEY_SIGNATURES}.items():
             fn = getattr(handle, name)  # AttributeError if the .so does not export the symbol
             fn.restype = res
             fn.argtypes = args

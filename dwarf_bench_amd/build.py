@@ -72,7 +72,8 @@ def build_hip(force: bool = False) -> Path:
     out = LIB / "libdbhip.so"
     srcs = sorted(CSRC.glob("*.hip"))
     headers = sorted(CSRC.glob("*.hpp")) + [ROOT / "include" / "dbhip.h", ROOT / "include" / "dbhip_topk.h",
-                                              ROOT / "include" / "dbhip_reduce_by_key.h"]
+                                              ROOT / "include" / "dbhip_reduce_by_key.h",
+                                              ROOT / "include" / "dbhip_scan_by_key.h"]
     deps = srcs + headers
     if force or _stale(out, deps):
         objs = []

@@ -180,6 +180,8 @@ void populate_join_pairs_registry();
 void populate_topk_registry();
 // GroupBySortedHip: only the dwarf_bench_groupby_sorted CLI registers it, after populate_registry()
 void populate_groupby_sorted_registry();
+// WindowSortedHip: only the dwarf_bench_window CLI registers it, after populate_registry()
+void populate_window_registry();
 
 namespace helpers {
 // $DWARF_BENCH_ROOT or the executable's directory (common/common.cpp:38-41, without Boost.DLL)

@@ -34,6 +34,7 @@
 
 #include "../../include/dbhip.h"
 #include "../../include/dbhip_reduce_by_key.h"
+#include "../../include/dbhip_scan_by_key.h"
 #include "../../include/dbhip_topk.h"
 #include "errors.hpp"
 
@@ -1471,6 +1472,56 @@ void GroupBySortedHip::_run(const size_t n, Meter &meter) {
       const auto g = chk.get();
       ok = srt[0] == 0 && g[0] == 0 && g[1] == 0 && g[2] == g[3];
     }
+    record(meter, n, std::move(result), ok, "Incorrect results");
+  }
+}
+
+// =====================================================================================================
+// WindowSortedHip — ROW_NUMBER, running 64-bit SUM, MIN, MAX and the run number over PARTITION BY key ORDER BY row: the
+// stable pairs sort (dbhip_radix_sort_pairs_u32, the values travel with the keys) and dbhip_scan_by_key_u32 behind it
+// (include/dbhip_scan_by_key.h).  Keys and values as GroupBySortedHip's; the timed region is the sort plus the scan, the
+// columns are copied afresh outside it (the sort works in place).  Result::valid from the sort's own check on the keys and
+// dbhip_check_scan_by_key_u32 on the sorted columns.  No reference counterpart.
+void WindowSortedHip::_run(const size_t n, Meter &meter) {
+  const auto &opts = static_cast<const GroupByRunOptions &>(meter.opts());
+  if (n >= (static_cast<size_t>(1) << 32)) fail("WindowSortedHip: fewer than 2^32 rows");
+  const uint32_t groups = static_cast<uint32_t>(opts.groups_count ? opts.groups_count : 1);
+  DevBuf<uint32_t> src_keys(n), src_vals(n), draw(n), keys(n), vals(n), tmp_keys(n), tmp_vals(n);
+  DevBuf<uint32_t> run_ids(n), row_numbers(n), mins(n), maxs(n);
+  DevBuf<uint64_t> sums(n);
+  const size_t sort_bytes = dbhip_radix_sort_pairs_workspace_bytes(n, 8);
+  const size_t ws_bytes = dbhip_scan_by_key_workspace_bytes(n);
+  const size_t cws_bytes = dbhip_check_scan_by_key_workspace_bytes(n);
+  DevBuf<unsigned char> sort_ws(sort_bytes), ws(ws_bytes), cws(cws_bytes);
+  db_ok(dbhip_gen_uniform_u32(src_vals.get(), n, 43, 0, 1, 10000, nullptr), "gen vals");
+  db_ok(dbhip_gen_uniform_u32(draw.get(), n, 42, 0, 0, groups - 1, nullptr), "gen draw");
+  db_ok(dbhip_gen_uniform_at_u32(src_keys.get(), draw.get(), n, 44, 0, 0xFFFFFFFFu, nullptr), "gen keys");
+  hip_ok(hipDeviceSynchronize(), "sync");
+  CheckWords chk;
+  Events ev;
+  for (size_t it = 0; it < opts.iterations; ++it) {
+    hip_ok(hipMemcpy(keys.get(), src_keys.get(), n * sizeof(uint32_t), hipMemcpyDeviceToDevice), "refresh");  // not timed
+    hip_ok(hipMemcpy(vals.get(), src_vals.get(), n * sizeof(uint32_t), hipMemcpyDeviceToDevice), "refresh");
+    auto result = std::make_unique<Result>();
+    time_launch(*result, ev, [&] {
+      db_ok(dbhip_radix_sort_pairs_u32(keys.get(), vals.get(), tmp_keys.get(), tmp_vals.get(), n, 8, 0, sort_ws.get(),
+                                       sort_bytes, nullptr),
+            "dbhip_radix_sort_pairs_u32");
+      db_ok(dbhip_scan_by_key_u32(keys.get(), vals.get(), n, 0, run_ids.get(), row_numbers.get(), sums.get(), mins.get(),
+                                  maxs.get(), ws.get(), ws_bytes, nullptr),
+            "dbhip_scan_by_key_u32");
+    });
+    if (n) check_status(sort_ws.get(), "WindowSortedHip");
+    if (n) check_status(ws.get(), "WindowSortedHip");
+    if (inject_fault() && n) poke_xor(sums.get() + n / 2, 1u);  // the low word of one sum
+    // sorted keys (so equal keys are one run), and every row continues the row above it
+    db_ok(dbhip_check_sorted_u32(keys.get(), n, 0, chk.dev(), nullptr), "dbhip_check_sorted_u32");
+    const auto srt = chk.get();
+    db_ok(dbhip_check_scan_by_key_u32(keys.get(), vals.get(), n, 0, run_ids.get(), row_numbers.get(), sums.get(), mins.get(),
+                                      maxs.get(), chk.dev(), cws.get(), cws_bytes, nullptr),
+          "dbhip_check_scan_by_key_u32");
+    const auto w = chk.get();
+    const bool ok = srt[0] == 0 && w[0] == 0 && w[1] == ~0ull && w[3] == 0;
     record(meter, n, std::move(result), ok, "Incorrect results");
   }
 }

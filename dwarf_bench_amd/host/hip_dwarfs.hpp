@@ -128,3 +128,10 @@ struct GroupBySortedHip : HipDwarf {
   GroupBySortedHip() : HipDwarf("GroupBySortedHip") {}
   void _run(size_t buf_size, Meter &meter) override;
 };
+// ROW_NUMBER, running 64-bit SUM, MIN, MAX and the run number per row over PARTITION BY key ORDER BY row: the stable pairs
+// sort and dbhip_scan_by_key_u32 (include/dbhip_scan_by_key.h); registered by populate_window_registry() only (the
+// dwarf_bench_window CLI); no reference counterpart.  --groups_count as GroupByHashHip
+struct WindowSortedHip : HipDwarf {
+  WindowSortedHip() : HipDwarf("WindowSortedHip") {}
+  void _run(size_t buf_size, Meter &meter) override;
+};

@@ -11,7 +11,8 @@
 // and with -DEXPERIMENTAL_JOIN_PAIRS `dwarf_bench_join_pairs`, the default set plus JoinPairsHip
 // (populate_join_pairs_registry), and with -DEXPERIMENTAL_TOPK `dwarf_bench_topk`, the default set plus TopKHip
 // (populate_topk_registry), and with -DEXPERIMENTAL_GROUPBY_SORTED `dwarf_bench_groupby_sorted`, the default set plus
-// GroupBySortedHip (populate_groupby_sorted_registry).
+// GroupBySortedHip (populate_groupby_sorted_registry), and with -DEXPERIMENTAL_WINDOW `dwarf_bench_window`, the default
+// set plus WindowSortedHip (populate_window_registry).
 #include <iostream>
 #include <memory>
 #include <sstream>
@@ -22,7 +23,10 @@
 #include "dwarf_api.hpp"
 
 namespace {
-bool isGroupBy(const std::string &dwarfName) { return dwarfName.find("GroupBy") != std::string::npos; }
+// the dwarfs that read --groups_count (WindowSortedHip partitions by the keys GroupBySortedHip groups by)
+bool isGroupBy(const std::string &dwarfName) {
+  return dwarfName.find("GroupBy") != std::string::npos || dwarfName.find("WindowSorted") != std::string::npos;
+}
 
 const char *kHelp =
     "Dwarf bench:\n"
@@ -61,6 +65,9 @@ int main(int argc, char *argv[]) {
 #endif
 #ifdef EXPERIMENTAL_GROUPBY_SORTED
   populate_groupby_sorted_registry();  // dwarf_bench_groupby_sorted
+#endif
+#ifdef EXPERIMENTAL_WINDOW
+  populate_window_registry();  // dwarf_bench_window
 #endif
   Registry *registry = Registry::instance();
 

@@ -86,3 +86,11 @@ void populate_groupby_sorted_registry() {
   Registry::instance()->registerd(new GroupBySortedHip());
 #endif
 }
+
+// the window functions (dbhip_radix_sort_pairs_u32 + dbhip_scan_by_key_u32): only the dwarf_bench_window CLI (main.cpp built
+// with -DEXPERIMENTAL_WINDOW) calls this, so the lists of the other eight CLIs stay as they are
+void populate_window_registry() {
+#ifdef HIP_ENABLED
+  Registry::instance()->registerd(new WindowSortedHip());
+#endif
+}

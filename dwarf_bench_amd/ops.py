@@ -385,6 +385,115 @@ def check_reduce_by_key(keys: torch.Tensor, vals: torch.Tensor, out_keys: torch.
 
 
 # ---------------------------------------------------------------------------------------------
+# scan by key: one row per input row over runs of equal adjacent keys; behind the pairs sort, the window functions over
+# PARTITION BY key ... UNBOUNDED PRECEDING AND CURRENT ROW (include/dbhip_scan_by_key.h)
+# ---------------------------------------------------------------------------------------------
+SCAN_BY_KEY_SEGMENT_ROWS = 4096   # DBHIP_SCAN_BY_KEY_SEGMENT_ROWS: one wave's rows in the two streaming kernels
+SCAN_BY_KEY_CHUNK_ROWS = 32768    # DBHIP_SCAN_BY_KEY_CHUNK_ROWS: one workgroup's rows there
+SCAN_BY_KEY_COLUMNS = ("run_ids", "row_numbers", "sums", "mins", "maxs")
+
+
+class ScanByKey:
+    """Reusable plan for the run number, the running COUNT, 64-bit SUM, MIN and MAX of every row over runs of equal adjacent
+    keys (dbhip_scan_by_key_u32): owns the workspace and the five output columns of n entries."""
+
+    def __init__(self, n: int, device="cuda"):
+        if n < 0:
+            raise ValueError("n must not be negative")
+        if n >= 1 << 32:
+            raise ValueError("scan_by_key takes fewer than 2^32 rows")
+        self.n = n
+        self.ws_bytes = _capi.lib().dbhip_scan_by_key_workspace_bytes(n)
+        self.ws = _ws(self.ws_bytes, device)
+        self.ws_bytes = self.ws.numel()
+        rows = max(n, 1)
+        self.run_ids = torch.empty(rows, dtype=torch.int32, device=device)
+        self.row_numbers = torch.empty(rows, dtype=torch.int32, device=device)
+        self.sums = torch.empty(rows, dtype=torch.int64, device=device)
+        self.mins = torch.empty(rows, dtype=torch.int32, device=device)
+        self.maxs = torch.empty(rows, dtype=torch.int32, device=device)
+        self._columns = ()
+
+    def launch(self, keys: torch.Tensor, vals: torch.Tensor | None, signed: bool = False,
+               columns=SCAN_BY_KEY_COLUMNS) -> None:
+        """Asynchronous on the current stream; nothing is read back (graph-capturable).  signed: the values are int32
+        (sign-extended sums, signed min and max).  columns: the columns to compute, names of SCAN_BY_KEY_COLUMNS;
+        vals=None allows run_ids and row_numbers only."""
+        _need(keys, torch.int32, "keys")
+        _need16(keys, "keys")
+        if vals is not None:
+            _need(vals, torch.int32, "vals")
+            _need16(vals, "vals")
+        if keys.numel() != self.n or (vals is not None and vals.numel() != self.n):
+            raise ValueError("size mismatch")
+        columns = tuple(columns)
+        if not columns or any(c not in SCAN_BY_KEY_COLUMNS for c in columns):
+            raise ValueError(f"columns: a non-empty subset of {SCAN_BY_KEY_COLUMNS}")
+        if vals is None and any(c in columns for c in SCAN_BY_KEY_COLUMNS[2:]):
+            raise ValueError("sums, mins and maxs need vals")
+        ptrs = [getattr(self, c).data_ptr() if c in columns else None for c in SCAN_BY_KEY_COLUMNS]
+        _capi.check(_capi.lib().dbhip_scan_by_key_u32(
+            keys.data_ptr(), vals.data_ptr() if vals is not None else None, self.n, int(signed), *ptrs, self.ws.data_ptr(),
+            self.ws_bytes, _stream()), "scan_by_key_u32")
+        self._columns = columns
+
+    def result(self):
+        """-> (run_ids, row_numbers, sums, mins, maxs) of the last launch (sums: int64 bit patterns; a column that was not
+        asked for is None), after the status word was read (synchronises)"""
+        _check_status(self.ws, "scan_by_key_u32")
+        return tuple(getattr(self, c)[:self.n] if c in self._columns else None for c in SCAN_BY_KEY_COLUMNS)
+
+
+def scan_by_key(keys: torch.Tensor, vals: torch.Tensor | None, signed: bool = False):
+    """One row per input row over runs of equal adjacent keys -> (run_ids, row_numbers, sums, mins, maxs); vals=None:
+    (run_ids, row_numbers, None, None, None)"""
+    _need(keys, torch.int32, "keys")
+    plan = ScanByKey(keys.numel(), keys.device)
+    plan.launch(keys, vals, signed, SCAN_BY_KEY_COLUMNS if vals is not None else SCAN_BY_KEY_COLUMNS[:2])
+    return plan.result()
+
+
+def check_scan_by_key(keys: torch.Tensor, vals: torch.Tensor | None, run_ids=None, row_numbers=None, sums=None, mins=None,
+                      maxs=None, signed: bool = False):
+    """-> the four words of dbhip_check_scan_by_key_u32: (violations, lowest violating row or 2^64 - 1, heads, 0); a column
+    that is None is skipped"""
+    cols = (run_ids, row_numbers, sums, mins, maxs)
+    for t, name in ((keys, "keys"), (vals, "vals"), (run_ids, "run_ids"), (row_numbers, "row_numbers"), (mins, "mins"),
+                    (maxs, "maxs")):
+        if t is not None:
+            _need(t, torch.int32, name)
+    if sums is not None:
+        _need(sums, torch.int64, "sums")
+    n = keys.numel()
+    if any(t is not None and t.numel() != n for t in (vals,) + cols):
+        raise ValueError("size mismatch")
+    ws = _ws(_capi.lib().dbhip_check_scan_by_key_workspace_bytes(n), keys.device)
+    res = _result(4, keys.device)
+    _capi.check(_capi.lib().dbhip_check_scan_by_key_u32(
+        keys.data_ptr(), vals.data_ptr() if vals is not None else None, n, int(signed),
+        *(t.data_ptr() if t is not None else None for t in cols), res.data_ptr(), ws.data_ptr(), ws.numel(), _stream()),
+        "check_scan_by_key_u32")
+    return tuple(_u64(res))
+
+
+def window_sorted(keys: torch.Tensor, vals: torch.Tensor, signed: bool = False, signed_keys: bool = False):
+    """The window functions over PARTITION BY keys ORDER BY <row order> ROWS BETWEEN UNBOUNDED PRECEDING AND CURRENT ROW
+    -> (sorted_keys, row_ids, run_ids, row_numbers, sums, mins, maxs), one entry per input row in (key, row) order.
+    Copies the keys, argsorts the copy with the stable pairs sort on row ids, gathers the values and scans by key: the
+    sort's stability makes the window order the original row order within each key.  row_ids[j] is the input row of output
+    row j (scatter the results back with it); run_ids[j] is its row in groupby_sorted's result.  signed: the values are
+    int32; signed_keys: the keys ascend as int32."""
+    _need(keys, torch.int32, "keys")
+    _need(vals, torch.int32, "vals")
+    if keys.numel() != vals.numel():
+        raise ValueError("size mismatch")
+    k = keys.clone()
+    row_ids = radix_argsort_(k, signed=signed_keys)
+    v = gather_u32(vals, row_ids)
+    return (k, row_ids) + scan_by_key(k, v, signed=signed)
+
+
+# ---------------------------------------------------------------------------------------------
 # dwarf 3: group-by SUM
 # ---------------------------------------------------------------------------------------------
 class GroupBySum:

@@ -26,6 +26,14 @@ the contract numbers come from bench.py.
                   return_counts) + the same scatters.  Every answer checked by dbhip_check_reduce_by_key_u32
   launch-groupby-sorted [lg] five reduce calls each on sorted keys with 64, 2^20 and n runs at 2^lg rows, nothing else
                   (`rocprofv3 --kernel-trace --stats`)
+  window [lg]     dbhip_scan_by_key_u32 at 2^lg rows (default 24).  Part 1, grouped input (the shapes of groupby-sorted):
+                  ScanByKey.launch with all five columns against the torch composition of the same columns (cumsum for the run
+                  numbers and the sums, cummax for the row numbers, cummin / cummax over the composite int64 words
+                  ((R-1-run) << 32 | x) and (run << 32 | x) for the extremes), in one process, alternating, REPS (default 5)
+                  repetitions of a median of 5; beside it the time of 16n + 24n bytes at 8 TB/s.  Part 2, the same keys
+                  shuffled: copy + argsort + gather + scan (ops.window_sorted's launches).  Every answer checked by
+                  dbhip_check_scan_by_key_u32 and, in part 1, against the torch columns
+  launch-window [lg] five scan-by-key calls on every grouped shape at 2^lg rows, nothing else (`rocprofv3 --kernel-trace`)
   join-pairs [lg] the join's pair table (dbhip_join_pairs_u32: scan + expansion, one call, capacity given) on the radix join's
                   answer at 2^20 / 2^24 / 2^26 rows a side (or 2^lg alone) with keys in [1, n], and on 2^13 x 2^13 rows of one
                   key (2^26 pairs); beside it the count-only call and, in the same process on the same (ids, pos, cnt), the
@@ -337,6 +345,89 @@ def launch_groupby_sorted(lg):
         for _ in range(5):
             plan.launch(keys, vals)
         plan.result()
+    print("ok")
+
+
+def _torch_window(keys, vals64):
+    """the five columns of dbhip_scan_by_key_u32 (unsigned values below 2^31) from torch's scans"""
+    n = keys.numel()
+    rows = torch.arange(n, dtype=torch.int64, device="cuda")
+    head = torch.ones(n, dtype=torch.bool, device="cuda")
+    head[1:] = keys[1:] != keys[:-1]
+    run = torch.cumsum(head, 0) - 1
+    head_row = torch.cummax(torch.where(head, rows, torch.zeros_like(rows)), 0).values
+    total = torch.cumsum(vals64, 0)
+    sums = total - (total - vals64)[head_row]
+    mins = torch.cummin(((run[-1] - run) << 32) | vals64, 0).values & 0xFFFFFFFF
+    maxs = torch.cummax((run << 32) | vals64, 0).values & 0xFFFFFFFF
+    return run, rows - head_row + 1, sums, mins, maxs
+
+
+def window(lg):
+    n = 1 << (lg or 24)
+    reps = int(os.environ.get("REPS", "5"))
+    vals = ops.gen_uniform_u32(n, 43, 1, 10000)
+    vals64 = vals.to(torch.int64)
+
+    def report(part, name, R, legs, ok, model=None):
+        cols = "  ".join(f"{leg} {min(ts):9.1f} .. {max(ts):9.1f} us" for leg, ts in legs.items())
+        extra = f"  model {model:7.1f} us" if model else ""
+        print(f"{TAG:10s} {part} n=2^{lg or 24} {name:14s} runs={R:9d}  {cols}{extra}  {'ok' if ok else 'WRONG'}   "
+              + " ".join(f"{leg}:" + "/".join(f"{t:.1f}" for t in ts) for leg, ts in legs.items()), flush=True)
+
+    for name, keys, R in _sorted_key_shapes(n):
+        plan = ops.ScanByKey(n)
+
+        def scan_call():
+            plan.launch(keys, vals)
+
+        def vendor():
+            return _torch_window(keys, vals64)
+
+        legs = {"scan_by_key": [], "torch": []}
+        for _ in range(reps):  # alternating
+            legs["scan_by_key"].append(median(times(scan_call, 5)))
+            legs["torch"].append(median(times(vendor, 5)))
+        scan_call()
+        got = plan.result()
+        words = ops.check_scan_by_key(keys, vals, *got)
+        want = vendor()
+        ok = words[0] == 0 and words[2] == R and all(torch.equal(g.to(torch.int64), w) for g, w in zip(got, want))
+        report("grouped ", name, R, legs, ok, model=40 * n / 8e12 * 1e6)
+        del plan, got, want
+
+        # part 2: the same groups in no order
+        shuffled = keys[torch.randperm(n, device="cuda")]
+        srt = ops.RadixSortPairs(n, 8)
+        plan = ops.ScanByKey(n)
+        k2 = torch.empty_like(shuffled)
+        kept = {}
+
+        def sort_route():
+            k2.copy_(shuffled)
+            kept["v"] = ops.gather_u32(vals, srt.launch(k2, None))
+            plan.launch(k2, kept["v"])
+
+        legs = {"window_sorted": []}
+        for _ in range(reps):
+            legs["window_sorted"].append(median(times(sort_route, 5)))
+        sort_route()
+        got = plan.result()
+        words = ops.check_scan_by_key(k2, kept["v"], *got)
+        ok = words[0] == 0 and words[2] == R and ops.workspace_status(srt.ws) == 0 and ops.check_sorted(k2)[0] == 0
+        report("unsorted", name, R, legs, ok)
+        del plan, srt, shuffled, k2, got, kept
+
+
+def launch_window(lg):
+    n = 1 << (lg or 24)
+    vals = ops.gen_uniform_u32(n, 43, 1, 10000)
+    for name, keys, R in _sorted_key_shapes(n):
+        plan = ops.ScanByKey(n)
+        for _ in range(5):
+            plan.launch(keys, vals)
+        plan.result()
+        print(name, R, flush=True)
     print("ok")
 
 
@@ -1095,7 +1186,8 @@ MODES = {"radix": radix, "ramp": ramp, "radix-idle": radix_idle, "radix-stream":
          "reduce": reduce, "xscan": xscan, "cuckoo": cuckoo, "slab": slab,
          "groupby-hash": groupby_hash, "sort-pairs": sort_pairs, "launch-sort-pairs": launch_sort_pairs,
          "join-pairs": join_pairs, "launch-join-pairs": launch_join_pairs, "topk": topk, "launch-topk": launch_topk,
-         "groupby-sorted": groupby_sorted, "launch-groupby-sorted": launch_groupby_sorted}
+         "groupby-sorted": groupby_sorted, "launch-groupby-sorted": launch_groupby_sorted,
+         "window": window, "launch-window": launch_window}
 
 if __name__ == "__main__":
     if len(sys.argv) < 2 or sys.argv[1] not in MODES:
