@@ -51,12 +51,6 @@ namespace {
 constexpr int kCkThreads = 256;
 constexpr unsigned long long kFpMul = 0x9E3779B97F4A7C15ull;  // odd: invertible mod 2^64
 
-inline unsigned ck_grid(size_t n, const DeviceInfo &dev, int per_cu = 8) {
-  const size_t want = (n + kCkThreads - 1) / kCkThreads;
-  const size_t cap = static_cast<size_t>(dev.cus) * per_cu;
-  return static_cast<unsigned>(want < cap ? (want ? want : 1) : cap);
-}
-
 __device__ __forceinline__ unsigned long long fp_pow(unsigned long long e) {
   unsigned long long r = 1, b = kFpMul;
   while (e) {
@@ -399,7 +393,7 @@ extern "C" int dbhip_check_sorted_u32(const uint32_t *keys, size_t n, int signed
   const hipError_t e = fill_async(result, 0, 3 * sizeof(uint64_t), s);
   if (e != hipSuccess) return static_cast<int>(e);
   if (n == 0) return DBHIP_OK;
-  hipLaunchKernelGGL(sorted_kernel, dim3(ck_grid(n, dev)), dim3(kCkThreads), 0, s, keys, n,
+  hipLaunchKernelGGL(sorted_kernel, dim3(capped_grid(n, kCkThreads, dev)), dim3(kCkThreads), 0, s, keys, n,
                      signed_order ? 0x80000000u : 0u, reinterpret_cast<unsigned long long *>(result));
   return launch_status();
 }
@@ -413,8 +407,8 @@ extern "C" int dbhip_check_sorted_pairs_u32(const uint32_t *keys_in, const uint3
   const hipError_t e = fill_async(result, 0, 2 * sizeof(uint64_t), s);
   if (e != hipSuccess) return static_cast<int>(e);
   if (n == 0) return DBHIP_OK;
-  hipLaunchKernelGGL(sorted_pairs_kernel, dim3(ck_grid(n, dev)), dim3(kCkThreads), 0, s, keys_in, keys_out, ids_out, n,
-                     signed_order ? 0x80000000u : 0u, reinterpret_cast<unsigned long long *>(result));
+  hipLaunchKernelGGL(sorted_pairs_kernel, dim3(capped_grid(n, kCkThreads, dev)), dim3(kCkThreads), 0, s, keys_in, keys_out,
+                     ids_out, n, signed_order ? 0x80000000u : 0u, reinterpret_cast<unsigned long long *>(result));
   return launch_status();
 }
 
@@ -427,7 +421,7 @@ extern "C" int dbhip_check_weighted_sum_u32(const uint32_t *keys, const uint32_t
   const hipError_t e = fill_async(result, 0, 2 * sizeof(uint64_t), s);
   if (e != hipSuccess) return static_cast<int>(e);
   if (n == 0) return DBHIP_OK;
-  hipLaunchKernelGGL(weighted_sum_kernel, dim3(ck_grid(n, dev)), dim3(kCkThreads), 0, s, keys, vals, n,
+  hipLaunchKernelGGL(weighted_sum_kernel, dim3(capped_grid(n, kCkThreads, dev)), dim3(kCkThreads), 0, s, keys, vals, n,
                      reinterpret_cast<unsigned long long *>(result));
   return launch_status();
 }
@@ -448,7 +442,7 @@ extern "C" int dbhip_check_permutation_u32(const uint32_t *ids, size_t n, uint64
   if (e != hipSuccess) return static_cast<int>(e);
   if (n == 0) return DBHIP_OK;
   unsigned *bitmap = reinterpret_cast<unsigned *>(static_cast<char *>(workspace) + kWsHeader);
-  hipLaunchKernelGGL(permutation_kernel, dim3(ck_grid(n, dev)), dim3(kCkThreads), 0, s, ids, n, bitmap,
+  hipLaunchKernelGGL(permutation_kernel, dim3(capped_grid(n, kCkThreads, dev)), dim3(kCkThreads), 0, s, ids, n, bitmap,
                      reinterpret_cast<unsigned long long *>(result));
   return launch_status();
 }
@@ -468,7 +462,8 @@ extern "C" int dbhip_check_join_u32(const uint32_t *sorted_build_keys, size_t n_
   if (e != hipSuccess) return static_cast<int>(e);
   if (n_probe == 0) return DBHIP_OK;
   const GenSpec gen{gen_seed, static_cast<unsigned long long>(gen_hi) - gen_lo + 1, gen_lo};
-  hipLaunchKernelGGL(join_check_kernel, dim3(ck_grid(n_probe > n_build ? n_probe : n_build, dev)), dim3(kCkThreads), 0, s,
+  hipLaunchKernelGGL(join_check_kernel, dim3(capped_grid(n_probe > n_build ? n_probe : n_build, kCkThreads, dev)),
+                     dim3(kCkThreads), 0, s,
                      sorted_build_keys, n_build, probe_keys, n_probe, out_pos, out_count, ids, build_keys, gen,
                      reinterpret_cast<unsigned long long *>(result));
   return launch_status();
@@ -487,8 +482,8 @@ extern "C" int dbhip_check_ujoin_u32(const uint32_t *sorted_build_keys, const ui
   const hipError_t e = fill_async(result, 0, 2 * sizeof(uint64_t), s);
   if (e != hipSuccess) return static_cast<int>(e);
   if (n_probe == 0) return DBHIP_OK;
-  hipLaunchKernelGGL(ujoin_check_kernel, dim3(ck_grid(n_probe, dev)), dim3(kCkThreads), 0, s, sorted_build_keys,
-                     build_vals, n_build, probe_keys, probe_vals, n_probe, out_key, out_build_val, out_probe_val,
+  hipLaunchKernelGGL(ujoin_check_kernel, dim3(capped_grid(n_probe, kCkThreads, dev)), dim3(kCkThreads), 0, s,
+                     sorted_build_keys, build_vals, n_build, probe_keys, probe_vals, n_probe, out_key, out_build_val, out_probe_val,
                      reinterpret_cast<unsigned long long *>(result));
   return launch_status();
 }
@@ -516,7 +511,7 @@ extern "C" int dbhip_check_distinct_u32(const uint32_t *keys, size_t n, uint64_t
   if (e != hipSuccess) return static_cast<int>(e);
   const int rc = dbhip_radix_sort_u32(copy, tmp, n, 8, static_cast<char *>(workspace) + 2 * col, workspace_bytes - 2 * col, stream);
   if (rc != 0) return rc;
-  hipLaunchKernelGGL(not_increasing_kernel, dim3(ck_grid(n, dev)), dim3(kCkThreads), 0, s, copy, n,
+  hipLaunchKernelGGL(not_increasing_kernel, dim3(capped_grid(n, kCkThreads, dev)), dim3(kCkThreads), 0, s, copy, n,
                      reinterpret_cast<unsigned long long *>(result));
   return launch_status();
 }
@@ -532,7 +527,7 @@ extern "C" int dbhip_check_gen_uniform_u32(const uint32_t *values, const uint32_
   if (e != hipSuccess) return static_cast<int>(e);
   if (n == 0) return DBHIP_OK;
   const GenSpec gen{seed, static_cast<unsigned long long>(hi) - lo + 1, lo};
-  hipLaunchKernelGGL(gen_check_kernel, dim3(ck_grid(n, dev)), dim3(kCkThreads), 0, s, values, indices, n,
+  hipLaunchKernelGGL(gen_check_kernel, dim3(capped_grid(n, kCkThreads, dev)), dim3(kCkThreads), 0, s, values, indices, n,
                      static_cast<unsigned long long>(first_index), gen, reinterpret_cast<unsigned long long *>(result));
   return launch_status();
 }

@@ -1,5 +1,9 @@
 // dbhip_common.hpp — shared device/host helpers for the gfx950 dwarf kernels.
 // Wave = 64 lanes everywhere (CDNA4); nothing here is written for 32-wide warps.
+//   host:    DeviceInfo, the workspace conventions (kWsAlign, kWsHeader, WsStatusHeader, ws_ok, align_up), capped_grid,
+//            fill_async, launch_status
+//   device:  lane_id, mbcnt, wg_barrier_lds_only, the wave scan and reductions (add, 64-bit add, min, max),
+//            block_exclusive_scan, the hashes (mix64, fmix32, murmur3_x86_32_u32)
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stddef.h>
@@ -19,6 +23,13 @@ typedef unsigned u32x4_a8 __attribute__((ext_vector_type(4), aligned(8)));  // 1
 constexpr size_t kWsAlign = 256;   // workspace alignment required from callers
 constexpr size_t kWsHeader = 256;  // [0] status word, rest reserved; cleared by every call
 
+// the header of a workspace that keeps nothing but the status word there
+struct WsStatusHeader {
+  unsigned status;
+  unsigned pad[63];
+};
+static_assert(sizeof(WsStatusHeader) == kWsHeader, "workspace header size");
+
 // ---------------------------------------------------------------------------------------------
 // host-side helpers
 // ---------------------------------------------------------------------------------------------
@@ -36,6 +47,13 @@ inline bool ws_ok(const void *ws, size_t have, size_t need) {
   return ws != nullptr && (reinterpret_cast<uintptr_t>(ws) % kWsAlign) == 0 && have >= need;
 }
 inline int launch_status() { return static_cast<int>(hipGetLastError()); }
+// Grid of a grid-stride kernel over `items` with `threads` per workgroup: one workgroup per `threads` items, at most
+// `per_cu` per compute unit and at least one (a launch over no items still runs its epilogue).
+inline unsigned capped_grid(size_t items, int threads, const DeviceInfo &dev, int per_cu = 8) {
+  const size_t want = (items + threads - 1) / threads;
+  const size_t cap = static_cast<size_t>(dev.cus) * per_cu;
+  return static_cast<unsigned>(want < cap ? (want ? want : 1) : cap);
+}
 
 // Fill `bytes` (a multiple of 4, `p` 4-byte aligned) with the byte `value`, asynchronously, by a kernel of this
 // library (dbhip_util.hip).  Used instead of hipMemsetAsync everywhere: a captured hipMemsetAsync becomes a graph
@@ -87,6 +105,42 @@ __device__ __forceinline__ unsigned long long wave_reduce_add_u64(unsigned long 
   return v;
 }
 
+__device__ __forceinline__ unsigned wave_reduce_min(unsigned v) {
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) {
+    const unsigned o = __shfl_xor(v, off, kWave);
+    v = v < o ? v : o;
+  }
+  return v;
+}
+__device__ __forceinline__ unsigned wave_reduce_max(unsigned v) {
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) {
+    const unsigned o = __shfl_xor(v, off, kWave);
+    v = v > o ? v : o;
+  }
+  return v;
+}
+
+// exclusive prefix sum over the workgroup (kThreads threads, all of them call); total = the workgroup's sum
+template <int kThreads>
+__device__ __forceinline__ unsigned block_exclusive_scan(unsigned v, unsigned *s_wsum, unsigned &total) {
+  constexpr int kWaves = kThreads / kWave;
+  const unsigned lane = threadIdx.x & (kWave - 1), wave = threadIdx.x / kWave;
+  const unsigned incl = wave_inclusive_scan(v);
+  __syncthreads();  // s_wsum may still be read from the call before
+  if (lane == kWave - 1) s_wsum[wave] = incl;
+  __syncthreads();
+  unsigned before = 0, all = 0;
+#pragma unroll
+  for (int w = 0; w < kWaves; ++w) {
+    const unsigned s = s_wsum[w];
+    before += static_cast<unsigned>(w) < wave ? s : 0u;
+    all += s;
+  }
+  total = all;
+  return before + incl - v;
+}
 
 // splitmix64-style counter hash shared with dbo_mix64 in oracle/dbo.c (must stay bit-identical)
 __host__ __device__ __forceinline__ uint64_t mix64(uint64_t seed, uint64_t i) {

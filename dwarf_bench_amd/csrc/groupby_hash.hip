@@ -489,10 +489,7 @@ extern "C" int dbhip_groupby_hash_u32(const uint32_t *keys, const uint32_t *vals
     const unsigned grid = static_cast<unsigned>(steps < static_cast<size_t>(dev.cus) ? (steps ? steps : 1) : dev.cus);
     hipLaunchKernelGGL(gbh_lds_kernel, dim3(grid), dim3(kGbhThreads), lds, s, k4, v4, keys, vals, n, g, hdr);
   } else if (L.path == kPathGlobal) {
-    const size_t blocks = (n + 255) / 256;
-    const size_t cap = static_cast<size_t>(dev.cus) * 8;
-    hipLaunchKernelGGL(gbh_global_kernel, dim3(static_cast<unsigned>(blocks < cap ? blocks : cap)), dim3(256), 0, s, keys,
-                       vals, n, g, hdr);
+    hipLaunchKernelGGL(gbh_global_kernel, dim3(capped_grid(n, 256, dev)), dim3(256), 0, s, keys, vals, n, g, hdr);
   } else {
     const unsigned *pairs = nullptr;
     const unsigned long long *starts = nullptr;
@@ -508,8 +505,7 @@ extern "C" int dbhip_groupby_hash_u32(const uint32_t *keys, const uint32_t *vals
                        reinterpret_cast<const u32x2 *>(pairs), starts, g, hdr, static_cast<const unsigned *>(giants),
                        L.max_giants);
   }
-  const unsigned long long cblocks = (L.slots + 255) / 256, ccap = static_cast<unsigned long long>(dev.cus) * 8;
-  hipLaunchKernelGGL(gbh_compact_kernel, dim3(static_cast<unsigned>(cblocks < ccap ? cblocks : ccap)), dim3(256), 0, s, g, out);
+  hipLaunchKernelGGL(gbh_compact_kernel, dim3(capped_grid(L.slots, 256, dev)), dim3(256), 0, s, g, out);
   hipLaunchKernelGGL(gbh_finish_kernel, dim3(1), dim3(kWave), 0, s, out, reinterpret_cast<unsigned long long *>(out_groups));
   return launch_status();
 }

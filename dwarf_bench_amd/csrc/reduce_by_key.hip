@@ -1,12 +1,11 @@
 // reduce_by_key.hip — one output row per run of equal adjacent keys for gfx950: COUNT, exact 64-bit SUM, MIN, MAX
 // (include/dbhip_reduce_by_key.h).  Behind the stable pairs sort this is GROUP BY key ORDER BY key.
 //
-// No reference counterpart.  A HEAD is row 0 or a row whose key differs from its left neighbour's; run r is the rows from
-// the r-th head to the row in front of the next one.  MIN and MAX work on x = value ^ sign (sign = 0x80000000 with
-// vals_signed), for which smaller means smaller as unsigned; the SUM adds the value itself, zero- or sign-extended.
+// No reference counterpart.  HEAD, run, the x domain, SEGMENT, chunk and step are defined in by_key.hpp, which also holds
+// the open run's aggregate (BkAgg) and its segmented wave scan.
 //
 // All dependent launches, no workgroup ever waits on another (DESIGN.md findings 8 and 9), no CAS loop, every loop bounded
-// by n.  A wave owns a 4096-row SEGMENT, a workgroup eight of them (a 32768-row chunk):
+// by n:
 //   fill        clears the header
 //   rk_count    one streaming read of the keys: the heads of every segment (the left neighbour of a segment's first row
 //               is read from memory)
@@ -24,13 +23,10 @@
 //               closes at the column's end.  A scan, not a walk: a column that is one run is n / 4096 records behind one head.
 //
 // workspace: header | cnt[segments] | pos[segments] | rec[segments] (48 bytes); every part at a 256-byte offset
-#include "../../include/dbhip_reduce_by_key.h"
-#include "dbhip_common.hpp"
+#include "by_key.hpp"
 
 namespace dbhip {
 namespace {
-
-typedef unsigned long long u64;
 
 constexpr int kRkThreads = 512;
 constexpr int kRkWaves = kRkThreads / kWave;
@@ -40,12 +36,6 @@ static_assert(kRkChunk == kRkSegment * kRkWaves, "a chunk is one segment per wav
 constexpr size_t kRkStep = 4 * kWave;  // rows a wave takes at a time: four consecutive rows per lane
 static_assert(kRkSegment % (2 * kRkStep) == 0, "a segment is a whole number of steps");
 constexpr int kRkScanThreads = 1024;
-
-struct RkHeader {
-  unsigned status;
-  unsigned pad[63];
-};
-static_assert(sizeof(RkHeader) == kWsHeader, "workspace header size");
 
 // what a segment leaves for rk_stitch; mn and mx in the x domain
 struct RkPart {
@@ -77,32 +67,6 @@ struct RkOut {
   unsigned *mins, *maxs;
   u64 capacity;
 };
-
-__device__ __forceinline__ u64 rk_ext(unsigned v, bool is_signed) {
-  return is_signed ? static_cast<u64>(static_cast<long long>(static_cast<int>(v))) : static_cast<u64>(v);
-}
-__device__ __forceinline__ unsigned rk_min(unsigned a, unsigned b) { return a < b ? a : b; }
-__device__ __forceinline__ unsigned rk_max(unsigned a, unsigned b) { return a > b ? a : b; }
-
-// exclusive prefix sum over the workgroup (kThreads threads, all of them call); total = the workgroup's sum (topk.hip)
-template <int kThreads>
-__device__ __forceinline__ unsigned rk_block_exclusive_scan(unsigned v, unsigned *s_wsum, unsigned &total) {
-  constexpr int kWaves = kThreads / kWave;
-  const unsigned lane = threadIdx.x & (kWave - 1), wave = threadIdx.x / kWave;
-  const unsigned incl = wave_inclusive_scan(v);
-  __syncthreads();  // s_wsum may still be read from the call before
-  if (lane == kWave - 1) s_wsum[wave] = incl;
-  __syncthreads();
-  unsigned before = 0, all = 0;
-#pragma unroll
-  for (int w = 0; w < kWaves; ++w) {
-    const unsigned s = s_wsum[w];
-    before += static_cast<unsigned>(w) < wave ? s : 0u;
-    all += s;
-  }
-  total = all;
-  return before + incl - v;
-}
 
 // ---- count -------------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(kRkThreads) void rk_count_kernel(const unsigned *__restrict__ keys, size_t n,
@@ -138,7 +102,7 @@ __global__ __launch_bounds__(kRkThreads) void rk_count_kernel(const unsigned *__
 }
 
 // ---- scan: one workgroup -------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(kRkScanThreads) void rk_scan_kernel(RkHeader *hdr, const unsigned *__restrict__ cnt,
+__global__ __launch_bounds__(kRkScanThreads) void rk_scan_kernel(WsStatusHeader *hdr, const unsigned *__restrict__ cnt,
                                                                  unsigned *__restrict__ pos, size_t segments, u64 capacity,
                                                                  int count_only, u64 *out_runs) {
   __shared__ unsigned s_wsum[kRkScanThreads / kWave];
@@ -147,7 +111,7 @@ __global__ __launch_bounds__(kRkScanThreads) void rk_scan_kernel(RkHeader *hdr, 
     const size_t seg = base + threadIdx.x;
     const unsigned c = seg < segments ? cnt[seg] : 0u;
     unsigned total;
-    const unsigned before = rk_block_exclusive_scan<kRkScanThreads>(c, s_wsum, total);
+    const unsigned before = block_exclusive_scan<kRkScanThreads>(c, s_wsum, total);
     if (seg < segments) pos[seg] = run + before;
     run += total;
   }
@@ -158,58 +122,6 @@ __global__ __launch_bounds__(kRkScanThreads) void rk_scan_kernel(RkHeader *hdr, 
 }
 
 // ---- reduce ------------------------------------------------------------------------------------------------------------
-// the rows from the last head (or from the segment's first row) up to some row: lh = 1 + the head's row inside the
-// segment, 0 when there is no head yet; sum, mn, mx over the rows behind that point
-struct RkAgg {
-  unsigned lh, mn, mx;
-  u64 sum;
-};
-__device__ __forceinline__ RkAgg rk_none() { return RkAgg{0u, 0xFFFFFFFFu, 0u, 0ull}; }
-// a = l (+) a: the rows of l directly in front of the rows of a
-__device__ __forceinline__ void rk_prepend(RkAgg &a, const RkAgg &l) {
-  if (a.lh == 0) {
-    a.lh = l.lh;
-    a.sum += l.sum;
-    a.mn = rk_min(a.mn, l.mn);
-    a.mx = rk_max(a.mx, l.mx);
-  }
-}
-template <int kCtrl, int kRowMask>
-__device__ __forceinline__ RkAgg rk_dpp(const RkAgg &a) {  // lanes without a source get rk_none()
-  RkAgg l;
-  l.lh = __builtin_amdgcn_update_dpp(0u, a.lh, kCtrl, kRowMask, 0xf, false);
-  l.mn = __builtin_amdgcn_update_dpp(0xFFFFFFFFu, a.mn, kCtrl, kRowMask, 0xf, false);
-  l.mx = __builtin_amdgcn_update_dpp(0u, a.mx, kCtrl, kRowMask, 0xf, false);
-  const unsigned lo = __builtin_amdgcn_update_dpp(0u, static_cast<unsigned>(a.sum), kCtrl, kRowMask, 0xf, false);
-  const unsigned hi = __builtin_amdgcn_update_dpp(0u, static_cast<unsigned>(a.sum >> 32), kCtrl, kRowMask, 0xf, false);
-  l.sum = (static_cast<u64>(hi) << 32) | lo;
-  return l;
-}
-template <int kCtrl, int kRowMask>
-__device__ __forceinline__ void rk_scan_step(RkAgg &a) {
-  const RkAgg l = rk_dpp<kCtrl, kRowMask>(a);
-  rk_prepend(a, l);
-}
-// inclusive segmented scan over the wave's lanes, the DPP ladder of wave_inclusive_scan
-__device__ __forceinline__ void rk_wave_scan(RkAgg &a) {
-  rk_scan_step<0x111, 0xf>(a);  // row_shr:1
-  rk_scan_step<0x112, 0xf>(a);  // row_shr:2
-  rk_scan_step<0x114, 0xf>(a);  // row_shr:4
-  rk_scan_step<0x118, 0xf>(a);  // row_shr:8
-  rk_scan_step<0x142, 0xa>(a);  // row_bcast:15 -> rows 1,3
-  rk_scan_step<0x143, 0xc>(a);  // row_bcast:31 -> rows 2,3
-}
-__device__ __forceinline__ unsigned rk_wave_min(unsigned v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v = rk_min(v, __shfl_xor(v, off, kWave));
-  return v;
-}
-__device__ __forceinline__ unsigned rk_wave_max(unsigned v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v = rk_max(v, __shfl_xor(v, off, kWave));
-  return v;
-}
-
 __device__ __forceinline__ void rk_write_run(const RkOut &out, u64 r, unsigned count, u64 sum, unsigned mn, unsigned mx,
                                              unsigned sign) {
   if (r >= out.capacity) return;
@@ -232,29 +144,20 @@ __global__ __launch_bounds__(kRkThreads) void rk_reduce_kernel(const unsigned *_
   const bool full = last - first == kRkSegment;
   const u64 base_run = pos[seg];
   unsigned left = first ? keys[first - 1] : 0u;  // key of the row in front of the rows in hand (wave-uniform)
-  RkAgg carry = rk_none();  // what is open in front of the rows in hand (wave-uniform) ...
-  RkAgg acc = rk_none();    // ... together with these per-lane sums of steps that had no head (lh unused)
+  BkAgg carry = bk_none();  // what is open in front of the rows in hand (wave-uniform) ...
+  BkAgg acc = bk_none();    // ... together with these per-lane sums of steps that had no head (lh unused)
   bool acc_used = false;
   unsigned heads_before = 0;  // heads of the segment in front of the rows in hand (wave-uniform)
 
-  auto load = [&](size_t row0, u32x4 &k, u32x4 &v) {
-    if (full) {  // segment starts are multiples of 4096 rows, the columns 16-byte aligned
-      k = __builtin_nontemporal_load(reinterpret_cast<const u32x4 *>(keys + row0));
-      v = vals ? __builtin_nontemporal_load(reinterpret_cast<const u32x4 *>(vals + row0)) : u32x4{0u, 0u, 0u, 0u};
-    } else {
-#pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        k[q] = row0 + q < last ? keys[row0 + q] : 0u;
-        v[q] = (vals && row0 + q < last) ? vals[row0 + q] : 0u;
-      }
-    }
-  };
+  // bk_load on this segment.  Through a lambda, as the loads were before by_key.hpp: called directly the kernel is
+  // the same instructions with two VGPR names exchanged.
+  auto load = [&](size_t row0, u32x4 &k, u32x4 &v) { bk_load(keys, vals, full, row0, last, k, v); };
   auto fold_acc = [&]() {  // the per-lane sums into the carry
     if (!acc_used) return;
     carry.sum += wave_reduce_add_u64(acc.sum);
-    carry.mn = rk_min(carry.mn, rk_wave_min(acc.mn));
-    carry.mx = rk_max(carry.mx, rk_wave_max(acc.mx));
-    acc = rk_none();
+    carry.mn = bk_min(carry.mn, wave_reduce_min(acc.mn));
+    carry.mx = bk_max(carry.mx, wave_reduce_max(acc.mx));
+    acc = bk_none();
     acc_used = false;
   };
 
@@ -264,31 +167,32 @@ __global__ __launch_bounds__(kRkThreads) void rk_reduce_kernel(const unsigned *_
     const size_t row0 = base + 4 * lane;  // this lane's four consecutive rows
     const unsigned rel0 = static_cast<unsigned>(row0 - first);
     const u32x4 k = k4, v = v4;
-    if (base + kRkStep < last) load(row0 + kRkStep, k4, v4);  // the next step's rows, in flight over this one
+    if (base + kRkStep < last) load(row0 + kRkStep, k4, v4);  // in flight over this step
+    // the previous key and the loop over the lane's rows are those of sk_scan_kernel (scan_by_key.hip)
     bool valid[4], head[4];
     unsigned x[4];
     unsigned prev = __builtin_amdgcn_update_dpp(0u, k[3], 0x138, 0xf, 0xf, false);  // wave_shr:1
     if (lane == 0) prev = left;
     left = __builtin_amdgcn_readlane(k[3], kWave - 1);
     unsigned n_heads = 0;
-    RkAgg a = rk_none();
+    BkAgg a = bk_none();
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
       valid[q] = full || row0 + q < last;
       x[q] = v[q] ^ sign;
       head[q] = valid[q] && (q ? k[q] != k[q - 1] : (row0 == 0 || k[0] != prev));
       n_heads += head[q] ? 1u : 0u;
-      if (head[q]) a = RkAgg{rel0 + q + 1, 0xFFFFFFFFu, 0u, 0ull};
+      if (head[q]) a = BkAgg{rel0 + q + 1, 0xFFFFFFFFu, 0u, 0ull};
       if (valid[q]) {
-        a.sum += rk_ext(v[q], is_signed);
-        a.mn = rk_min(a.mn, x[q]);
-        a.mx = rk_max(a.mx, x[q]);
+        a.sum += bk_ext(v[q], is_signed);
+        a.mn = bk_min(a.mn, x[q]);
+        a.mx = bk_max(a.mx, x[q]);
       }
     }
     if (__ballot(n_heads != 0) == 0) {  // no head in the wave's rows: a plain sum, reduced over the wave later
       acc.sum += a.sum;
-      acc.mn = rk_min(acc.mn, a.mn);
-      acc.mx = rk_max(acc.mx, a.mx);
+      acc.mn = bk_min(acc.mn, a.mn);
+      acc.mx = bk_max(acc.mx, a.mx);
       acc_used = true;
       continue;
     }
@@ -296,18 +200,18 @@ __global__ __launch_bounds__(kRkThreads) void rk_reduce_kernel(const unsigned *_
     const unsigned h_incl = wave_inclusive_scan(n_heads);
     unsigned h_before = heads_before + h_incl - n_heads;  // heads of the segment in front of this lane's rows
     heads_before += __builtin_amdgcn_readlane(h_incl, kWave - 1);
-    RkAgg incl = a;
-    rk_wave_scan(incl);
-    RkAgg open = rk_dpp<0x138, 0xf>(incl);  // wave_shr:1: what the lanes in front of this one leave open
-    rk_prepend(open, carry);
-    RkAgg total;
+    BkAgg incl = a;
+    bk_wave_scan<true>(incl);
+    BkAgg open = bk_dpp<0x138, 0xf>(incl);  // wave_shr:1: what the lanes in front of this one leave open
+    bk_prepend<true>(open, carry);
+    BkAgg total;  // the last lane's; down to `carry = total` as in sk_scan_kernel
     total.lh = __builtin_amdgcn_readlane(incl.lh, kWave - 1);
     total.mn = __builtin_amdgcn_readlane(incl.mn, kWave - 1);
     total.mx = __builtin_amdgcn_readlane(incl.mx, kWave - 1);
     const unsigned total_hi = __builtin_amdgcn_readlane(static_cast<unsigned>(incl.sum >> 32), kWave - 1);
     const unsigned total_lo = __builtin_amdgcn_readlane(static_cast<unsigned>(incl.sum), kWave - 1);  // (readlane gives an int)
     total.sum = (static_cast<u64>(total_hi) << 32) | total_lo;
-    rk_prepend(total, carry);
+    bk_prepend<true>(total, carry);
     carry = total;
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
@@ -320,12 +224,12 @@ __global__ __launch_bounds__(kRkThreads) void rk_reduce_kernel(const unsigned *_
           rk_write_run(out, r - 1, rel0 + q - (open.lh - 1), open.sum, open.mn, open.mx, sign);
         }
         ++h_before;
-        open = RkAgg{rel0 + q + 1, 0xFFFFFFFFu, 0u, 0ull};
+        open = BkAgg{rel0 + q + 1, 0xFFFFFFFFu, 0u, 0ull};
       }
       if (valid[q]) {
-        open.sum += rk_ext(v[q], is_signed);
-        open.mn = rk_min(open.mn, x[q]);
-        open.mx = rk_max(open.mx, x[q]);
+        open.sum += bk_ext(v[q], is_signed);
+        open.mn = bk_min(open.mn, x[q]);
+        open.mx = bk_max(open.mx, x[q]);
       }
     }
   }
@@ -346,8 +250,8 @@ __device__ __forceinline__ void rk_part_prepend(RkPart &a, const RkPart &l) {
   if (!a.flag) {
     a.sum += l.sum;
     a.cnt += l.cnt;
-    a.mn = rk_min(a.mn, l.mn);
-    a.mx = rk_max(a.mx, l.mx);
+    a.mn = bk_min(a.mn, l.mn);
+    a.mx = bk_max(a.mx, l.mx);
     a.flag = l.flag;
   }
 }
@@ -523,7 +427,7 @@ __global__ __launch_bounds__(kRkCheckThreads) void rk_check_rows_kernel(
     unsigned seen = (x == mn ? 1u : 0u) | (x == mx ? 2u : 0u);
     if (seen) seen &= ~flags[lo];  // set only when not yet set
     if (seen) atomicOr(&flags[lo], seen);
-    wsum += rk_ext(v, sign != 0) * rk_weight(lo);
+    wsum += bk_ext(v, sign != 0) * rk_weight(lo);
   }
   rk_check_flush(faults, wsum, result, 0, 2, s_part);
 }
@@ -540,12 +444,6 @@ __global__ __launch_bounds__(kRkCheckThreads) void rk_check_final_kernel(const u
   }
   const u64 wrong_total = (blockIdx.x == 0 && threadIdx.x == 0 && hdr->total != n) ? 1u : 0u;
   rk_check_flush(wrong_total, unseen, result, 0, 1, s_part);
-}
-
-inline unsigned rk_check_grid(size_t items, const DeviceInfo &dev) {
-  const size_t want = (items + kRkCheckThreads - 1) / kRkCheckThreads;
-  const size_t cap = static_cast<size_t>(dev.cus) * 8;
-  return static_cast<unsigned>(want < cap ? (want ? want : 1) : cap);
 }
 
 }  // namespace
@@ -588,7 +486,7 @@ extern "C" int dbhip_reduce_by_key_u32(const uint32_t *keys, const uint32_t *val
   const DeviceInfo &dev = current_device_info();
   if (!dev.ok) return DBHIP_ENODEVICE;
   char *base = static_cast<char *>(workspace);
-  RkHeader *hdr = reinterpret_cast<RkHeader *>(base);
+  WsStatusHeader *hdr = reinterpret_cast<WsStatusHeader *>(base);
   unsigned *cnt = reinterpret_cast<unsigned *>(base + l.cnt);
   unsigned *pos = reinterpret_cast<unsigned *>(base + l.pos);
   RkRec *rec = reinterpret_cast<RkRec *>(base + l.rec);
@@ -638,13 +536,13 @@ extern "C" int dbhip_check_reduce_by_key_u32(const uint32_t *keys, const uint32_
   if (runs) {
     const int rc = dbhip_exclusive_scan_u32(out_counts, runs, 0u, starts, base + l.scan_ws, l.scan_bytes, stream);
     if (rc != DBHIP_OK) return rc;
-    hipLaunchKernelGGL(rk_check_runs_kernel, dim3(rk_check_grid(runs, dev)), dim3(kRkCheckThreads), 0, s, keys, n, out_keys,
-                       out_counts, reinterpret_cast<const u64 *>(out_sums), starts, runs, hdr, res);
+    hipLaunchKernelGGL(rk_check_runs_kernel, dim3(capped_grid(runs, kRkCheckThreads, dev)), dim3(kRkCheckThreads), 0, s,
+                       keys, n, out_keys, out_counts, reinterpret_cast<const u64 *>(out_sums), starts, runs, hdr, res);
   }
   if (n)
-    hipLaunchKernelGGL(rk_check_rows_kernel, dim3(rk_check_grid(n, dev)), dim3(kRkCheckThreads), 0, s, keys, vals, n,
-                       vals_signed ? 0x80000000u : 0u, out_keys, out_mins, out_maxs, starts, runs, hdr, flags, res);
-  hipLaunchKernelGGL(rk_check_final_kernel, dim3(rk_check_grid(runs, dev)), dim3(kRkCheckThreads), 0, s, flags, runs, n, hdr,
-                     res);
+    hipLaunchKernelGGL(rk_check_rows_kernel, dim3(capped_grid(n, kRkCheckThreads, dev)), dim3(kRkCheckThreads), 0, s, keys,
+                       vals, n, vals_signed ? 0x80000000u : 0u, out_keys, out_mins, out_maxs, starts, runs, hdr, flags, res);
+  hipLaunchKernelGGL(rk_check_final_kernel, dim3(capped_grid(runs, kRkCheckThreads, dev)), dim3(kRkCheckThreads), 0, s,
+                     flags, runs, n, hdr, res);
   return launch_status();
 }

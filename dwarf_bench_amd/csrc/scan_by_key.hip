@@ -2,9 +2,8 @@
 // COUNT, exact 64-bit SUM, MIN and MAX (include/dbhip_scan_by_key.h).  Behind the stable pairs sort these are the window
 // functions over PARTITION BY key ... ROWS BETWEEN UNBOUNDED PRECEDING AND CURRENT ROW.
 //
-// No reference counterpart.  Heads, runs and the x = value ^ sign domain of MIN and MAX are those of reduce_by_key.hip, and
-// so are the 4096-row SEGMENT of a wave, the 32768-row chunk of a workgroup and the segmented DPP wave scan (sk_wave_scan is
-// rk_wave_scan, copied: the two files share no code object).
+// No reference counterpart.  HEAD, run, the x domain, SEGMENT, chunk and step are defined in by_key.hpp, which also holds
+// the open run's aggregate (BkAgg) and its segmented wave scan; the run number is the run's row in reduce_by_key.hip's table.
 //
 // All dependent launches, no workgroup ever waits on another (DESIGN.md findings 8 and 9), no CAS loop, every loop bounded
 // by n:
@@ -23,14 +22,10 @@
 //             selects.  The ragged last segment loads and stores row by row.
 //
 // workspace: header | rec[segments] (32 bytes) | carry[segments] (32 bytes); every part at a 256-byte offset
-#include "../../include/dbhip_scan_by_key.h"
-#include "dbhip_common.hpp"
+#include "by_key.hpp"
 
 namespace dbhip {
 namespace {
-
-typedef unsigned long long u64;
-typedef u64 u64x2 __attribute__((ext_vector_type(2)));
 
 constexpr int kSkThreads = 512;
 constexpr int kSkWaves = kSkThreads / kWave;
@@ -40,12 +35,6 @@ static_assert(kSkChunk == kSkSegment * kSkWaves, "a chunk is one segment per wav
 constexpr size_t kSkStep = 4 * kWave;  // rows a wave takes at a time: four consecutive rows per lane
 static_assert(kSkSegment % kSkStep == 0, "a segment is a whole number of steps");
 constexpr int kSkCarryThreads = 1024;
-
-struct SkHeader {
-  unsigned status;
-  unsigned pad[63];
-};
-static_assert(sizeof(SkHeader) == kWsHeader, "workspace header size");
 
 // A range of rows as the scans over segments see it: heads = its number of heads; cnt, sum, mn, mx (x domain) over the rows
 // from its last head on, or over all of it when heads == 0.  sk_tail writes one per segment (the record); sk_carry writes
@@ -75,38 +64,6 @@ struct SkOut {
   unsigned *mins, *maxs;
 };
 
-__device__ __forceinline__ u64 sk_ext(unsigned v, bool is_signed) {
-  return is_signed ? static_cast<u64>(static_cast<long long>(static_cast<int>(v))) : static_cast<u64>(v);
-}
-__device__ __forceinline__ unsigned sk_min(unsigned a, unsigned b) { return a < b ? a : b; }
-__device__ __forceinline__ unsigned sk_max(unsigned a, unsigned b) { return a > b ? a : b; }
-__device__ __forceinline__ unsigned sk_wave_min(unsigned v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v = sk_min(v, __shfl_xor(v, off, kWave));
-  return v;
-}
-__device__ __forceinline__ unsigned sk_wave_max(unsigned v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v = sk_max(v, __shfl_xor(v, off, kWave));
-  return v;
-}
-
-// this lane's four consecutive rows of a step: 16-byte non-temporal loads in a whole segment (segment starts are multiples
-// of 4096 rows, the columns 16-byte aligned), row by row and bounded by `last` in the ragged one
-__device__ __forceinline__ void sk_load(const unsigned *__restrict__ keys, const unsigned *__restrict__ vals, bool full,
-                                        size_t row0, size_t last, u32x4 &k, u32x4 &v) {
-  if (full) {
-    k = __builtin_nontemporal_load(reinterpret_cast<const u32x4 *>(keys + row0));
-    v = vals ? __builtin_nontemporal_load(reinterpret_cast<const u32x4 *>(vals + row0)) : u32x4{0u, 0u, 0u, 0u};
-  } else {
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      k[q] = row0 + q < last ? keys[row0 + q] : 0u;
-      v[q] = (vals && row0 + q < last) ? vals[row0 + q] : 0u;
-    }
-  }
-}
-
 // ---- tail --------------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(kSkThreads) void sk_tail_kernel(const unsigned *__restrict__ keys,
                                                              const unsigned *__restrict__ vals, size_t n, unsigned sign,
@@ -124,15 +81,16 @@ __global__ __launch_bounds__(kSkThreads) void sk_tail_kernel(const unsigned *__r
   unsigned acc_cnt = 0, acc_mn = 0xFFFFFFFFu, acc_mx = 0u, heads = 0;
 
   u32x4 k4, v4;
-  sk_load(keys, vals, full, first + 4 * lane, last, k4, v4);
+  bk_load(keys, vals, full, first + 4 * lane, last, k4, v4);
   for (size_t base = first; base < last; base += kSkStep) {
     const size_t row0 = base + 4 * lane;
     const u32x4 k = k4, v = v4;
-    if (base + kSkStep < last) sk_load(keys, vals, full, row0 + kSkStep, last, k4, v4);  // in flight over this step
+    if (base + kSkStep < last) bk_load(keys, vals, full, row0 + kSkStep, last, k4, v4);  // in flight over this step
     unsigned prev = __builtin_amdgcn_update_dpp(0u, k[3], 0x138, 0xf, 0xf, false);  // wave_shr:1
     if (lane == 0) prev = left;
     left = __builtin_amdgcn_readlane(k[3], kWave - 1);
-    // this lane's rows from its own last head on (all four when it has none)
+    // this lane's rows from its own last head on (all four when it has none): the loop of sk_scan_kernel and
+    // rk_reduce_kernel, counting rows instead of keeping the head's position
     u64 a_sum = 0;
     unsigned a_cnt = 0, a_mn = 0xFFFFFFFFu, a_mx = 0u, n_heads = 0;
 #pragma unroll
@@ -148,10 +106,10 @@ __global__ __launch_bounds__(kSkThreads) void sk_tail_kernel(const unsigned *__r
       }
       if (valid) {
         const unsigned x = v[q] ^ sign;
-        a_sum += sk_ext(v[q], is_signed);
+        a_sum += bk_ext(v[q], is_signed);
         ++a_cnt;
-        a_mn = sk_min(a_mn, x);
-        a_mx = sk_max(a_mx, x);
+        a_mn = bk_min(a_mn, x);
+        a_mx = bk_max(a_mx, x);
       }
     }
     heads += n_heads;
@@ -159,8 +117,8 @@ __global__ __launch_bounds__(kSkThreads) void sk_tail_kernel(const unsigned *__r
     if (mask == 0) {  // the open run goes on
       acc_sum += a_sum;
       acc_cnt += a_cnt;
-      acc_mn = sk_min(acc_mn, a_mn);
-      acc_mx = sk_max(acc_mx, a_mx);
+      acc_mn = bk_min(acc_mn, a_mn);
+      acc_mx = bk_max(acc_mx, a_mx);
     } else {  // only the rows at or behind the step's last head count
       const unsigned last_lane = 63u - static_cast<unsigned>(__builtin_clzll(mask));
       const bool keep = lane >= last_lane;
@@ -172,8 +130,8 @@ __global__ __launch_bounds__(kSkThreads) void sk_tail_kernel(const unsigned *__r
   }
   acc_sum = wave_reduce_add_u64(acc_sum);
   acc_cnt = wave_reduce_add(acc_cnt);
-  acc_mn = sk_wave_min(acc_mn);
-  acc_mx = sk_wave_max(acc_mx);
+  acc_mn = wave_reduce_min(acc_mn);
+  acc_mx = wave_reduce_max(acc_mx);
   heads = wave_reduce_add(heads);
   if (lane == 0) rec[seg] = SkPart{acc_sum, heads, acc_cnt, acc_mn, acc_mx, {0u, 0u}};
 }
@@ -185,8 +143,8 @@ __device__ __forceinline__ void sk_part_prepend(SkPart &a, const SkPart &l) {
   if (a.heads == 0) {
     a.sum += l.sum;
     a.cnt += l.cnt;
-    a.mn = sk_min(a.mn, l.mn);
-    a.mx = sk_max(a.mx, l.mx);
+    a.mn = bk_min(a.mn, l.mn);
+    a.mx = bk_max(a.mx, l.mx);
   }
   a.heads += l.heads;
 }
@@ -198,8 +156,8 @@ __device__ __forceinline__ void sk_part_append(SkPart &a, const SkPart &r) {
   } else {
     a.sum += r.sum;
     a.cnt += r.cnt;
-    a.mn = sk_min(a.mn, r.mn);
-    a.mx = sk_max(a.mx, r.mx);
+    a.mn = bk_min(a.mn, r.mn);
+    a.mx = bk_max(a.mx, r.mx);
   }
   a.heads = heads;
 }
@@ -242,50 +200,6 @@ __global__ __launch_bounds__(kSkCarryThreads) void sk_carry_kernel(const SkPart 
 }
 
 // ---- scan ----------------------------------------------------------------------------------------------------------------
-// the rows from the last head (or from the segment's first row) up to some row: lh = 1 + the head's row inside the segment,
-// 0 when there is no head yet; sum, mn, mx over the rows behind that point (reduce_by_key.hip's RkAgg)
-struct SkAgg {
-  unsigned lh, mn, mx;
-  u64 sum;
-};
-__device__ __forceinline__ SkAgg sk_none() { return SkAgg{0u, 0xFFFFFFFFu, 0u, 0ull}; }
-// a = l (+) a: the rows of l directly in front of the rows of a; kSeg = false: a is known to hold no head
-template <bool kSeg>
-__device__ __forceinline__ void sk_prepend(SkAgg &a, const SkAgg &l) {
-  if (!kSeg || a.lh == 0) {
-    a.lh = l.lh;
-    a.sum += l.sum;
-    a.mn = sk_min(a.mn, l.mn);
-    a.mx = sk_max(a.mx, l.mx);
-  }
-}
-template <int kCtrl, int kRowMask>
-__device__ __forceinline__ SkAgg sk_dpp(const SkAgg &a) {  // lanes without a source get sk_none()
-  SkAgg l;
-  l.lh = __builtin_amdgcn_update_dpp(0u, a.lh, kCtrl, kRowMask, 0xf, false);
-  l.mn = __builtin_amdgcn_update_dpp(0xFFFFFFFFu, a.mn, kCtrl, kRowMask, 0xf, false);
-  l.mx = __builtin_amdgcn_update_dpp(0u, a.mx, kCtrl, kRowMask, 0xf, false);
-  const unsigned lo = __builtin_amdgcn_update_dpp(0u, static_cast<unsigned>(a.sum), kCtrl, kRowMask, 0xf, false);
-  const unsigned hi = __builtin_amdgcn_update_dpp(0u, static_cast<unsigned>(a.sum >> 32), kCtrl, kRowMask, 0xf, false);
-  l.sum = (static_cast<u64>(hi) << 32) | lo;
-  return l;
-}
-template <bool kSeg, int kCtrl, int kRowMask>
-__device__ __forceinline__ void sk_scan_step(SkAgg &a) {
-  const SkAgg l = sk_dpp<kCtrl, kRowMask>(a);
-  sk_prepend<kSeg>(a, l);
-}
-// inclusive (segmented) scan over the wave's lanes, the DPP ladder of wave_inclusive_scan
-template <bool kSeg>
-__device__ __forceinline__ void sk_wave_scan(SkAgg &a) {
-  sk_scan_step<kSeg, 0x111, 0xf>(a);  // row_shr:1
-  sk_scan_step<kSeg, 0x112, 0xf>(a);  // row_shr:2
-  sk_scan_step<kSeg, 0x114, 0xf>(a);  // row_shr:4
-  sk_scan_step<kSeg, 0x118, 0xf>(a);  // row_shr:8
-  sk_scan_step<kSeg, 0x142, 0xa>(a);  // row_bcast:15 -> rows 1,3
-  sk_scan_step<kSeg, 0x143, 0xc>(a);  // row_bcast:31 -> rows 2,3
-}
-
 __device__ __forceinline__ void sk_store4(unsigned *col, size_t row0, size_t last, bool full, const u32x4 w) {
   if (full) {
     __builtin_nontemporal_store(w, reinterpret_cast<u32x4 *>(col + row0));
@@ -310,56 +224,57 @@ __global__ __launch_bounds__(kSkThreads) void sk_scan_kernel(const unsigned *__r
   const unsigned run_base = in.heads;  // heads in front of the segment
   const unsigned cnt_base = in.cnt;    // rows of the run that is open in front of the segment
   unsigned left = first ? keys[first - 1] : 0u;  // key of the row in front of the rows in hand (wave-uniform)
-  SkAgg carry{0u, in.mn, in.mx, in.sum};  // what is open in front of the rows in hand (wave-uniform)
+  BkAgg carry{0u, in.mn, in.mx, in.sum};  // what is open in front of the rows in hand (wave-uniform)
   unsigned heads_before = 0;              // heads of the segment in front of the rows in hand (wave-uniform)
 
   u32x4 k4, v4;
-  sk_load(keys, vals, full, first + 4 * lane, last, k4, v4);
+  bk_load(keys, vals, full, first + 4 * lane, last, k4, v4);
   for (size_t base = first; base < last; base += kSkStep) {
     const size_t row0 = base + 4 * lane;  // this lane's four consecutive rows
     const unsigned rel0 = static_cast<unsigned>(row0 - first);
     const u32x4 k = k4, v = v4;
-    if (base + kSkStep < last) sk_load(keys, vals, full, row0 + kSkStep, last, k4, v4);  // in flight over this step
+    if (base + kSkStep < last) bk_load(keys, vals, full, row0 + kSkStep, last, k4, v4);  // in flight over this step
+    // the previous key and the loop over the lane's rows are those of rk_reduce_kernel (reduce_by_key.hip)
     bool valid[4], head[4];
     unsigned x[4];
     unsigned prev = __builtin_amdgcn_update_dpp(0u, k[3], 0x138, 0xf, 0xf, false);  // wave_shr:1
     if (lane == 0) prev = left;
     left = __builtin_amdgcn_readlane(k[3], kWave - 1);
     unsigned n_heads = 0;
-    SkAgg a = sk_none();
+    BkAgg a = bk_none();
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
       valid[q] = full || row0 + q < last;
       x[q] = v[q] ^ sign;
       head[q] = valid[q] && (q ? k[q] != k[q - 1] : (row0 == 0 || k[0] != prev));
       n_heads += head[q] ? 1u : 0u;
-      if (head[q]) a = SkAgg{rel0 + q + 1, 0xFFFFFFFFu, 0u, 0ull};
+      if (head[q]) a = BkAgg{rel0 + q + 1, 0xFFFFFFFFu, 0u, 0ull};
       if (valid[q]) {
-        a.sum += sk_ext(v[q], is_signed);
-        a.mn = sk_min(a.mn, x[q]);
-        a.mx = sk_max(a.mx, x[q]);
+        a.sum += bk_ext(v[q], is_signed);
+        a.mn = bk_min(a.mn, x[q]);
+        a.mx = bk_max(a.mx, x[q]);
       }
     }
-    SkAgg incl = a;
+    BkAgg incl = a;
     unsigned h_before = heads_before;  // heads of the segment in front of this lane's rows
     if (__ballot(n_heads != 0) == 0) {  // no head in the wave's rows: plain sums, minima and maxima
-      sk_wave_scan<false>(incl);
+      bk_wave_scan<false>(incl);
     } else {
-      sk_wave_scan<true>(incl);
+      bk_wave_scan<true>(incl);
       const unsigned h_incl = wave_inclusive_scan(n_heads);
       h_before += h_incl - n_heads;
       heads_before += __builtin_amdgcn_readlane(h_incl, kWave - 1);
     }
-    SkAgg open = sk_dpp<0x138, 0xf>(incl);  // wave_shr:1: what the lanes in front of this one leave open
-    sk_prepend<true>(open, carry);
-    SkAgg total;
+    BkAgg open = bk_dpp<0x138, 0xf>(incl);  // wave_shr:1: what the lanes in front of this one leave open
+    bk_prepend<true>(open, carry);
+    BkAgg total;  // the last lane's; down to `carry = total` as in rk_reduce_kernel
     total.lh = __builtin_amdgcn_readlane(incl.lh, kWave - 1);
     total.mn = __builtin_amdgcn_readlane(incl.mn, kWave - 1);
     total.mx = __builtin_amdgcn_readlane(incl.mx, kWave - 1);
     const unsigned total_hi = __builtin_amdgcn_readlane(static_cast<unsigned>(incl.sum >> 32), kWave - 1);
     const unsigned total_lo = __builtin_amdgcn_readlane(static_cast<unsigned>(incl.sum), kWave - 1);
     total.sum = (static_cast<u64>(total_hi) << 32) | total_lo;
-    sk_prepend<true>(total, carry);
+    bk_prepend<true>(total, carry);
     carry = total;
 
     u32x4 w_run, w_num, w_mn, w_mx;
@@ -368,11 +283,11 @@ __global__ __launch_bounds__(kSkThreads) void sk_scan_kernel(const unsigned *__r
     for (int q = 0; q < 4; ++q) {
       if (head[q]) {
         ++h_before;
-        open = SkAgg{rel0 + q + 1, 0xFFFFFFFFu, 0u, 0ull};
+        open = BkAgg{rel0 + q + 1, 0xFFFFFFFFu, 0u, 0ull};
       }
-      open.sum += sk_ext(v[q], is_signed);  // (rows behind `last` are never stored)
-      open.mn = sk_min(open.mn, x[q]);
-      open.mx = sk_max(open.mx, x[q]);
+      open.sum += bk_ext(v[q], is_signed);  // (rows behind `last` are never stored)
+      open.mn = bk_min(open.mn, x[q]);
+      open.mx = bk_max(open.mx, x[q]);
       w_run[q] = run_base + h_before - 1u;
       w_num[q] = open.lh ? rel0 + q + 2u - open.lh : cnt_base + rel0 + q + 1u;
       w_sum[q] = open.sum;
@@ -418,15 +333,15 @@ __global__ __launch_bounds__(kSkCheckThreads) void sk_check_kernel(const unsigne
       ++heads;
       if (run_ids) bad += run_ids[i] != (i ? run_ids[i - 1] + 1u : 0u) ? 1u : 0u;
       if (row_numbers) bad += row_numbers[i] != 1u ? 1u : 0u;
-      if (sums) bad += sums[i] != sk_ext(v, is_signed) ? 1u : 0u;
+      if (sums) bad += sums[i] != bk_ext(v, is_signed) ? 1u : 0u;
       if (mins) bad += mins[i] != v ? 1u : 0u;
       if (maxs) bad += maxs[i] != v ? 1u : 0u;
     } else {
       if (run_ids) bad += run_ids[i] != run_ids[i - 1] ? 1u : 0u;
       if (row_numbers) bad += row_numbers[i] != row_numbers[i - 1] + 1u ? 1u : 0u;
-      if (sums) bad += sums[i] != sums[i - 1] + sk_ext(v, is_signed) ? 1u : 0u;
-      if (mins) bad += (mins[i] ^ sign) != sk_min(mins[i - 1] ^ sign, v ^ sign) ? 1u : 0u;
-      if (maxs) bad += (maxs[i] ^ sign) != sk_max(maxs[i - 1] ^ sign, v ^ sign) ? 1u : 0u;
+      if (sums) bad += sums[i] != sums[i - 1] + bk_ext(v, is_signed) ? 1u : 0u;
+      if (mins) bad += (mins[i] ^ sign) != bk_min(mins[i - 1] ^ sign, v ^ sign) ? 1u : 0u;
+      if (maxs) bad += (maxs[i] ^ sign) != bk_max(maxs[i - 1] ^ sign, v ^ sign) ? 1u : 0u;
     }
     faults += bad;
     if (bad && i < lowest) lowest = i;
@@ -525,9 +440,7 @@ extern "C" int dbhip_check_scan_by_key_u32(const uint32_t *keys, const uint32_t 
   e = fill_async(result + 1, 0xFF, sizeof(uint64_t), s);  // no violating row yet
   if (e != hipSuccess) return static_cast<int>(e);
   if (n) {
-    const size_t want = (n + kSkCheckThreads - 1) / kSkCheckThreads;
-    const size_t cap = static_cast<size_t>(dev.cus) * 8;
-    hipLaunchKernelGGL(sk_check_kernel, dim3(static_cast<unsigned>(want < cap ? want : cap)), dim3(kSkCheckThreads), 0, s,
+    hipLaunchKernelGGL(sk_check_kernel, dim3(capped_grid(n, kSkCheckThreads, dev)), dim3(kSkCheckThreads), 0, s,
                        keys, vals, n, vals_signed ? 0x80000000u : 0u, run_ids, row_numbers,
                        reinterpret_cast<const u64 *>(sums), mins, maxs, reinterpret_cast<u64 *>(result));
   }

@@ -167,26 +167,6 @@ __global__ __launch_bounds__(kTkThreads) void tk_hist_kernel(const unsigned *__r
   }
 }
 
-// exclusive prefix sum over the workgroup (kThreads threads, all of them call); total = the workgroup's sum
-template <int kThreads>
-__device__ __forceinline__ unsigned tk_block_exclusive_scan(unsigned v, unsigned *s_wsum, unsigned &total) {
-  constexpr int kWaves = kThreads / kWave;
-  const unsigned lane = threadIdx.x & (kWave - 1), wave = threadIdx.x / kWave;
-  const unsigned incl = wave_inclusive_scan(v);
-  __syncthreads();  // s_wsum may still be read from the call before
-  if (lane == kWave - 1) s_wsum[wave] = incl;
-  __syncthreads();
-  unsigned before = 0, all = 0;
-#pragma unroll
-  for (int w = 0; w < kWaves; ++w) {
-    const unsigned s = s_wsum[w];
-    before += static_cast<unsigned>(w) < wave ? s : 0u;
-    all += s;
-  }
-  total = all;
-  return before + incl - v;
-}
-
 // one workgroup: the bin of this level that holds the k-th key
 template <int BITS>
 __global__ __launch_bounds__(kTkPickThreads) void tk_pick_kernel(TkHeader *hdr, const unsigned *__restrict__ bins, unsigned k,
@@ -208,7 +188,7 @@ __global__ __launch_bounds__(kTkPickThreads) void tk_pick_kernel(TkHeader *hdr, 
     mine += c[j];
   }
   unsigned total;
-  unsigned run = tk_block_exclusive_scan<kTkPickThreads>(mine, s_wsum, total);
+  unsigned run = block_exclusive_scan<kTkPickThreads>(mine, s_wsum, total);
 #pragma unroll
   for (int j = 0; j < kPer; ++j) {
     if (run < need && need - run <= c[j]) {  // exactly one bin of the workgroup
@@ -277,10 +257,10 @@ __global__ __launch_bounds__(kTkPickThreads) void tk_scan_kernel(const TkHeader 
     const size_t seg = base + threadIdx.x;
     const u32x2 c = seg < segments ? cnt[seg] : u32x2{0u, 0u};
     unsigned eq_total, out_total;
-    const unsigned eq_before = eq_run + tk_block_exclusive_scan<kTkPickThreads>(c.y, s_wsum, eq_total);
+    const unsigned eq_before = eq_run + block_exclusive_scan<kTkPickThreads>(c.y, s_wsum, eq_total);
     const unsigned room = eq_before < r ? r - eq_before : 0u;  // rows in [lo, hi] still to take from here on
     const unsigned take = c.x + (c.y < room ? c.y : room);
-    const unsigned out_first = out_run + tk_block_exclusive_scan<kTkPickThreads>(take, s_wsum, out_total);
+    const unsigned out_first = out_run + block_exclusive_scan<kTkPickThreads>(take, s_wsum, out_total);
     if (seg < segments) pos[seg] = u32x2{out_first, eq_before};
     eq_run += eq_total;
     out_run += out_total;
@@ -399,9 +379,7 @@ int topk_impl(const unsigned *keys, size_t n, size_t m, unsigned mask, int sorte
   const hipError_t e = fill_async(workspace, 0, kWsHeader + sizeof(unsigned) * level_bins * levels, s);
   if (e != hipSuccess) return static_cast<int>(e);
 
-  const size_t want = (n / 4 + 4 * kTkThreads - 1) / (4 * kTkThreads);
-  const size_t cap = static_cast<size_t>(dev.cus) * 4;
-  const unsigned hist_grid = static_cast<unsigned>(want < cap ? (want ? want : 1) : cap);
+  const unsigned hist_grid = capped_grid(n / 4, 4 * kTkThreads, dev, 4);
   for (int lv = 0; lv < levels; ++lv) {
     const TkLevel t = tk_level(BITS, lv);
     const unsigned digit_mask = (1u << t.width) - 1u;
@@ -424,9 +402,7 @@ int topk_impl(const unsigned *keys, size_t n, size_t m, unsigned mask, int sorte
     if (rc != DBHIP_OK) return rc;
     sort_status = reinterpret_cast<const unsigned *>(base + l.sort_ws);
   }
-  const size_t fwant = (m / 4 + kTkThreads - 1) / kTkThreads;
-  const unsigned fgrid = static_cast<unsigned>(fwant < cap ? (fwant ? fwant : 1) : cap);
-  hipLaunchKernelGGL(tk_finish_kernel, dim3(fgrid), dim3(kTkThreads), 0, s, sel_keys, sel_rows, m, mask, out_keys, out_rows,
+  hipLaunchKernelGGL(tk_finish_kernel, dim3(capped_grid(m / 4, kTkThreads, dev, 4)), dim3(kTkThreads), 0, s, sel_keys, sel_rows, m, mask, out_keys, out_rows,
                      hdr, sort_status);
   return launch_status();
 }
@@ -526,9 +502,7 @@ extern "C" int dbhip_check_topk_u32(const uint32_t *keys, size_t n, const uint32
   const hipError_t e = fill_async(result, 0, 2 * sizeof(uint64_t), s);
   if (e != hipSuccess) return static_cast<int>(e);
   if (m == 0) return DBHIP_OK;
-  const size_t want = (n + kTkCheckThreads - 1) / kTkCheckThreads;  // m <= n
-  const size_t cap = static_cast<size_t>(dev.cus) * 8;
-  const unsigned grid = static_cast<unsigned>(want < cap ? want : cap);
+  const unsigned grid = capped_grid(n, kTkCheckThreads, dev);  // m <= n
   const unsigned mask = (is_signed ? 0x80000000u : 0u) ^ (largest ? 0xFFFFFFFFu : 0u);
   hipLaunchKernelGGL(tk_check_kernel, dim3(grid), dim3(kTkCheckThreads), 0, s, keys, n, out_keys, out_rows, m, mask,
                      reinterpret_cast<unsigned long long *>(result));
