@@ -115,6 +115,15 @@ SCAN_BY_KEY_SIGNATURES = {
     "dbhip_check_scan_by_key_u32": (_int, [_vp, _vp, _sz, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
 }
 
+# the same for include/dbhip_sorted_search.h (tests/test_sorted_search_host.py checks this pair)
+SORTED_SEARCH_SIGNATURES = {
+    "dbhip_sorted_index_workspace_bytes": (_sz, [_sz, _u32]),
+    "dbhip_sorted_index_build_u32": (_int, [_vp, _sz, _int, _u32, _vp, _sz, _vp]),
+    "dbhip_sorted_search_u32": (_int, [_vp, _sz, _vp, _vp, _sz, _vp, _vp, _vp, _sz, _vp]),
+    "dbhip_check_sorted_search_workspace_bytes": (_sz, [_sz]),
+    "dbhip_check_sorted_search_u32": (_int, [_vp, _sz, _int, _vp, _vp, _sz, _vp, _vp, _vp, _vp, _sz, _vp]),
+}
+
 _lib = None
 
 
@@ -140,7 +149,7 @@ def lib() -> C.CDLL:
             pass
         handle = C.CDLL(str(_LIB_PATH), mode=C.RTLD_GLOBAL)
         for name, (res, args) in {**SIGNATURES, **TOPK_SIGNATURES, **REDUCE_BY_KEY_SIGNATURES,
-                                   **SCAN_BY_KEY_SIGNATURES}.items():
+                                   **SCAN_BY_KEY_SIGNATURES, **SORTED_SEARCH_SIGNATURES}.items():
             fn = getattr(handle, name)  # AttributeError if the .so does not export the symbol
             fn.restype = res
             fn.argtypes = args

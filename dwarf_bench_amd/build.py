@@ -73,7 +73,8 @@ def build_hip(force: bool = False) -> Path:
     srcs = sorted(CSRC.glob("*.hip"))
     headers = sorted(CSRC.glob("*.hpp")) + [ROOT / "include" / "dbhip.h", ROOT / "include" / "dbhip_topk.h",
                                               ROOT / "include" / "dbhip_reduce_by_key.h",
-                                              ROOT / "include" / "dbhip_scan_by_key.h"]
+                                              ROOT / "include" / "dbhip_scan_by_key.h",
+                                              ROOT / "include" / "dbhip_sorted_search.h"]
     deps = srcs + headers
     if force or _stale(out, deps):
         objs = []

@@ -182,6 +182,8 @@ void populate_topk_registry();
 void populate_groupby_sorted_registry();
 // WindowSortedHip: only the dwarf_bench_window CLI registers it, after populate_registry()
 void populate_window_registry();
+// RangeJoinHip: only the dwarf_bench_range_join CLI registers it, after populate_registry()
+void populate_range_join_registry();
 
 namespace helpers {
 // $DWARF_BENCH_ROOT or the executable's directory (common/common.cpp:38-41, without Boost.DLL)

@@ -35,6 +35,7 @@
 #include "../../include/dbhip.h"
 #include "../../include/dbhip_reduce_by_key.h"
 #include "../../include/dbhip_scan_by_key.h"
+#include "../../include/dbhip_sorted_search.h"
 #include "../../include/dbhip_topk.h"
 #include "errors.hpp"
 
@@ -1522,6 +1523,79 @@ void WindowSortedHip::_run(const size_t n, Meter &meter) {
           "dbhip_check_scan_by_key_u32");
     const auto w = chk.get();
     const bool ok = srt[0] == 0 && w[0] == 0 && w[1] == ~0ull && w[3] == 0;
+    record(meter, n, std::move(result), ok, "Incorrect results");
+  }
+}
+
+// =====================================================================================================
+// RangeJoinHip — the band join b.key BETWEEN p.lo AND p.hi as a table of (build row, probe row) pairs: the stable pairs sort
+// of the build keys on row ids, the fence ladder over the sorted keys and the search of include/dbhip_sorted_search.h, then
+// dbhip_join_pairs_u32 in probe-row order.  n rows a side; build keys and probe lo uniform in [1, max(10000, n)] from
+// JoinPairsHip's seeds, hi = lo + W saturating, W from DWARF_BENCH_RANGE_WIDTH (default 2).  The timed region is the sort,
+// the index build, the search and the expansion, with the capacity an untimed count-only pass returned; the keys are copied
+// afresh outside it (the sort works in place).  Result::valid from dbhip_check_sorted_u32 on the sorted keys,
+// dbhip_check_sorted_search_u32 on (pos, cnt) and *out_pairs == its pair total.  No reference counterpart.
+void RangeJoinHip::_run(const size_t n, Meter &meter) {
+  const RunOptions &opts = meter.opts();
+  if (n == 0 || n > (static_cast<size_t>(1) << 31)) fail("RangeJoinHip: between 1 and 2^31 rows a side");
+  uint32_t width = 2;
+  if (const char *w = std::getenv("DWARF_BENCH_RANGE_WIDTH")) width = static_cast<uint32_t>(std::strtoul(w, nullptr, 10));
+  DevBuf<uint32_t> src(n), keys(n), ids(n), tmp_keys(n), tmp_ids(n), lo(n), hi(n), pos(n), cnt(n);
+  const size_t sort_bytes = dbhip_radix_sort_pairs_workspace_bytes(n, 8);
+  const size_t index_bytes = dbhip_sorted_index_workspace_bytes(n, 0);
+  const size_t pairs_bytes = dbhip_join_pairs_workspace_bytes(n);
+  const size_t check_bytes = dbhip_check_sorted_search_workspace_bytes(n);
+  DevBuf<unsigned char> sort_ws(sort_bytes), index_ws(index_bytes), pairs_ws(pairs_bytes), check_ws(check_bytes);
+  DevBuf<uint64_t> total(1);
+  const uint32_t key_hi = static_cast<uint32_t>(std::max<size_t>(10000, n));
+  db_ok(dbhip_gen_uniform_u32(src.get(), n, 42, 0, 1, key_hi, nullptr), "gen build keys");
+  db_ok(dbhip_gen_uniform_u32(lo.get(), n, 43, 0, 1, key_hi, nullptr), "gen probe lo");
+  {
+    auto h = lo.to_host(n);
+    for (auto &v : h) v = v > 0xFFFFFFFFu - width ? 0xFFFFFFFFu : v + width;  // saturating
+    hip_ok(hipMemcpy(hi.get(), h.data(), n * sizeof(uint32_t), hipMemcpyHostToDevice), "probe hi");
+  }
+  const auto refresh = [&] {
+    hip_ok(hipMemcpy(keys.get(), src.get(), n * sizeof(uint32_t), hipMemcpyDeviceToDevice), "refresh");
+  };
+  const auto join = [&](uint64_t capacity, uint32_t *out_b, uint32_t *out_p) {
+    db_ok(dbhip_radix_sort_pairs_u32(keys.get(), ids.get(), tmp_keys.get(), tmp_ids.get(), n, 8, 1, sort_ws.get(), sort_bytes,
+                                     nullptr),
+          "dbhip_radix_sort_pairs_u32");
+    db_ok(dbhip_sorted_index_build_u32(keys.get(), n, 0, 0, index_ws.get(), index_bytes, nullptr),
+          "dbhip_sorted_index_build_u32");
+    db_ok(dbhip_sorted_search_u32(keys.get(), n, lo.get(), hi.get(), n, pos.get(), cnt.get(), index_ws.get(), index_bytes,
+                                  nullptr),
+          "dbhip_sorted_search_u32");
+    db_ok(dbhip_join_pairs_u32(ids.get(), n, nullptr, pos.get(), cnt.get(), n, 0, capacity, out_b, out_p, total.get(),
+                               pairs_ws.get(), pairs_bytes, nullptr),
+          "dbhip_join_pairs_u32");
+  };
+  const auto statuses = [&] {
+    check_status(sort_ws.get(), "RangeJoinHip");
+    check_status(index_ws.get(), "RangeJoinHip");
+    check_status(pairs_ws.get(), "RangeJoinHip");
+  };
+  refresh();
+  join(0, nullptr, nullptr);  // not timed: the count-only pass that sizes the output
+  statuses();
+  const uint64_t capacity = total.to_host(1)[0];
+  DevBuf<uint32_t> out_b(capacity), out_p(capacity);
+  CheckWords chk;
+  Events ev;
+  for (size_t it = 0; it < opts.iterations; ++it) {
+    refresh();  // not timed
+    auto result = std::make_unique<Result>();
+    time_launch(*result, ev, [&] { join(capacity, out_b.get(), out_p.get()); });
+    statuses();
+    if (inject_fault()) poke_xor(cnt.get() + n / 2, 1u);  // one row's interval length
+    db_ok(dbhip_check_sorted_u32(keys.get(), n, 0, chk.dev(), nullptr), "dbhip_check_sorted_u32");
+    const auto srt = chk.get();
+    db_ok(dbhip_check_sorted_search_u32(keys.get(), n, 0, lo.get(), hi.get(), n, pos.get(), cnt.get(), chk.dev(),
+                                        check_ws.get(), check_bytes, nullptr),
+          "dbhip_check_sorted_search_u32");
+    const auto w = chk.get();
+    const bool ok = srt[0] == 0 && w[0] == 0 && w[1] == ~0ull && w[3] == 0 && total.to_host(1)[0] == w[2] && w[2] == capacity;
     record(meter, n, std::move(result), ok, "Incorrect results");
   }
 }

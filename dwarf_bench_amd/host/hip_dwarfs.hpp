@@ -135,3 +135,10 @@ struct WindowSortedHip : HipDwarf {
   WindowSortedHip() : HipDwarf("WindowSortedHip") {}
   void _run(size_t buf_size, Meter &meter) override;
 };
+// The band join b.key BETWEEN p.lo AND p.hi as (build row, probe row) pairs: the stable pairs sort, the sorted search of
+// include/dbhip_sorted_search.h and dbhip_join_pairs_u32; registered by populate_range_join_registry() only (the
+// dwarf_bench_range_join CLI); no reference counterpart.  DWARF_BENCH_RANGE_WIDTH: hi - lo (default 2)
+struct RangeJoinHip : HipDwarf {
+  RangeJoinHip() : HipDwarf("RangeJoinHip") {}
+  void _run(size_t buf_size, Meter &meter) override;
+};

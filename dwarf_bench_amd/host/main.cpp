@@ -12,7 +12,8 @@
 // (populate_join_pairs_registry), and with -DEXPERIMENTAL_TOPK `dwarf_bench_topk`, the default set plus TopKHip
 // (populate_topk_registry), and with -DEXPERIMENTAL_GROUPBY_SORTED `dwarf_bench_groupby_sorted`, the default set plus
 // GroupBySortedHip (populate_groupby_sorted_registry), and with -DEXPERIMENTAL_WINDOW `dwarf_bench_window`, the default
-// set plus WindowSortedHip (populate_window_registry).
+// set plus WindowSortedHip (populate_window_registry), and with -DEXPERIMENTAL_RANGE_JOIN `dwarf_bench_range_join`, the
+// default set plus RangeJoinHip (populate_range_join_registry).
 #include <iostream>
 #include <memory>
 #include <sstream>
@@ -68,6 +69,9 @@ int main(int argc, char *argv[]) {
 #endif
 #ifdef EXPERIMENTAL_WINDOW
   populate_window_registry();  // dwarf_bench_window
+#endif
+#ifdef EXPERIMENTAL_RANGE_JOIN
+  populate_range_join_registry();  // dwarf_bench_range_join
 #endif
   Registry *registry = Registry::instance();
 

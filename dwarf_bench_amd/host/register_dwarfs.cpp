@@ -94,3 +94,11 @@ void populate_window_registry() {
   Registry::instance()->registerd(new WindowSortedHip());
 #endif
 }
+
+// the range join (dbhip_radix_sort_pairs_u32 + the sorted search + dbhip_join_pairs_u32): only the dwarf_bench_range_join CLI
+// (main.cpp built with -DEXPERIMENTAL_RANGE_JOIN) calls this, so the lists of the other nine CLIs stay as they are
+void populate_range_join_registry() {
+#ifdef HIP_ENABLED
+  Registry::instance()->registerd(new RangeJoinHip());
+#endif
+}

@@ -494,6 +494,139 @@ def window_sorted(keys: torch.Tensor, vals: torch.Tensor, signed: bool = False, 
 
 
 # ---------------------------------------------------------------------------------------------
+# sorted search: lower / upper bound of every probe row in a sorted column; behind the stable argsort and in front of
+# JoinPairs, the range join b.key BETWEEN p.lo AND p.hi (include/dbhip_sorted_search.h)
+# ---------------------------------------------------------------------------------------------
+SORTED_SEARCH_FANOUT = 64    # DBHIP_SORTED_SEARCH_FANOUT: entries under one fence
+SORTED_SEARCH_TOP = 16384    # DBHIP_SORTED_SEARCH_TOP: default and largest top level
+
+
+class SortedSearch:
+    """Reusable plan for the interval [lo, hi] of every probe row in a sorted column of m entries
+    (dbhip_sorted_index_build_u32, dbhip_sorted_search_u32): owns the index workspace and both output columns of n
+    entries.  top: the largest top level of the fence ladder, 0 = the default."""
+
+    def __init__(self, m: int, n: int, device="cuda", top: int = 0):
+        if m < 0 or n < 0:
+            raise ValueError("m and n must not be negative")
+        if m > 1 << 31 or n >= 1 << 32:
+            raise ValueError("sorted_search takes at most 2^31 sorted entries and fewer than 2^32 probe rows")
+        self.m, self.n, self.top = m, n, int(top)
+        self.ws_bytes = _capi.lib().dbhip_sorted_index_workspace_bytes(m, self.top)
+        if self.ws_bytes == 0:
+            raise ValueError(f"top = {top}: 0 or a power of two from 64 to {SORTED_SEARCH_TOP}")
+        self.ws = _ws(self.ws_bytes, device)
+        self.ws_bytes = self.ws.numel()
+        self.pos = torch.empty(max(n, 1), dtype=torch.int32, device=device)
+        self.cnt = torch.empty(max(n, 1), dtype=torch.int32, device=device)
+        self.sorted = None
+
+    def index(self, sorted: torch.Tensor, signed: bool = False) -> None:
+        """Asynchronous: builds the fence ladder over `sorted` (ascending as uint32, or as int32 when signed), which the
+        plan keeps a reference to and which must not change before the last search."""
+        _need(sorted, torch.int32, "sorted")
+        if sorted.numel() != self.m:
+            raise ValueError("size mismatch")
+        _capi.check(_capi.lib().dbhip_sorted_index_build_u32(
+            sorted.data_ptr(), self.m, int(signed), self.top, self.ws.data_ptr(), self.ws_bytes, _stream()),
+            "sorted_index_build_u32")
+        self.sorted = sorted
+
+    def search(self, lo: torch.Tensor | None, hi: torch.Tensor | None = None) -> None:
+        """Asynchronous on the current stream; nothing is read back (graph-capturable).  hi=None: hi = lo; lo=None: minus
+        infinity."""
+        if self.sorted is None:
+            raise ValueError("index() comes first")
+        for t, name in ((lo, "lo"), (hi, "hi")):
+            if t is not None:
+                _need(t, torch.int32, name)
+                _need16(t, name)
+                if t.numel() != self.n:
+                    raise ValueError("size mismatch")
+        if lo is None and hi is None:
+            raise ValueError("lo or hi")
+        _capi.check(_capi.lib().dbhip_sorted_search_u32(
+            self.sorted.data_ptr(), self.m, lo.data_ptr() if lo is not None else None,
+            hi.data_ptr() if hi is not None else None, self.n, self.pos.data_ptr(), self.cnt.data_ptr(), self.ws.data_ptr(),
+            self.ws_bytes, _stream()), "sorted_search_u32")
+
+    def result(self):
+        """-> (pos, cnt) of the last search, int32 storage of uint32, after the status word was read (synchronises)"""
+        _check_status(self.ws, "sorted_search_u32")
+        return self.pos[:self.n], self.cnt[:self.n]
+
+
+def sorted_search(sorted: torch.Tensor, lo: torch.Tensor | None, hi: torch.Tensor | None = None, signed: bool = False):
+    """For every probe row the interval [lo, hi] of the ascending column `sorted` -> (pos, cnt): pos = the number of
+    entries < lo (torch.searchsorted side="left"), pos + cnt = the number of entries <= hi (side="right"), cnt = 0 when
+    hi < lo.  hi=None: hi = lo, the equality join; lo=None: minus infinity, pos = 0 and pos + cnt - 1 the ASOF row."""
+    _need(sorted, torch.int32, "sorted")
+    probe = lo if lo is not None else hi
+    if probe is None:
+        raise ValueError("lo or hi")
+    _need(probe, torch.int32, "lo" if lo is not None else "hi")
+    plan = SortedSearch(sorted.numel(), probe.numel(), sorted.device)
+    plan.index(sorted, signed)
+    plan.search(lo, hi)
+    return plan.result()
+
+
+def check_sorted_search(sorted: torch.Tensor, lo: torch.Tensor | None, hi: torch.Tensor | None, pos: torch.Tensor | None,
+                        cnt: torch.Tensor | None, signed: bool = False):
+    """-> the four words of dbhip_check_sorted_search_u32: (violations, lowest violating row or 2^64 - 1, the sum of cnt,
+    0); a column that is None is not judged"""
+    cols = ((sorted, "sorted"), (lo, "lo"), (hi, "hi"), (pos, "pos"), (cnt, "cnt"))
+    for t, name in cols:
+        if t is not None:
+            _need(t, torch.int32, name)
+    probe = next((t for t, _ in cols[1:] if t is not None), None)
+    if probe is None:
+        raise ValueError("no probe column")
+    n = probe.numel()
+    if any(t is not None and t.numel() != n for t, _ in cols[1:]):
+        raise ValueError("size mismatch")
+    ws = _ws(_capi.lib().dbhip_check_sorted_search_workspace_bytes(n), sorted.device)
+    res = _result(4, sorted.device)
+    _capi.check(_capi.lib().dbhip_check_sorted_search_u32(
+        sorted.data_ptr(), sorted.numel(), int(signed), *(t.data_ptr() if t is not None else None for t, _ in cols[1:3]), n,
+        *(t.data_ptr() if t is not None else None for t, _ in cols[3:]), res.data_ptr(), ws.data_ptr(), ws.numel(),
+        _stream()), "check_sorted_search_u32")
+    return tuple(_u64(res))
+
+
+def range_join(build_keys: torch.Tensor, probe_lo: torch.Tensor | None, probe_hi: torch.Tensor | None = None,
+               left_outer: bool = False, capacity: int | None = None, signed: bool = False):
+    """The range join build.key BETWEEN probe.lo AND probe.hi -> (build_rows, probe_rows), one entry per matching pair of
+    rows (left_outer: and one with build row -1 per probe row without a match).  probe_hi=None: the equality join;
+    probe_lo=None: every build key <= hi.  Copies the build keys, argsorts the copy with the stable pairs sort on row
+    ids, builds the fence ladder, searches, and expands with JoinPairs in probe-row order.  The pairs are grouped by probe
+    row ascending; inside a row they go by ascending build key, and equal keys by ascending build row, because the sort
+    is stable: the result is unique.  capacity=None: a count-only launch, one read-back, an exact allocation, the fill; a
+    given capacity: one launch (more pairs than that raise DbhipError, which names the total).  signed: the keys and the
+    bounds compare as int32."""
+    _need(build_keys, torch.int32, "build_keys")
+    probe = probe_lo if probe_lo is not None else probe_hi
+    if probe is None:
+        raise ValueError("probe_lo or probe_hi")
+    _need(probe, torch.int32, "probe_lo" if probe_lo is not None else "probe_hi")
+    nb, npr = build_keys.numel(), probe.numel()
+    keys = build_keys.clone()
+    ids = radix_argsort_(keys, signed=signed)[:nb]
+    search = SortedSearch(nb, npr, build_keys.device)
+    search.index(keys, signed)
+    search.search(probe_lo, probe_hi)
+    pos, cnt = search.pos[:npr], search.cnt[:npr]
+    if capacity is None:
+        counter = JoinPairs(npr, 0, build_keys.device)
+        counter.launch(ids, pos, cnt, None, left_outer)
+        capacity = counter.count()
+    plan = JoinPairs(npr, capacity, build_keys.device)
+    plan.launch(ids, pos, cnt, None, left_outer)
+    _check_status(search.ws, "sorted_search_u32")
+    return plan.result()
+
+
+# ---------------------------------------------------------------------------------------------
 # dwarf 3: group-by SUM
 # ---------------------------------------------------------------------------------------------
 class GroupBySum:

@@ -39,6 +39,17 @@ the contract numbers come from bench.py.
                   key (2^26 pairs); beside it the count-only call and, in the same process on the same (ids, pos, cnt), the
                   torch composition repeat_interleave + cumsum + gather (median of 9); both columns of both legs compared
                   with each other and the pair table checked by dbhip_check_join_pairs_u32
+  sorted-search [lg] dbhip_sorted_search_u32 of 2^lg probe rows (default 24) in sorted columns of 2^14, 2^20, 2^24 and 2^26 entries
+                  (SS_M=<lg m>: that one alone), uniform and with 2^13 distinct values; probe values uniform, the same sorted, all
+                  one value; hi == lo and a band of about 16 matches per row; SortedSearch.search against
+                  torch.searchsorted(side="left") on lo, side="right") on hi and the subtraction, in one process, alternating,
+                  REPS (default 5) repetitions of a median of 5; beside it the index build, the ladder's levels, the gather model
+                  (rows x block loads that leave the CU / 53 G/s) and whether this code's slowest repetition beat torch's fastest
+                  (the floor); every answer checked by dbhip_check_sorted_search_u32 and against torch.  lg 10: the
+                  single-launch cost against a large column
+  range-join [lg] the band join at 2^lg rows a side (default 24), keys in [1, n], hi = lo + 2: copy + argsort + index + search +
+                  pairs (ops.range_join's launches, capacity given) against torch.sort(stable) + two searchsorted + join-pairs'
+                  torch expansion, same protocol; both pair columns compared with torch's
   launch-join-pairs [lg]  five expansions at 2^lg rows a side (default 24) and five of the one-key shape, nothing else
                   (`rocprofv3 --kernel-trace --stats`)
   launch-sort-pairs [lg]  five 8-bit argsorts of 2^lg full-range keys (default 24) and nothing else (`rocprofv3 --kernel-trace`)
@@ -483,6 +494,118 @@ def launch_join_pairs(lg):
         b, p = plan.result()
         words = ops.check_join_pairs(bk, pk, ids, pos, cnt, b, p, rid)
         print(name, "ok" if words[0] == 0 and words[1] == b.numel() and words[2] == words[3] else "WRONG")
+
+
+def _search_columns(m):
+    """(name, ascending int32 column of m entries in [0, 2^31): torch's signed order is the unsigned one)"""
+    yield "uniform", torch.sort(ops.gen_uniform_u32(m, 42, 0, 2**31 - 1)).values
+    yield "2^13 distinct", torch.sort(ops.gen_uniform_u32(m, 42, 0, 8191) * (1 << 18)).values
+
+
+def _search_levels(m, top=16384):
+    levels = 0
+    while m > top:
+        m, levels = (m + 63) // 64, levels + 1
+    return levels
+
+
+def sorted_search(lg):
+    """SS_M=<lg m> takes one column size instead of 2^14, 2^20, 2^24, 2^26"""
+    n = 1 << (lg or 24)
+    reps = int(os.environ.get("REPS", "5"))
+    sizes = [int(os.environ["SS_M"])] if os.environ.get("SS_M") else [14, 20, 24, 26]
+    draw = ops.gen_uniform_u32(n, 43, 0, 2**31 - 1)
+    for lgm in sizes:
+        m = 1 << lgm
+        levels = _search_levels(m)
+        for col_name, col in _search_columns(m):
+            plan = ops.SortedSearch(m, n)
+            t_index = median(times(lambda: plan.index(col), 9))
+            width = max((16 << 31) // m, 1)
+            for probe_name, lo in (("uniform", draw), ("sorted", torch.sort(draw).values),
+                                   ("one value", torch.full_like(draw, 1 << 30))):
+                for band_name, hi in (("hi == lo", None), ("band ~16", torch.clamp(lo.to(torch.int64) + width, max=2**31 - 1)
+                                                           .to(torch.int32))):
+                    top_hi = hi if hi is not None else lo
+
+                    def mine():
+                        plan.search(lo, hi)
+
+                    def vendor():
+                        pos = torch.searchsorted(col, lo, side="left")
+                        return pos, torch.searchsorted(col, top_hi, side="right") - pos
+
+                    legs = {"sorted_search": [], "torch": []}
+                    for _ in range(reps):  # alternating
+                        legs["sorted_search"].append(median(times(mine, 5)))
+                        legs["torch"].append(median(times(vendor, 5)))
+                    mine()
+                    pos, cnt = plan.result()
+                    words = ops.check_sorted_search(col, lo, hi, pos, cnt)
+                    want = vendor()
+                    ok = (words[0] == 0 and words[2] == int(want[1].sum()) and torch.equal(u64(pos), want[0])
+                          and torch.equal(u64(cnt), want[1]))
+                    floor = max(legs["sorted_search"]) <= min(legs["torch"])
+                    model = n * levels * (1 if hi is None else 2) / 53e9 * 1e6  # block loads that leave the CU, at most
+                    cols = "  ".join(f"{leg} {min(ts):9.1f} .. {max(ts):9.1f} us" for leg, ts in legs.items())
+                    print(f"{TAG:10s} n=2^{lg or 24} m=2^{lgm} {col_name:13s} probe {probe_name:9s} {band_name:8s} pairs={words[2]:11d}  "
+                          f"{cols}  index {t_index:6.1f} us  levels {levels}  model {model:8.1f} us  floor {'holds' if floor else 'MISSED'}  "
+                          f"{'ok' if ok else 'WRONG'}   "
+                          + " ".join(f"{leg}:" + "/".join(f"{t:.1f}" for t in ts) for leg, ts in legs.items()), flush=True)
+                    del pos, cnt, want
+            del plan, col
+
+
+def range_join(lg):
+    """the whole band join at 2^lg rows a side, keys in [1, n], hi = lo + 2: copy + argsort + index + search + pairs against
+    torch.sort(stable) + two searchsorted + the expansion of join-pairs"""
+    n = 1 << (lg or 24)
+    reps = int(os.environ.get("REPS", "5"))
+    build = ops.gen_uniform_u32(n, 42, 1, n)
+    lo = ops.gen_uniform_u32(n, 43, 1, n)
+    hi = lo + 2
+    rid = torch.arange(n, dtype=torch.int32, device="cuda")
+    keys = torch.empty_like(build)
+    srt, search = ops.RadixSortPairs(n, 8), ops.SortedSearch(n, n)
+    counter = ops.JoinPairs(n, 0)
+    kept = {}
+
+    def front():
+        keys.copy_(build)
+        kept["ids"] = srt.launch(keys, None)
+        search.index(keys)
+        search.search(lo, hi)
+
+    front()
+    counter.launch(kept["ids"], search.pos, search.cnt)
+    total = counter.count()
+    plan = ops.JoinPairs(n, total)
+
+    def mine():
+        front()
+        plan.launch(kept["ids"], search.pos, search.cnt)
+
+    def vendor():
+        s, ids = torch.sort(build, stable=True)
+        pos = torch.searchsorted(s, lo, side="left")
+        cnt = torch.searchsorted(s, hi, side="right") - pos
+        return _torch_pairs(ids, pos, cnt, rid)
+
+    legs = {"range_join": [], "torch": []}
+    for _ in range(reps):  # alternating
+        legs["range_join"].append(median(times(mine, 5)))
+        legs["torch"].append(median(times(vendor, 5)))
+    mine()
+    b, p = plan.result()
+    words = ops.check_sorted_search(keys, lo, hi, search.pos, search.cnt)
+    tb, tp = vendor()
+    ok = (words[0] == 0 and words[2] == total == b.numel() and ops.check_sorted(keys)[0] == 0
+          and torch.equal(u64(b), tb) and torch.equal(p, tp) and ops.workspace_status(search.ws) == 0)
+    floor = max(legs["range_join"]) <= min(legs["torch"])
+    cols = "  ".join(f"{leg} {min(ts):9.1f} .. {max(ts):9.1f} us" for leg, ts in legs.items())
+    print(f"{TAG:10s} range-join n=2^{lg or 24} pairs={total:11d}  {cols}  floor {'holds' if floor else 'MISSED'}  "
+          f"{'ok' if ok else 'WRONG'}   " + " ".join(f"{leg}:" + "/".join(f"{t:.1f}" for t in ts) for leg, ts in legs.items()),
+          flush=True)
 
 
 def launch_sort_pairs(lg):
@@ -1187,7 +1310,7 @@ MODES = {"radix": radix, "ramp": ramp, "radix-idle": radix_idle, "radix-stream":
          "groupby-hash": groupby_hash, "sort-pairs": sort_pairs, "launch-sort-pairs": launch_sort_pairs,
          "join-pairs": join_pairs, "launch-join-pairs": launch_join_pairs, "topk": topk, "launch-topk": launch_topk,
          "groupby-sorted": groupby_sorted, "launch-groupby-sorted": launch_groupby_sorted,
-         "window": window, "launch-window": launch_window}
+         "window": window, "launch-window": launch_window, "sorted-search": sorted_search, "range-join": range_join}
 
 if __name__ == "__main__":
     if len(sys.argv) < 2 or sys.argv[1] not in MODES:
