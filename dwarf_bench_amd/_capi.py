@@ -1,4 +1,4 @@
-"""ctypes binding of libdbhip.so (include/dbhip.h).  Plumbing only: every compute call lands in the
+"""ctypes binding of libdbhip.so (include/dbhip*.h).  Plumbing only: every compute call lands in the
 hand-written gfx950 kernels.  There is NO fallback: if the library is missing or a symbol is absent the
 import of the product path fails loudly."""
 from __future__ import annotations
@@ -14,8 +14,9 @@ if os.environ.get("DBHIP_LIB"):  # kernel experiments: an alternative build of t
 c_u32p = C.POINTER(C.c_uint32)
 _vp, _sz, _u64, _u32, _i32, _int = C.c_void_p, C.c_size_t, C.c_uint64, C.c_uint32, C.c_int32, C.c_int
 
-# name -> (restype, argtypes); mirrors include/dbhip.h one to one (tests check the two stay in sync)
-SIGNATURES = {
+# header under include/ -> {entry point: (restype, argtypes)}; each table mirrors its header one to one, and the headers
+# are the ones in include/ (tests/test_capi_headers.py holds both)
+HEADERS = {"dbhip.h": {
     "dbhip_version": (_int, []),
     "dbhip_device_info": (_int, [_int, C.c_char_p, _sz, C.POINTER(_int), C.POINTER(_int)]),
     "dbhip_workspace_status": (_int, [_vp, C.POINTER(_u32), _vp]),
@@ -89,40 +90,28 @@ SIGNATURES = {
     "dbhip_check_distinct_u32": (_int, [_vp, _sz, _vp, _vp, _sz, _vp]),
     "dbhip_check_join_pairs_u32": (_int, [_vp, _sz, _vp, _sz, _vp, _vp, _vp, _vp, _int, _vp, _vp, _u64, _vp, _vp]),
     "dbhip_check_gen_uniform_u32": (_int, [_vp, _vp, _sz, _u64, _u64, _u32, _u32, _vp, _vp]),
-}
-
-# the same for include/dbhip_topk.h (tests/test_topk_host.py checks this pair)
-TOPK_SIGNATURES = {
+}, "dbhip_topk.h": {
     "dbhip_topk_workspace_bytes": (_sz, [_sz, _sz]),
     "dbhip_topk_u32": (_int, [_vp, _sz, _sz, _int, _int, _vp, _vp, _vp, _sz, _vp]),
     "dbhip_topk_i32": (_int, [_vp, _sz, _sz, _int, _int, _vp, _vp, _vp, _sz, _vp]),
     "dbhip_check_topk_u32": (_int, [_vp, _sz, _vp, _vp, _sz, _int, _int, _vp, _vp]),
-}
-
-# the same for include/dbhip_reduce_by_key.h (tests/test_reduce_by_key_host.py checks this pair)
-REDUCE_BY_KEY_SIGNATURES = {
+}, "dbhip_reduce_by_key.h": {
     "dbhip_reduce_by_key_workspace_bytes": (_sz, [_sz]),
     "dbhip_reduce_by_key_u32": (_int, [_vp, _vp, _sz, _int, _vp, _vp, _vp, _vp, _vp, _sz, _vp, _vp, _sz, _vp]),
     "dbhip_check_reduce_by_key_workspace_bytes": (_sz, [_sz, _sz]),
     "dbhip_check_reduce_by_key_u32": (_int, [_vp, _vp, _sz, _int, _vp, _vp, _vp, _vp, _vp, _sz, _vp, _vp, _sz, _vp]),
-}
-
-# the same for include/dbhip_scan_by_key.h (tests/test_scan_by_key_host.py checks this pair)
-SCAN_BY_KEY_SIGNATURES = {
+}, "dbhip_scan_by_key.h": {
     "dbhip_scan_by_key_workspace_bytes": (_sz, [_sz]),
     "dbhip_scan_by_key_u32": (_int, [_vp, _vp, _sz, _int, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "dbhip_check_scan_by_key_workspace_bytes": (_sz, [_sz]),
     "dbhip_check_scan_by_key_u32": (_int, [_vp, _vp, _sz, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
-}
-
-# the same for include/dbhip_sorted_search.h (tests/test_sorted_search_host.py checks this pair)
-SORTED_SEARCH_SIGNATURES = {
+}, "dbhip_sorted_search.h": {
     "dbhip_sorted_index_workspace_bytes": (_sz, [_sz, _u32]),
     "dbhip_sorted_index_build_u32": (_int, [_vp, _sz, _int, _u32, _vp, _sz, _vp]),
     "dbhip_sorted_search_u32": (_int, [_vp, _sz, _vp, _vp, _sz, _vp, _vp, _vp, _sz, _vp]),
     "dbhip_check_sorted_search_workspace_bytes": (_sz, [_sz]),
     "dbhip_check_sorted_search_u32": (_int, [_vp, _sz, _int, _vp, _vp, _sz, _vp, _vp, _vp, _vp, _sz, _vp]),
-}
+}}
 
 _lib = None
 
@@ -148,11 +137,11 @@ def lib() -> C.CDLL:
         except Exception:  # pragma: no cover - torch is plumbing, the C++ host layer runs without it
             pass
         handle = C.CDLL(str(_LIB_PATH), mode=C.RTLD_GLOBAL)
-        for name, (res, args) in {**SIGNATURES, **TOPK_SIGNATURES, **REDUCE_BY_KEY_SIGNATURES,
-                                   **SCAN_BY_KEY_SIGNATURES, **SORTED_SEARCH_SIGNATURES}.items():
-            fn = getattr(handle, name)  # AttributeError if the .so does not export the symbol
-            fn.restype = res
-            fn.argtypes = args
+        for table in HEADERS.values():
+            for name, (res, args) in table.items():
+                fn = getattr(handle, name)  # AttributeError if the .so does not export the symbol
+                fn.restype = res
+                fn.argtypes = args
         _lib = handle
     return _lib
 

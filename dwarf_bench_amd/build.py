@@ -66,15 +66,17 @@ def kernel_tree_sha256() -> str:
     return h.hexdigest()
 
 
+def public_headers() -> list[Path]:
+    """The C headers of libdbhip.so: one per table of _capi.HEADERS (tests/test_capi_headers.py holds the two together)."""
+    return sorted((ROOT / "include").glob("dbhip*.h"))
+
+
 def build_hip(force: bool = False) -> Path:
     """hipcc --offload-arch=gfx950: every .hip under csrc/ into one shared library."""
     LIB.mkdir(exist_ok=True)
     out = LIB / "libdbhip.so"
     srcs = sorted(CSRC.glob("*.hip"))
-    headers = sorted(CSRC.glob("*.hpp")) + [ROOT / "include" / "dbhip.h", ROOT / "include" / "dbhip_topk.h",
-                                              ROOT / "include" / "dbhip_reduce_by_key.h",
-                                              ROOT / "include" / "dbhip_scan_by_key.h",
-                                              ROOT / "include" / "dbhip_sorted_search.h"]
+    headers = sorted(CSRC.glob("*.hpp")) + public_headers()
     deps = srcs + headers
     if force or _stale(out, deps):
         objs = []

@@ -164,26 +164,9 @@ class Registry {
 };
 
 void populate_registry();  // register_dwarfs.cpp:20-56: here it registers the ...Hip dwarfs
-// the reference's EXPERIMENTAL block (register_dwarfs.cpp:41-47, CMakeLists.txt ENABLE_EXPERIMENTAL): the dwarfs only the
-// dwarf_bench_experimental CLI registers, after populate_registry()
-void populate_experimental_registry();
-// the reference's slab dwarfs (register_dwarfs.cpp:44-46, inside its EXPERIMENTAL block): only the dwarf_bench_slab CLI
-// registers them, after populate_registry()
-void populate_slab_registry();
-// GroupByHashHip: only the dwarf_bench_groupby_hash CLI registers it, after populate_registry()
-void populate_groupby_hash_registry();
-// RadixPairsHip: only the dwarf_bench_sort_pairs CLI registers it, after populate_registry()
-void populate_sort_pairs_registry();
-// JoinPairsHip: only the dwarf_bench_join_pairs CLI registers it, after populate_registry()
-void populate_join_pairs_registry();
-// TopKHip: only the dwarf_bench_topk CLI registers it, after populate_registry()
-void populate_topk_registry();
-// GroupBySortedHip: only the dwarf_bench_groupby_sorted CLI registers it, after populate_registry()
-void populate_groupby_sorted_registry();
-// WindowSortedHip: only the dwarf_bench_window CLI registers it, after populate_registry()
-void populate_window_registry();
-// RangeJoinHip: only the dwarf_bench_range_join CLI registers it, after populate_registry()
-void populate_range_join_registry();
+// the dwarfs of one named set (register_dwarfs.cpp kDwarfSets), after populate_registry(): what the dwarf_bench_<set> CLI adds
+// to the default list; false for a name that table does not have
+bool populate_dwarf_set(const std::string &set);
 
 namespace helpers {
 // $DWARF_BENCH_ROOT or the executable's directory (common/common.cpp:38-41, without Boost.DLL)

@@ -77,12 +77,12 @@ struct NestedLoopJoinHip : HipDwarf {  // join/nested_join.cpp:10-110 (dense cel
   NestedLoopJoinHip() : HipDwarf("NestedLoopJoinHip") {}
   void _run(size_t buf_size, Meter &meter) override;
 };
-// the reference's EXPERIMENTAL block: registered by populate_experimental_registry() only
+// the reference's EXPERIMENTAL block: registered by the set "experimental" only (register_dwarfs.cpp kDwarfSets)
 struct CuckooHashBuildHip : HipDwarf {  // hash/cuckoo_hash_build.cpp:8-134 (lock-free cuckoo table, rebuild on failure)
   CuckooHashBuildHip() : HipDwarf("CuckooHashBuildHip") {}
   void _run(size_t buf_size, Meter &meter) override;
 };
-// the reference's EXPERIMENTAL slab dwarfs: registered by populate_slab_registry() only (the dwarf_bench_slab CLI)
+// the reference's EXPERIMENTAL slab dwarfs: registered by the set "slab" only
 struct SlabHashBuildHip : HipDwarf {  // hash/slab_hash_build.cpp:9-108 (lock-free slab table, insert timed)
   SlabHashBuildHip() : HipDwarf("SlabHashBuildHip") {}
   void _run(size_t buf_size, Meter &meter) override;
@@ -95,49 +95,47 @@ struct SlabJoinHip : HipDwarf {  // join/slab_join.cpp:10-144 (build and probe t
   SlabJoinHip() : HipDwarf("SlabJoinHip") {}
   void _run(size_t buf_size, Meter &meter) override;
 };
-// group-by on arbitrary 32-bit keys (SUM and COUNT): registered by populate_groupby_hash_registry() only (the
-// dwarf_bench_groupby_hash CLI)
+// group-by on arbitrary 32-bit keys (SUM and COUNT): registered by the set "groupby_hash" only
 struct GroupByHashHip : HipDwarf {  // groupby/groupby.cpp:58-93 (the hash table keyed by the group key)
   GroupByHashHip() : HipDwarf("GroupByHashHip") {}
   void _run(size_t buf_size, Meter &meter) override;
 };
-// the argsort (key-value radix sort with row ids as values): registered by populate_sort_pairs_registry() only (the
-// dwarf_bench_sort_pairs CLI); no reference counterpart, the reference sorts keys only
+// the argsort (key-value radix sort with row ids as values): registered by the set "sort_pairs" only; no
+// reference counterpart, the reference sorts keys only
 struct RadixPairsHip : RadixHip {  // RadixHip's init and digit width
   RadixPairsHip() : RadixHip("RadixPairsHip") {}
   void _run(size_t buf_size, Meter &meter) override;
 };
 // the join result as a table of (build row, probe row) pairs (radix join + dbhip_join_pairs_u32): registered by
-// populate_join_pairs_registry() only (the dwarf_bench_join_pairs CLI); no reference counterpart, JoinOmnisci stops at the
-// per-row {pointer, size} record
+// the set "join_pairs" only; no reference counterpart, JoinOmnisci stops at the per-row {pointer, size} record
 struct JoinPairsHip : HipDwarf {
   JoinPairsHip() : HipDwarf("JoinPairsHip") {}
   void _run(size_t buf_size, Meter &meter) override;
 };
-// ORDER BY key LIMIT k (dbhip_topk_i32, include/dbhip_topk.h): registered by populate_topk_registry() only (the
-// dwarf_bench_topk CLI); no reference counterpart.  k: DWARF_BENCH_TOPK_K (default 1024, clipped to the row count),
+// ORDER BY key LIMIT k (dbhip_topk_i32, include/dbhip_topk.h): registered by the set "topk" only; no
+// reference counterpart.  k: DWARF_BENCH_TOPK_K (default 1024, clipped to the row count),
 // DWARF_BENCH_TOPK_LARGEST=1: the largest keys
 struct TopKHip : HipDwarf {
   TopKHip() : HipDwarf("TopKHip") {}
   void _run(size_t buf_size, Meter &meter) override;
 };
 // GROUP BY key ORDER BY key with COUNT, 64-bit SUM, MIN, MAX: the stable pairs sort and dbhip_reduce_by_key_u32
-// (include/dbhip_reduce_by_key.h); registered by populate_groupby_sorted_registry() only (the dwarf_bench_groupby_sorted
-// CLI); no reference counterpart.  --groups_count as GroupByHashHip
+// (include/dbhip_reduce_by_key.h); registered by the set "groupby_sorted" only; no reference counterpart.
+// --groups_count as GroupByHashHip
 struct GroupBySortedHip : HipDwarf {
   GroupBySortedHip() : HipDwarf("GroupBySortedHip") {}
   void _run(size_t buf_size, Meter &meter) override;
 };
 // ROW_NUMBER, running 64-bit SUM, MIN, MAX and the run number per row over PARTITION BY key ORDER BY row: the stable pairs
-// sort and dbhip_scan_by_key_u32 (include/dbhip_scan_by_key.h); registered by populate_window_registry() only (the
-// dwarf_bench_window CLI); no reference counterpart.  --groups_count as GroupByHashHip
+// sort and dbhip_scan_by_key_u32 (include/dbhip_scan_by_key.h); registered by the set "window" only; no reference
+// counterpart.  --groups_count as GroupByHashHip
 struct WindowSortedHip : HipDwarf {
   WindowSortedHip() : HipDwarf("WindowSortedHip") {}
   void _run(size_t buf_size, Meter &meter) override;
 };
 // The band join b.key BETWEEN p.lo AND p.hi as (build row, probe row) pairs: the stable pairs sort, the sorted search of
-// include/dbhip_sorted_search.h and dbhip_join_pairs_u32; registered by populate_range_join_registry() only (the
-// dwarf_bench_range_join CLI); no reference counterpart.  DWARF_BENCH_RANGE_WIDTH: hi - lo (default 2)
+// include/dbhip_sorted_search.h and dbhip_join_pairs_u32; registered by the set "range_join" only; no reference
+// counterpart.  DWARF_BENCH_RANGE_WIDTH: hi - lo (default 2)
 struct RangeJoinHip : HipDwarf {
   RangeJoinHip() : HipDwarf("RangeJoinHip") {}
   void _run(size_t buf_size, Meter &meter) override;

@@ -3,17 +3,8 @@
 //   dwarf_bench <Dwarf|list> [--input_size N [N ...]] [--iterations K] [--device cpu|gpu|igpu|hip]
 //               [--report_path FILE] [--groups_count G] [--executors E] [--gpus P] [--help]
 // Exit codes as in the reference: 1 for an unknown dwarf, 0 otherwise — also after a caught exception.
-// Built twice: `dwarf_bench`, and with -DEXPERIMENTAL `dwarf_bench_experimental`, which also registers the reference's
-// EXPERIMENTAL dwarfs that have a HIP counterpart (populate_experimental_registry), and with -DEXPERIMENTAL_SLAB
-// `dwarf_bench_slab`, the default set plus the slab dwarfs (populate_slab_registry), and with -DEXPERIMENTAL_GROUPBY_HASH
-// `dwarf_bench_groupby_hash`, the default set plus GroupByHashHip (populate_groupby_hash_registry), and with
-// -DEXPERIMENTAL_SORT_PAIRS `dwarf_bench_sort_pairs`, the default set plus RadixPairsHip (populate_sort_pairs_registry),
-// and with -DEXPERIMENTAL_JOIN_PAIRS `dwarf_bench_join_pairs`, the default set plus JoinPairsHip
-// (populate_join_pairs_registry), and with -DEXPERIMENTAL_TOPK `dwarf_bench_topk`, the default set plus TopKHip
-// (populate_topk_registry), and with -DEXPERIMENTAL_GROUPBY_SORTED `dwarf_bench_groupby_sorted`, the default set plus
-// GroupBySortedHip (populate_groupby_sorted_registry), and with -DEXPERIMENTAL_WINDOW `dwarf_bench_window`, the default
-// set plus WindowSortedHip (populate_window_registry), and with -DEXPERIMENTAL_RANGE_JOIN `dwarf_bench_range_join`, the
-// default set plus RangeJoinHip (populate_range_join_registry).
+// Built once per CLI: `dwarf_bench`, and `dwarf_bench_<set>` with -DDWARF_BENCH_SET="<set>" for every set of
+// register_dwarfs.cpp's kDwarfSets (the Makefile's SETS): the default dwarfs plus that set's (exit code 2: no such set).
 #include <iostream>
 #include <memory>
 #include <sstream>
@@ -46,32 +37,11 @@ bool is_flag(const std::string &s) { return s.rfind("--", 0) == 0; }
 
 int main(int argc, char *argv[]) {
   populate_registry();
-#ifdef EXPERIMENTAL
-  populate_experimental_registry();  // dwarf_bench_experimental
-#endif
-#ifdef EXPERIMENTAL_SLAB
-  populate_slab_registry();  // dwarf_bench_slab
-#endif
-#ifdef EXPERIMENTAL_GROUPBY_HASH
-  populate_groupby_hash_registry();  // dwarf_bench_groupby_hash
-#endif
-#ifdef EXPERIMENTAL_SORT_PAIRS
-  populate_sort_pairs_registry();  // dwarf_bench_sort_pairs
-#endif
-#ifdef EXPERIMENTAL_JOIN_PAIRS
-  populate_join_pairs_registry();  // dwarf_bench_join_pairs
-#endif
-#ifdef EXPERIMENTAL_TOPK
-  populate_topk_registry();  // dwarf_bench_topk
-#endif
-#ifdef EXPERIMENTAL_GROUPBY_SORTED
-  populate_groupby_sorted_registry();  // dwarf_bench_groupby_sorted
-#endif
-#ifdef EXPERIMENTAL_WINDOW
-  populate_window_registry();  // dwarf_bench_window
-#endif
-#ifdef EXPERIMENTAL_RANGE_JOIN
-  populate_range_join_registry();  // dwarf_bench_range_join
+#ifdef DWARF_BENCH_SET
+  if (!populate_dwarf_set(DWARF_BENCH_SET)) {
+    std::cerr << argv[0] << ": built for the dwarf set '" << DWARF_BENCH_SET << "', which register_dwarfs.cpp does not have\n";
+    return 2;
+  }
 #endif
   Registry *registry = Registry::instance();
 

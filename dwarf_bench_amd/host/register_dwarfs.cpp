@@ -2,11 +2,14 @@
 // registers its dwarfs under EXPERIMENTAL / DPCPP_ENABLED / CUDA_ENABLED guards; this build has one
 // guard, HIP_ENABLED, and registers the hand-written gfx950 dwarfs — plus, unguarded, the two HOST dwarfs of the hot
 // path under the reference's own names (cpu_dwarfs.cpp: TwoPassScan for --device=cpu, TBBSort).
-// populate_experimental_registry() is the reference's `#ifdef EXPERIMENTAL` block (:41-47): only the
-// dwarf_bench_experimental CLI (main.cpp built with -DEXPERIMENTAL) calls it.
+// The dwarfs beyond that list come in named sets, kDwarfSets below: the dwarf_bench_<set> CLI is main.cpp built with
+// -DDWARF_BENCH_SET="<set>" and registers the default list plus the rows of its set, so `dwarf_bench list` and
+// DwarfBench::makeMeasurements stay what they are in the reference.
 #include "cpu_dwarfs.hpp"
 #include "dwarf_api.hpp"
 #include "hip_dwarfs.hpp"
+
+#include <vector>
 
 void populate_registry() {
   Registry *registry = Registry::instance();
@@ -29,76 +32,39 @@ void populate_registry() {
 #endif
 }
 
-void populate_experimental_registry() {
-#ifdef HIP_ENABLED
-  Registry *registry = Registry::instance();
-  registry->registerd(new CuckooHashBuildHip());  // hash/cuckoo_hash_build.cpp (register_dwarfs.cpp:44 in the reference)
-#endif
+namespace {
+template <class T>
+Dwarf *make() {
+  return new T();
 }
-
-// the reference's SlabHashBuild, SlabJoin and SlabProbe (register_dwarfs.cpp:44-46): only the dwarf_bench_slab CLI (main.cpp
-// built with -DEXPERIMENTAL_SLAB) calls this, so the lists of dwarf_bench and dwarf_bench_experimental stay as they are
-void populate_slab_registry() {
+struct SetRow {
+  const char *set;
+  Dwarf *(*make)();
+};
+// set name (the CLI's suffix, a word of SETS in the Makefile) -> a dwarf it registers; one set per dwarf
+const std::vector<SetRow> kDwarfSets = {
 #ifdef HIP_ENABLED
-  Registry *registry = Registry::instance();
-  registry->registerd(new SlabHashBuildHip());  // hash/slab_hash_build.cpp
-  registry->registerd(new SlabJoinHip());       // join/slab_join.cpp
-  registry->registerd(new SlabProbeHip());      // probe/slab_probe.cpp
+    {"experimental", make<CuckooHashBuildHip>},  // hash/cuckoo_hash_build.cpp, the reference's EXPERIMENTAL block (:41-47)
+    {"slab", make<SlabHashBuildHip>},            // hash/slab_hash_build.cpp (:44-46 in the reference, with the next two)
+    {"slab", make<SlabJoinHip>},                 // join/slab_join.cpp
+    {"slab", make<SlabProbeHip>},                // probe/slab_probe.cpp
+    {"groupby_hash", make<GroupByHashHip>},      // group-by on arbitrary 32-bit keys (dbhip_groupby_hash_u32)
+    {"sort_pairs", make<RadixPairsHip>},         // the key-value sort's argsort (dbhip_radix_sort_pairs_i32)
+    {"join_pairs", make<JoinPairsHip>},          // the join's pair table (dbhip_join_pairs_u32)
+    {"topk", make<TopKHip>},                     // ORDER BY key LIMIT k (dbhip_topk_i32)
+    {"groupby_sorted", make<GroupBySortedHip>},  // pairs sort + dbhip_reduce_by_key_u32
+    {"window", make<WindowSortedHip>},           // pairs sort + dbhip_scan_by_key_u32
+    {"range_join", make<RangeJoinHip>},          // pairs sort + the sorted search + dbhip_join_pairs_u32
 #endif
-}
+};
+}  // namespace
 
-// the general group-by (dbhip_groupby_hash_u32): only the dwarf_bench_groupby_hash CLI (main.cpp built with
-// -DEXPERIMENTAL_GROUPBY_HASH) calls this, so the lists of the other three CLIs stay as they are
-void populate_groupby_hash_registry() {
-#ifdef HIP_ENABLED
-  Registry::instance()->registerd(new GroupByHashHip());
-#endif
-}
-
-// the key-value sort's argsort (dbhip_radix_sort_pairs_i32): only the dwarf_bench_sort_pairs CLI (main.cpp built with
-// -DEXPERIMENTAL_SORT_PAIRS) calls this, so the lists of the other four CLIs stay as they are
-void populate_sort_pairs_registry() {
-#ifdef HIP_ENABLED
-  Registry::instance()->registerd(new RadixPairsHip());
-#endif
-}
-
-// the join's pair table (dbhip_join_pairs_u32): only the dwarf_bench_join_pairs CLI (main.cpp built with
-// -DEXPERIMENTAL_JOIN_PAIRS) calls this, so the lists of the other five CLIs stay as they are
-void populate_join_pairs_registry() {
-#ifdef HIP_ENABLED
-  Registry::instance()->registerd(new JoinPairsHip());
-#endif
-}
-
-// the top-k (dbhip_topk_i32): only the dwarf_bench_topk CLI (main.cpp built with -DEXPERIMENTAL_TOPK) calls this, so the
-// lists of the other six CLIs stay as they are
-void populate_topk_registry() {
-#ifdef HIP_ENABLED
-  Registry::instance()->registerd(new TopKHip());
-#endif
-}
-
-// the sort-based group-by (dbhip_radix_sort_pairs_u32 + dbhip_reduce_by_key_u32): only the dwarf_bench_groupby_sorted CLI
-// (main.cpp built with -DEXPERIMENTAL_GROUPBY_SORTED) calls this, so the lists of the other seven CLIs stay as they are
-void populate_groupby_sorted_registry() {
-#ifdef HIP_ENABLED
-  Registry::instance()->registerd(new GroupBySortedHip());
-#endif
-}
-
-// the window functions (dbhip_radix_sort_pairs_u32 + dbhip_scan_by_key_u32): only the dwarf_bench_window CLI (main.cpp built
-// with -DEXPERIMENTAL_WINDOW) calls this, so the lists of the other eight CLIs stay as they are
-void populate_window_registry() {
-#ifdef HIP_ENABLED
-  Registry::instance()->registerd(new WindowSortedHip());
-#endif
-}
-
-// the range join (dbhip_radix_sort_pairs_u32 + the sorted search + dbhip_join_pairs_u32): only the dwarf_bench_range_join CLI
-// (main.cpp built with -DEXPERIMENTAL_RANGE_JOIN) calls this, so the lists of the other nine CLIs stay as they are
-void populate_range_join_registry() {
-#ifdef HIP_ENABLED
-  Registry::instance()->registerd(new RangeJoinHip());
-#endif
+bool populate_dwarf_set(const std::string &set) {
+  bool known = false;
+  for (const SetRow &row : kDwarfSets) {
+    if (set != row.set) continue;
+    Registry::instance()->registerd(row.make());
+    known = true;
+  }
+  return known;
 }

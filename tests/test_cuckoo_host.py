@@ -1,6 +1,5 @@
 """The cuckoo table without a GPU: the Python model against the reference tests' assertions, the C ABI's workspace
-query and argument checks (host-side, before any HIP call), the compiled code object of csrc/cuckoo.hip, and the
-experimental CLI's dwarf list."""
+query and argument checks (host-side, before any HIP call), and the compiled code object of csrc/cuckoo.hip."""
 import json
 import re
 import subprocess
@@ -9,11 +8,10 @@ from pathlib import Path
 import pytest
 
 from dwarf_bench_amd import _capi
+from tests.capi_testlib import EINVAL, EWORKSPACE
 from tests.cuckoo_model import EMPTY_KEY, CuckooModel
 
 ROOT = Path(__file__).resolve().parents[1]
-LIB = ROOT / "dwarf_bench_amd" / "_lib"
-EINVAL, EWORKSPACE = -1, -2
 
 
 @pytest.fixture(scope="module")
@@ -117,24 +115,6 @@ def test_code_object_swaps_with_one_atomic_and_has_no_scratch(tmp_path):
     meta = re.findall(r"\.name:\s+(_ZN\S*ck_\w+)\s*\n(?:.*\n)*?\s*\.private_segment_fixed_size:\s+(\d+)", asm)
     assert len(meta) == 4 and all(size == "0" for _, size in meta), meta
     assert "scratch_" not in "".join(bodies.values())
-
-
-def _names(exe):
-    r = subprocess.run([str(exe), "list"], capture_output=True, text=True, timeout=60)
-    assert r.returncode == 0
-    return [l.strip() for l in r.stdout.splitlines() if l.startswith("\t")]
-
-
-def test_experimental_cli_lists_the_cuckoo_dwarf_and_the_default_one_does_not():
-    exe, exp = LIB / "dwarf_bench", LIB / "dwarf_bench_experimental"
-    if not exe.exists() or not exp.exists():
-        from dwarf_bench_amd import build
-        build.build_hip()
-        build.build_host()
-    default, experimental = _names(exe), _names(exp)
-    assert "CuckooHashBuildHip" not in default
-    assert "CuckooHashBuildHip" in experimental and set(default) <= set(experimental)
-    assert sorted(set(experimental) - set(default)) == ["CuckooHashBuildHip"]
 
 
 def test_vectorised_murmur_matches_the_oracle():

@@ -5,7 +5,7 @@ hold a guard word; every replay is compared with numpy and, bitwise, with an eag
 validator is captured behind a captured call: accept, reject a poked table, accept.
 
 COVERAGE is for the entry points of include/dbhip_reduce_by_key.h what the table in tests/graph_testlib.py is for those of
-include/dbhip.h; tests/test_reduce_by_key_host.py holds it to the header."""
+include/dbhip.h; tests/test_capi_headers.py holds it to the header."""
 import numpy as np
 import pytest
 import torch

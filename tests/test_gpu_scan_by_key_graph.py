@@ -6,7 +6,7 @@ with numpy and, bitwise, with an eager run of the same plan shape.  The validato
 accept, reject a poked table, accept.
 
 COVERAGE is for the entry points of include/dbhip_scan_by_key.h what the table in tests/graph_testlib.py is for those of
-include/dbhip.h; tests/test_scan_by_key_host.py holds it to the header."""
+include/dbhip.h; tests/test_capi_headers.py holds it to the header."""
 import numpy as np
 import pytest
 import torch

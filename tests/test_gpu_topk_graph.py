@@ -5,7 +5,7 @@ workspace is poisoned and the outputs hold a guard word; every replay is compare
 run of the same plan shape.  The validator is captured behind a captured top-k: accept, reject a poked table, accept.
 
 COVERAGE is for the entry points of include/dbhip_topk.h what the table in tests/graph_testlib.py is for those of
-include/dbhip.h; tests/test_topk_host.py holds it to the header."""
+include/dbhip.h; tests/test_capi_headers.py holds it to the header."""
 import numpy as np
 import pytest
 import torch

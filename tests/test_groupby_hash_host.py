@@ -1,6 +1,5 @@
-"""The general group-by (dbhip_groupby_hash_u32) without a GPU: the C ABI declared, bound and exported, the workspace
-query, the host-side argument checks (before any HIP call), the compiled code object of csrc/groupby_hash.hip and the
-dwarf list of the group-by CLI."""
+"""The general group-by (dbhip_groupby_hash_u32) without a GPU: the workspace query, the host-side argument
+checks (before any HIP call), the compiled code object of csrc/groupby_hash.hip and the shape tests' constructed inputs."""
 import re
 import subprocess
 from pathlib import Path
@@ -8,21 +7,9 @@ from pathlib import Path
 import pytest
 
 from dwarf_bench_amd import _capi
+from tests.capi_testlib import EINVAL, EWORKSPACE
 
 ROOT = Path(__file__).resolve().parents[1]
-LIB = ROOT / "dwarf_bench_amd" / "_lib"
-EINVAL, EWORKSPACE = -1, -2
-NEW = ("dbhip_groupby_hash_workspace_bytes", "dbhip_groupby_hash_u32", "dbhip_check_distinct_workspace_bytes",
-       "dbhip_check_distinct_u32")
-
-
-def test_entry_points_are_declared_bound_and_exported():
-    header = re.sub(r"/\*.*?\*/", "", (ROOT / "include" / "dbhip.h").read_text(), flags=re.S)
-    lib = _capi.lib()
-    for name in NEW:
-        assert re.search(rf"\b{name}\s*\(", header), name
-        assert name in _capi.SIGNATURES, name
-        assert hasattr(lib, name), name
 
 
 def test_workspace_query():
@@ -86,25 +73,6 @@ def test_code_object_has_no_scratch_and_uses_lds_cas(tmp_path):
     lds = next(b for name, b in bodies.items() if "gbh_lds_kernel" in name)
     assert "ds_cmpst" in lds and "ds_add_u32" in lds
     assert "global_atomic_cmpswap " in lds  # the flush / overflow into the global table
-
-
-def _names(exe):
-    r = subprocess.run([str(exe), "list"], capture_output=True, text=True, timeout=60)
-    assert r.returncode == 0
-    return [l.strip() for l in r.stdout.splitlines() if l.startswith("\t")]
-
-
-def test_groupby_hash_cli_lists_the_default_set_plus_its_dwarf():
-    exe, gbh = LIB / "dwarf_bench", LIB / "dwarf_bench_groupby_hash"
-    if not exe.exists() or not gbh.exists():
-        from dwarf_bench_amd import build
-        build.build_hip()
-        build.build_host()
-    default, with_gbh = _names(exe), _names(gbh)
-    assert sorted(set(with_gbh) - set(default)) == ["GroupByHashHip"] and len(with_gbh) == len(default) + 1
-    assert set(default) <= set(with_gbh)
-    for other in ("dwarf_bench", "dwarf_bench_experimental", "dwarf_bench_slab"):
-        assert "GroupByHashHip" not in _names(LIB / other)
 
 
 # ---- the constructed inputs of tests/test_gpu_groupby_hash_shapes.py do what their names say ----------------------

@@ -1,26 +1,9 @@
-"""The join's pair table (dbhip_join_pairs_u32, dbhip_check_join_pairs_u32) without a GPU: the C ABI declared, bound and
-exported, the workspace query, the host-side argument checks (all before any HIP call) and the dwarf lists of the CLIs."""
-import re
-import subprocess
-from pathlib import Path
-
+"""The join's pair table (dbhip_join_pairs_u32, dbhip_check_join_pairs_u32) without a GPU: the workspace query and the
+host-side argument checks (all before any HIP call)."""
 import pytest
 
 from dwarf_bench_amd import _capi
-
-ROOT = Path(__file__).resolve().parents[1]
-LIB = ROOT / "dwarf_bench_amd" / "_lib"
-EINVAL, EWORKSPACE = -1, -2
-NEW = ("dbhip_join_pairs_workspace_bytes", "dbhip_join_pairs_u32", "dbhip_check_join_pairs_u32")
-
-
-def test_entry_points_are_declared_bound_and_exported():
-    header = re.sub(r"/\*.*?\*/", "", (ROOT / "include" / "dbhip.h").read_text(), flags=re.S)
-    lib = _capi.lib()
-    for name in NEW:
-        assert re.search(rf"\b{name}\s*\(", header), name
-        assert name in _capi.SIGNATURES, name
-        assert hasattr(lib, name), name
+from tests.capi_testlib import EINVAL, EWORKSPACE
 
 
 def test_workspace_query():
@@ -85,40 +68,3 @@ def test_ops_has_the_plan_and_refuses_host_tensors():
     t = torch.zeros(16, dtype=torch.int32)
     with pytest.raises(ValueError):
         ops.check_join_pairs(t, t, t, t, t, t, t)  # not on the GPU
-
-
-def _names(exe):
-    r = subprocess.run([str(exe), "list"], capture_output=True, text=True, timeout=60)
-    assert r.returncode == 0
-    return [l.strip() for l in r.stdout.splitlines() if l.startswith("\t")]
-
-
-DEFAULT = ["DPLScanHip", "GroupByHip", "GroupByLocalHip", "HashBuildHip", "HashBuildNonBitmaskHip", "JoinHip",
-           "JoinOmnisciHip", "NestedLoopJoinHip", "PartitionedJoinHip", "ProbeHip", "RadixHip", "ReduceHip", "TBBSort",
-           "TwoPassScan", "TwoPassScanHip"]
-# the dwarf lists of the five CLIs before JoinPairsHip existed
-OTHER_CLIS = {
-    "dwarf_bench": DEFAULT,
-    "dwarf_bench_experimental": sorted(DEFAULT + ["CuckooHashBuildHip"]),
-    "dwarf_bench_slab": sorted(DEFAULT + ["SlabHashBuildHip", "SlabJoinHip", "SlabProbeHip"]),
-    "dwarf_bench_groupby_hash": sorted(DEFAULT + ["GroupByHashHip"]),
-    "dwarf_bench_sort_pairs": sorted(DEFAULT + ["RadixPairsHip"]),
-}
-
-
-def _built():
-    if not all((LIB / exe).exists() for exe in list(OTHER_CLIS) + ["dwarf_bench_join_pairs"]):
-        from dwarf_bench_amd import build
-        build.build_hip()
-        build.build_host()
-
-
-def test_join_pairs_cli_lists_the_default_set_plus_its_dwarf():
-    _built()
-    assert _names(LIB / "dwarf_bench_join_pairs") == sorted(DEFAULT + ["JoinPairsHip"])
-
-
-@pytest.mark.parametrize("exe", sorted(OTHER_CLIS))
-def test_the_other_clis_list_what_they_listed_before(exe):
-    _built()
-    assert _names(LIB / exe) == OTHER_CLIS[exe]

@@ -1,44 +1,15 @@
-"""The reduce by key (include/dbhip_reduce_by_key.h) without a GPU: the third header declared, bound and exported, the
-workspace queries against the bounds the header states, the host-side argument checks (all before any HIP call), the
-tensor API's refusals, the dwarf list of the new CLI, and the capture test of every entry point that works on a stream."""
-from pathlib import Path
-
+"""The reduce by key (include/dbhip_reduce_by_key.h) without a GPU: the workspace queries against the bounds the header
+states, the host-side argument checks (all before any HIP call) and the tensor API's refusals."""
 import pytest
 
 from dwarf_bench_amd import _capi
-from tests import test_topk_host as th
-from tests.test_join_pairs_host import DEFAULT
-
-ROOT = Path(__file__).resolve().parents[1]
-LIB = ROOT / "dwarf_bench_amd" / "_lib"
-EINVAL, EWORKSPACE, OK = -1, -2, 0
-HEADER = "dbhip_reduce_by_key.h"
-NAMES = ["dbhip_check_reduce_by_key_u32", "dbhip_check_reduce_by_key_workspace_bytes", "dbhip_reduce_by_key_u32",
-         "dbhip_reduce_by_key_workspace_bytes"]
-
-
-def test_entry_points_are_declared_bound_and_exported():
-    names = th._declared(HEADER)
-    assert names == NAMES == sorted(_capi.REDUCE_BY_KEY_SIGNATURES)
-    lib = _capi.lib()
-    for name in names:
-        fn = getattr(lib, name)
-        res, args = _capi.REDUCE_BY_KEY_SIGNATURES[name]
-        assert list(fn.argtypes) == args and fn.restype == res, name
-
-
-def test_the_older_headers_and_their_tables_are_what_they_were():
-    assert th._declared("dbhip.h") == sorted(_capi.SIGNATURES)
-    assert th._declared("dbhip_topk.h") == sorted(_capi.TOPK_SIGNATURES)
-    older = set(_capi.SIGNATURES) | set(_capi.TOPK_SIGNATURES)
-    assert not older & set(_capi.REDUCE_BY_KEY_SIGNATURES)
-    assert not any("reduce_by_key" in name for name in older)
+from tests.capi_testlib import EINVAL, EWORKSPACE, OK, SIZES
 
 
 def test_workspace_queries():
     lib = _capi.lib()
     ws, cws = lib.dbhip_reduce_by_key_workspace_bytes, lib.dbhip_check_reduce_by_key_workspace_bytes
-    for n in th.SIZES:
+    for n in SIZES:
         got = ws(n)
         # include/dbhip_reduce_by_key.h: 2048 + n / 64; and it holds 56 bytes per 4096-row segment behind the header
         assert got % 256 == 0 and 256 <= got <= 2048 + n // 64, (n, got)
@@ -127,10 +98,6 @@ def test_ops_has_the_plan_and_refuses_host_tensors_wrong_types_and_slices():
     for name in ("ReduceByKey", "reduce_by_key", "groupby_sorted", "check_reduce_by_key", "REDUCE_BY_KEY_CHUNK_ROWS",
                  "REDUCE_BY_KEY_SEGMENT_ROWS"):
         assert hasattr(ops, name), name
-    header = (ROOT / "include" / HEADER).read_text()
-    assert f"#define DBHIP_REDUCE_BY_KEY_CHUNK_ROWS {ops.REDUCE_BY_KEY_CHUNK_ROWS} " in header
-    assert f"#define DBHIP_REDUCE_BY_KEY_SEGMENT_ROWS {ops.REDUCE_BY_KEY_SEGMENT_ROWS} " in header
-    assert ops.REDUCE_BY_KEY_CHUNK_ROWS == 8 * ops.REDUCE_BY_KEY_SEGMENT_ROWS
     t = torch.zeros(16, dtype=torch.int32)
     for call in (lambda: ops.reduce_by_key(t, t), lambda: ops.groupby_sorted(t, t),
                  lambda: ops.check_reduce_by_key(t, t, t[:3], t[:3], t[:3].long(), t[:3], t[:3])):
@@ -144,28 +111,3 @@ def test_ops_has_the_plan_and_refuses_host_tensors_wrong_types_and_slices():
         ops.ReduceByKey(1 << 32, 1, device="cpu")
     with pytest.raises(ValueError):
         ops.ReduceByKey(16, -1, device="cpu")
-
-
-def test_groupby_sorted_cli_lists_the_default_set_plus_its_dwarf():
-    if not (LIB / "dwarf_bench_groupby_sorted").exists():
-        from dwarf_bench_amd import build
-        build.build_hip()
-        build.build_host()
-    assert th._names(LIB / "dwarf_bench_groupby_sorted") == sorted(DEFAULT + ["GroupBySortedHip"])
-
-
-def test_every_stream_working_entry_point_has_a_capture_test():
-    """what a COVERAGE row in tests/graph_testlib.py says for the entry points of dbhip.h"""
-    pytest.importorskip("torch")
-    from tests import graph_testlib as gl
-    from tests import test_gpu_reduce_by_key_graph as tg
-    assert sorted(tg.COVERAGE) == th._declared(HEADER)
-    assert sorted(name for name, test in tg.COVERAGE.items() if test == gl.NO_STREAM_WORK) == [
-        "dbhip_check_reduce_by_key_workspace_bytes", "dbhip_reduce_by_key_workspace_bytes"]
-    source = (ROOT / "tests" / "test_gpu_reduce_by_key_graph.py").read_text()
-    for name, test in tg.COVERAGE.items():
-        if test == gl.NO_STREAM_WORK:
-            continue
-        assert callable(getattr(tg, test, None)) and test.startswith("test_"), (name, test)
-        body = source.split(f"def {test}(")[1].split("\ndef ")[0]
-        assert "capture" in body or "run_family" in body, (name, test)

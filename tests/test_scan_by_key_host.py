@@ -1,52 +1,20 @@
-"""The scan by key (include/dbhip_scan_by_key.h) without a GPU: the fourth header declared, bound and exported, the workspace
-queries against the bound the header states, the host-side argument checks (all before any HIP call, in the header's order),
-the tensor API's refusals, the dwarf list of the new CLI, and the capture test of every entry point that works on a stream."""
-from pathlib import Path
-
+"""The scan by key (include/dbhip_scan_by_key.h) without a GPU: the workspace queries against the bound the header states,
+the host-side argument checks (all before any HIP call, in the header's order) and the tensor API's refusals."""
 import pytest
 
 from dwarf_bench_amd import _capi
-from tests import test_topk_host as th
-from tests.test_join_pairs_host import DEFAULT
+from tests.capi_testlib import EINVAL, EWORKSPACE, INCLUDE, OK, SIZES
 
-ROOT = Path(__file__).resolve().parents[1]
-LIB = ROOT / "dwarf_bench_amd" / "_lib"
-EINVAL, EWORKSPACE, OK = -1, -2, 0
 HEADER = "dbhip_scan_by_key.h"
-NAMES = ["dbhip_check_scan_by_key_u32", "dbhip_check_scan_by_key_workspace_bytes", "dbhip_scan_by_key_u32",
-         "dbhip_scan_by_key_workspace_bytes"]
 COLS = ("run", "num", "osum", "omn", "omx")
-
-
-def test_entry_points_are_declared_bound_and_exported():
-    names = th._declared(HEADER)
-    assert names == NAMES == sorted(_capi.SCAN_BY_KEY_SIGNATURES)
-    lib = _capi.lib()
-    for name in names:
-        fn = getattr(lib, name)
-        res, args = _capi.SCAN_BY_KEY_SIGNATURES[name]
-        assert list(fn.argtypes) == args and fn.restype == res, name
-
-
-def test_the_older_headers_and_their_tables_are_what_they_were():
-    assert th._declared("dbhip.h") == sorted(_capi.SIGNATURES)
-    assert th._declared("dbhip_topk.h") == sorted(_capi.TOPK_SIGNATURES)
-    assert th._declared("dbhip_reduce_by_key.h") == sorted(_capi.REDUCE_BY_KEY_SIGNATURES)
-    assert len(_capi.SIGNATURES) == 73 and len(_capi.TOPK_SIGNATURES) == 4 and len(_capi.REDUCE_BY_KEY_SIGNATURES) == 4
-    older = set(_capi.SIGNATURES) | set(_capi.TOPK_SIGNATURES) | set(_capi.REDUCE_BY_KEY_SIGNATURES)
-    assert not older & set(_capi.SCAN_BY_KEY_SIGNATURES)
-    assert not any("scan_by_key" in name for name in older)
-    assert not any("reduce_by_key" in name or "topk" in name for name in _capi.SCAN_BY_KEY_SIGNATURES)
-    from tests import graph_testlib as gl
-    assert sorted(gl.COVERAGE) == th._declared("dbhip.h")
 
 
 def test_workspace_queries():
     lib = _capi.lib()
     ws, cws = lib.dbhip_scan_by_key_workspace_bytes, lib.dbhip_check_scan_by_key_workspace_bytes
-    header = (ROOT / "include" / HEADER).read_text()
+    header = (INCLUDE / HEADER).read_text()
     assert "dbhip_scan_by_key_workspace_bytes(n) <= 2048 + n / 64, a multiple of 256" in header
-    for n in th.SIZES:
+    for n in SIZES:
         got = ws(n)
         # include/dbhip_scan_by_key.h: 2048 + n / 64; and it holds 64 bytes per 4096-row segment behind the header
         assert got % 256 == 0 and 256 <= got <= 2048 + n // 64, (n, got)
@@ -131,10 +99,6 @@ def test_ops_has_the_plan_and_refuses_host_tensors_wrong_types_and_slices():
     for name in ("ScanByKey", "scan_by_key", "window_sorted", "check_scan_by_key", "SCAN_BY_KEY_CHUNK_ROWS",
                  "SCAN_BY_KEY_SEGMENT_ROWS"):
         assert hasattr(ops, name), name
-    header = (ROOT / "include" / HEADER).read_text()
-    assert f"#define DBHIP_SCAN_BY_KEY_CHUNK_ROWS {ops.SCAN_BY_KEY_CHUNK_ROWS} " in header
-    assert f"#define DBHIP_SCAN_BY_KEY_SEGMENT_ROWS {ops.SCAN_BY_KEY_SEGMENT_ROWS} " in header
-    assert ops.SCAN_BY_KEY_CHUNK_ROWS == 8 * ops.SCAN_BY_KEY_SEGMENT_ROWS
     t = torch.zeros(16, dtype=torch.int32)
     for call in (lambda: ops.scan_by_key(t, t), lambda: ops.window_sorted(t, t),
                  lambda: ops.check_scan_by_key(t, t, t, t, t.long(), t, t)):
@@ -151,28 +115,3 @@ def test_ops_has_the_plan_and_refuses_host_tensors_wrong_types_and_slices():
     plan = ops.ScanByKey(16, device="cpu")  # the plan itself is plain memory; launch refuses what it is given
     with pytest.raises(ValueError, match="on the GPU"):
         plan.launch(t, t)
-
-
-def test_window_cli_lists_the_default_set_plus_its_dwarf():
-    if not (LIB / "dwarf_bench_window").exists():
-        from dwarf_bench_amd import build
-        build.build_hip()
-        build.build_host()
-    assert th._names(LIB / "dwarf_bench_window") == sorted(DEFAULT + ["WindowSortedHip"])
-
-
-def test_every_stream_working_entry_point_has_a_capture_test():
-    """what a COVERAGE row in tests/graph_testlib.py says for the entry points of dbhip.h"""
-    pytest.importorskip("torch")
-    from tests import graph_testlib as gl
-    from tests import test_gpu_scan_by_key_graph as tg
-    assert sorted(tg.COVERAGE) == th._declared(HEADER)
-    assert sorted(name for name, test in tg.COVERAGE.items() if test == gl.NO_STREAM_WORK) == [
-        "dbhip_check_scan_by_key_workspace_bytes", "dbhip_scan_by_key_workspace_bytes"]
-    source = (ROOT / "tests" / "test_gpu_scan_by_key_graph.py").read_text()
-    for name, test in tg.COVERAGE.items():
-        if test == gl.NO_STREAM_WORK:
-            continue
-        assert callable(getattr(tg, test, None)) and test.startswith("test_"), (name, test)
-        body = source.split(f"def {test}(")[1].split("\ndef ")[0]
-        assert "capture" in body or "run_family" in body, (name, test)

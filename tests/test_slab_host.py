@@ -1,6 +1,6 @@
 """The slab table without a GPU: the Python model against the reference tests' assertions, the exact bucket hash the
 kernel computes without a 64-bit division, the C ABI's workspace query and argument checks (host-side, before any HIP
-call), the compiled code object of csrc/slab.hip, and the slab CLI's dwarf list."""
+call), and the compiled code object of csrc/slab.hip."""
 import json
 import random
 import re
@@ -11,12 +11,11 @@ import numpy as np
 import pytest
 
 from dwarf_bench_amd import _capi
+from tests.capi_testlib import EINVAL, EWORKSPACE
 from tests.slab_model import (EMPTY_KEY, NONE, SlabModel, barrett_constant, barrett_rem, barrett_rem_np, device_hash,
                               slab_hash)
 
 ROOT = Path(__file__).resolve().parents[1]
-LIB = ROOT / "dwarf_bench_amd" / "_lib"
-EINVAL, EWORKSPACE = -1, -2
 REFERENCE_HASHERS = [(242792921, 653019598, 2147483647), (32, 48, 1031), (13, 24, 343)]
 M32 = (1 << 32) - 1
 
@@ -188,25 +187,6 @@ def test_code_object_has_no_scratch_and_no_64_bit_division(tmp_path):
     assert len(meta) == 4 and all(size == "0" for _, size in meta), meta
     text = "".join(bodies.values())
     assert "scratch_" not in text and "__udivdi3" not in text and "__umoddi3" not in text
-
-
-def _names(exe):
-    r = subprocess.run([str(exe), "list"], capture_output=True, text=True, timeout=60)
-    assert r.returncode == 0
-    return [l.strip() for l in r.stdout.splitlines() if l.startswith("\t")]
-
-
-def test_slab_cli_lists_the_default_set_plus_the_slab_dwarfs():
-    exe, slab = LIB / "dwarf_bench", LIB / "dwarf_bench_slab"
-    if not exe.exists() or not slab.exists():
-        from dwarf_bench_amd import build
-        build.build_hip()
-        build.build_host()
-    default, with_slab = _names(exe), _names(slab)
-    assert not any(n.startswith("Slab") for n in default)
-    assert set(default) <= set(with_slab) and len(with_slab) == len(default) + 3
-    assert sorted(set(with_slab) - set(default)) == ["SlabHashBuildHip", "SlabJoinHip", "SlabProbeHip"]
-    assert not any(n.startswith("Slab") for n in _names(LIB / "dwarf_bench_experimental"))
 
 
 def test_slab_buckets_is_the_reference_sizing_without_its_zero():

@@ -1,6 +1,5 @@
-"""The key-value radix sort / argsort (dbhip_radix_sort_pairs_*) without a GPU: the C ABI declared, bound and exported,
-the workspace query, the host-side argument checks (all before any HIP call), the compiled code object of the pairs
-kernels and the dwarf list of the sort-pairs CLI."""
+"""The key-value radix sort / argsort (dbhip_radix_sort_pairs_*) without a GPU: the workspace query, the host-side
+argument checks (all before any HIP call) and the compiled code object of the pairs kernels."""
 import re
 import subprocess
 from pathlib import Path
@@ -8,21 +7,9 @@ from pathlib import Path
 import pytest
 
 from dwarf_bench_amd import _capi
+from tests.capi_testlib import EINVAL, EWORKSPACE
 
 ROOT = Path(__file__).resolve().parents[1]
-LIB = ROOT / "dwarf_bench_amd" / "_lib"
-EINVAL, EWORKSPACE = -1, -2
-NEW = ("dbhip_radix_sort_pairs_workspace_bytes", "dbhip_radix_sort_pairs_u32", "dbhip_radix_sort_pairs_i32",
-       "dbhip_check_sorted_pairs_u32")
-
-
-def test_entry_points_are_declared_bound_and_exported():
-    header = re.sub(r"/\*.*?\*/", "", (ROOT / "include" / "dbhip.h").read_text(), flags=re.S)
-    lib = _capi.lib()
-    for name in NEW:
-        assert re.search(rf"\b{name}\s*\(", header), name
-        assert name in _capi.SIGNATURES, name
-        assert hasattr(lib, name), name
 
 
 def test_workspace_query():
@@ -107,22 +94,3 @@ def test_pairs_kernels_use_no_scratch_and_keep_the_occupancy(tmp_path):
         assert scratch == 0 and vgprs <= 128, (name, scratch, vgprs)
     bodies = re.findall(r"^(_ZN\S*rsp_\w+):.*?\n(.*?)s_endpgm", asm, flags=re.S | re.M)
     assert len(bodies) == 9 and "scratch_" not in "".join(b for _, b in bodies)
-
-
-def _names(exe):
-    r = subprocess.run([str(exe), "list"], capture_output=True, text=True, timeout=60)
-    assert r.returncode == 0
-    return [l.strip() for l in r.stdout.splitlines() if l.startswith("\t")]
-
-
-def test_sort_pairs_cli_lists_the_default_set_plus_its_dwarf():
-    exe, pairs = LIB / "dwarf_bench", LIB / "dwarf_bench_sort_pairs"
-    if not exe.exists() or not pairs.exists():
-        from dwarf_bench_amd import build
-        build.build_hip()
-        build.build_host()
-    default, with_pairs = _names(exe), _names(pairs)
-    assert "RadixPairsHip" in with_pairs and set(default) <= set(with_pairs)
-    assert sorted(set(with_pairs) - set(default)) == ["RadixPairsHip"] and len(with_pairs) == len(default) + 1
-    for other in ("dwarf_bench", "dwarf_bench_experimental", "dwarf_bench_slab", "dwarf_bench_groupby_hash"):
-        assert "RadixPairsHip" not in _names(LIB / other)

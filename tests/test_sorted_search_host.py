@@ -1,51 +1,23 @@
-"""The sorted search (include/dbhip_sorted_search.h) without a GPU: the fifth header declared, bound and exported, the
-workspace query against the model and the bound the header states, the host-side argument checks (all before any HIP call, in
-the header's order), the tensor API's refusals, the dwarf list of the new CLI, no scratch in the kernels, and the capture test
-of every entry point that works on a stream."""
+"""The sorted search (include/dbhip_sorted_search.h) without a GPU: the workspace query against the model and the bound the
+header states, the host-side argument checks (all before any HIP call, in the header's order), the tensor API's refusals and no
+scratch in the kernels."""
 import re
 import subprocess
-from pathlib import Path
 
 import pytest
 
 from dwarf_bench_amd import _capi
 from tests import sorted_search_model as sm
-from tests import test_topk_host as th
-from tests.test_join_pairs_host import DEFAULT
+from tests.capi_testlib import EINVAL, EWORKSPACE, INCLUDE, OK, ROOT, SIZES
 from tests.test_sorted_search_model import BOUNDARIES
 
-ROOT = Path(__file__).resolve().parents[1]
-LIB = ROOT / "dwarf_bench_amd" / "_lib"
-EINVAL, EWORKSPACE, ENODEVICE, OK = -1, -2, -3, 0
 HEADER = "dbhip_sorted_search.h"
-NAMES = ["dbhip_check_sorted_search_u32", "dbhip_check_sorted_search_workspace_bytes", "dbhip_sorted_index_build_u32",
-         "dbhip_sorted_index_workspace_bytes", "dbhip_sorted_search_u32"]
-
-
-def test_entry_points_are_declared_bound_and_exported():
-    names = th._declared(HEADER)
-    assert names == NAMES == sorted(_capi.SORTED_SEARCH_SIGNATURES)
-    lib = _capi.lib()
-    for name in names:
-        fn = getattr(lib, name)
-        res, args = _capi.SORTED_SEARCH_SIGNATURES[name]
-        assert list(fn.argtypes) == args and fn.restype == res, name
-
-
-def test_the_older_headers_and_their_tables_are_what_they_were():
-    older = {"dbhip.h": _capi.SIGNATURES, "dbhip_topk.h": _capi.TOPK_SIGNATURES,
-             "dbhip_reduce_by_key.h": _capi.REDUCE_BY_KEY_SIGNATURES, "dbhip_scan_by_key.h": _capi.SCAN_BY_KEY_SIGNATURES}
-    for header, table in older.items():
-        assert th._declared(header) == sorted(table), header
-        assert not set(table) & set(_capi.SORTED_SEARCH_SIGNATURES)
-        assert not any("sorted_search" in name or "sorted_index" in name for name in table)
-    assert [len(t) for t in older.values()] == [73, 4, 4, 4]
 
 
 def test_workspace_query_is_the_model_and_keeps_its_bound():
     lib = _capi.lib()
     ws, cws = lib.dbhip_sorted_index_workspace_bytes, lib.dbhip_check_sorted_search_workspace_bytes
-    header = (ROOT / "include" / HEADER).read_text()
+    header = (INCLUDE / HEADER).read_text()
     assert "dbhip_sorted_index_workspace_bytes(m, top_entries) <= 1536 + m / 15" in header
     for top in (0,) + sm.TOPS:
         for m in BOUNDARIES + (4095, 4096, 4097, 262145, 100003):
@@ -56,7 +28,7 @@ def test_workspace_query_is_the_model_and_keeps_its_bound():
         assert ws(m, 0) == 0 and ws(m, 64) == 0, m
     for bad in (1, 2, 32, 63, 65, 96, 1000, 16383, 16385, 32768, 1 << 31):
         assert ws(1000, bad) == 0, bad
-    for n in th.SIZES:
+    for n in SIZES:
         assert cws(n) == 256
     assert cws(1 << 32) == 0 and cws(1 << 40) == 0
 
@@ -145,10 +117,6 @@ def test_ops_has_the_plan_and_refuses_host_tensors_wrong_types_and_slices():
     for name in ("SortedSearch", "sorted_search", "check_sorted_search", "range_join", "SORTED_SEARCH_FANOUT",
                  "SORTED_SEARCH_TOP"):
         assert hasattr(ops, name), name
-    header = (ROOT / "include" / HEADER).read_text()
-    assert f"#define DBHIP_SORTED_SEARCH_FANOUT {ops.SORTED_SEARCH_FANOUT} " in header
-    assert f"#define DBHIP_SORTED_SEARCH_TOP {ops.SORTED_SEARCH_TOP} " in header
-    assert (ops.SORTED_SEARCH_FANOUT, ops.SORTED_SEARCH_TOP) == (sm.FANOUT, sm.TOP)
     t = torch.zeros(16, dtype=torch.int32)
     for call in (lambda: ops.sorted_search(t, t), lambda: ops.range_join(t, t, t),
                  lambda: ops.check_sorted_search(t, t, t, t, t), lambda: ops.sorted_search(t.float(), t)):
@@ -169,16 +137,6 @@ def test_ops_has_the_plan_and_refuses_host_tensors_wrong_types_and_slices():
     assert "unique" in doc and "stable" in doc
 
 
-def test_range_join_cli_lists_the_default_set_plus_its_dwarf():
-    if not (LIB / "dwarf_bench_range_join").exists() or not (LIB / "dwarf_bench").exists():
-        from dwarf_bench_amd import build
-        build.build_hip()
-        build.build_host()
-    assert th._names(LIB / "dwarf_bench_range_join") == sorted(DEFAULT + ["RangeJoinHip"])
-    assert "RangeJoinHip" not in th._names(LIB / "dwarf_bench")
-    assert th._names(LIB / "dwarf_bench") == sorted(DEFAULT)
-
-
 def test_code_object_has_no_scratch(tmp_path):
     subprocess.run(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fno-gpu-rdc",
                     "--save-temps", "-c", str(ROOT / "dwarf_bench_amd" / "csrc" / "sorted_search.hip"), "-o",
@@ -191,20 +149,3 @@ def test_code_object_has_no_scratch(tmp_path):
     assert "scratch_" not in "".join(bodies.values())
     lds = re.findall(r"\.group_segment_fixed_size:\s+(\d+)", asm)
     assert sorted(int(v) for v in lds) == [0, 0, 0, 65536, 65536, 65536]  # the top level: two workgroups a compute unit
-
-
-def test_every_stream_working_entry_point_has_a_capture_test():
-    """what a COVERAGE row in tests/graph_testlib.py says for the entry points of dbhip.h"""
-    pytest.importorskip("torch")
-    from tests import graph_testlib as gl
-    from tests import test_gpu_sorted_search_graph as tg
-    assert sorted(tg.COVERAGE) == th._declared(HEADER)
-    assert sorted(name for name, test in tg.COVERAGE.items() if test == gl.NO_STREAM_WORK) == [
-        "dbhip_check_sorted_search_workspace_bytes", "dbhip_sorted_index_workspace_bytes"]
-    source = (ROOT / "tests" / "test_gpu_sorted_search_graph.py").read_text()
-    for name, test in tg.COVERAGE.items():
-        if test == gl.NO_STREAM_WORK:
-            continue
-        assert callable(getattr(tg, test, None)) and test.startswith("test_"), (name, test)
-        body = source.split(f"def {test}(")[1].split("\ndef ")[0]
-        assert "capture" in body or "run_family" in body, (name, test)
