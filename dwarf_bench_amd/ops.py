@@ -1,8 +1,10 @@
 """Tensor-level front door to the gfx950 dwarf kernels.
 
 PyTorch is plumbing here (device memory, the current HIP stream, torch.distributed); every op is one or
-more calls through the C ABI of include/dbhip.h into libdbhip.so.  Nothing in this module computes on
-the host or falls back to torch ops: without the built library the first call raises.
+more calls through a C ABI into hand-written gfx950 kernels: that of include/dbhip*.h into libdbhip.so, and for the
+selection vectors (SelectRows, select_range, semi_join) that of host/select_rows.hpp into libdbench.so, where entry
+points live until they are promoted to include/ (INTEGRATION.md).  Nothing in this module computes on the host or
+falls back to torch ops: without the built libraries the first call raises.
 """
 from __future__ import annotations
 
@@ -10,7 +12,7 @@ import ctypes as C
 
 import torch
 
-from . import _capi
+from . import _capi, select_native
 
 DEV_OK, DEV_SPIN_TIMEOUT, DEV_KEY_RANGE, DEV_TABLE_FULL, DEV_RANK_ORDER = 0, 1, 2, 4, 8
 
@@ -123,6 +125,104 @@ class CopyIfLt:
 def copy_if_lt(src: torch.Tensor, filter_value: int, dense: bool = False) -> torch.Tensor:
     plan = CopyIfLt(src.numel(), src.device)
     plan.launch(src, filter_value, dense=dense)
+    return plan.result()
+
+
+# ---------------------------------------------------------------------------------------------
+# selection vectors: range filters that return row ids (host/select_rows.hpp, libdbench.so)
+# ---------------------------------------------------------------------------------------------
+def _bounds(lo: int, hi: int, signed: bool) -> tuple[int, int]:
+    """Python ints in the range of the chosen signedness -> their 32-bit patterns"""
+    least, most = (-(1 << 31), (1 << 31) - 1) if signed else (0, (1 << 32) - 1)
+    for name, v in (("lo", lo), ("hi", hi)):
+        if isinstance(v, bool) or not isinstance(v, int) or not least <= v <= most:
+            raise ValueError(f"{name}: expected an int in [{least}, {most}] ({'int32' if signed else 'uint32'}), got {v!r}")
+    return lo & 0xFFFFFFFF, hi & 0xFFFFFFFF
+
+
+class SelectRows:
+    """Reusable plan for row ids under range predicates, up to `capacity` candidates per call: owns the workspace, two
+    row-id buffers (ping-pong: a call never writes the buffer it reads, and the view result() returned last stays intact
+    through the next call) and their device counts.  launch() filters all rows of a column or a given row-id list;
+    refine() filters the plan's own last output on another column with its count still on the device, so a conjunction
+    is a chain of launches without a read-back.  Row ids come out in candidate order."""
+
+    def __init__(self, capacity: int, device="cuda"):
+        self.capacity = int(capacity)
+        self.ws_bytes = select_native.workspace_bytes(self.capacity)
+        if self.ws_bytes == 0:
+            raise ValueError("capacity: at most 2^32 - 1 candidates")
+        self.ws = _ws(self.ws_bytes, device)
+        self.rows = [torch.empty(max(self.capacity, 1), dtype=torch.int32, device=device) for _ in range(2)]
+        self.counts = torch.zeros(2, dtype=torch.int64, device=device)
+        self._last = None  # index of the buffer the last launch wrote
+
+    def launch(self, col: torch.Tensor, lo: int, hi: int, rows: torch.Tensor | None = None,
+               count: torch.Tensor | None = None, signed: bool = False, negate: bool = False) -> None:
+        """Asynchronous on the current stream; nothing is read back.  rows: an int32 row-id list (None: all rows of
+        col); count: a device int64 of one element, the number of entries of `rows` that count (None: all of them)."""
+        _need(col, torch.int32, "col")
+        lo, hi = _bounds(lo, hi, signed)
+        if rows is not None:
+            _need(rows, torch.int32, "rows")
+        elif count is not None:
+            raise ValueError("count: given without rows")
+        if count is not None and (not count.is_cuda or count.dtype != torch.int64 or count.numel() != 1):
+            raise ValueError("count: expected one int64 on the GPU")
+        candidates = col.numel() if rows is None else rows.numel()
+        if candidates > self.capacity:
+            raise ValueError(f"{candidates} candidates, the plan holds {self.capacity}")
+        into = 0 if self._last is None else 1 - self._last
+        if rows is not None and rows.untyped_storage().data_ptr() == self.rows[into].untyped_storage().data_ptr():
+            into = 1 - into  # the list is a view of that buffer: write the other one
+        col_ptr, col_n, list_ptr, count_ptr = col.data_ptr() if col.numel() else None, col.numel(), None, None
+        if rows is not None and rows.numel():
+            list_ptr, count_ptr = rows.data_ptr(), count.data_ptr() if count is not None else None
+        elif rows is not None:  # an empty list has no address: the call over no rows at all
+            col_ptr, col_n = None, 0
+        flags = (select_native.SIGNED if signed else 0) | (select_native.NEGATE if negate else 0)
+        _capi.check(select_native.select_range(
+            col_ptr, col_n, list_ptr, count_ptr, rows.numel() if list_ptr else 0, lo, hi, flags,
+            self.rows[into].data_ptr(), self.counts[into:].data_ptr(), self.ws.data_ptr(), self.ws_bytes, _stream()),
+            "select_range_u32")
+        self._last = into
+
+    def refine(self, col: torch.Tensor, lo: int, hi: int, signed: bool = False, negate: bool = False) -> None:
+        """the rows of the last launch that also pass this predicate on `col`: its output list and its device count are
+        the candidates, nothing is read back in between"""
+        if self._last is None:
+            raise ValueError("refine: nothing was launched on this plan")
+        at = self._last
+        self.launch(col, lo, hi, rows=self.rows[at][: self.capacity], count=self.counts[at: at + 1], signed=signed,
+                    negate=negate)
+
+    def status(self) -> int:
+        return workspace_status(self.ws)
+
+    def count(self) -> int:
+        return int(self.counts[self._last].item())
+
+    def result(self, strict: bool = True) -> torch.Tensor:
+        """the int32 row ids of the last launch (a view of the plan's buffer; synchronises).  strict: a row id outside
+        the column among the candidates (DEV_KEY_RANGE) raises; otherwise such candidates are just dropped."""
+        if self._last is None:
+            raise ValueError("result: nothing was launched on this plan")
+        if strict:
+            _check_status(self.ws, "select_range_u32")
+        return self.rows[self._last][: self.count()]
+
+
+def select_range(col: torch.Tensor, lo: int, hi: int, rows: torch.Tensor | None = None, signed: bool = False,
+                 negate: bool = False) -> torch.Tensor:
+    """Row ids r (ascending, or in the order of `rows`) with lo <= col[r] <= hi — outside [lo, hi] with negate —
+    compared as uint32, or as int32 with signed.  lo > hi is the empty interval.  rows: candidates, a row id as often
+    as the list holds it; a row id >= col.numel() raises."""
+    _bounds(lo, hi, signed)
+    _need(col, torch.int32, "col")
+    if rows is not None:
+        _need(rows, torch.int32, "rows")
+    plan = SelectRows(col.numel() if rows is None else rows.numel(), col.device)
+    plan.launch(col, lo, hi, rows=rows, signed=signed, negate=negate)
     return plan.result()
 
 
@@ -825,6 +925,18 @@ def hash_join(build_keys: torch.Tensor, probe_keys: torch.Tensor):
     plan.build(build_keys)
     plan.probe(probe_keys)
     return plan.result()
+
+
+def semi_join(build_keys: torch.Tensor, probe_keys: torch.Tensor, anti: bool = False) -> torch.Tensor:
+    """EXISTS / IN: the ascending probe row ids with at least one build row of the same key; anti: NOT EXISTS, the
+    probe rows with none.  HashJoin.build + probe, then the rows whose match count lies in [1, 0xFFFFFFFF] (outside it
+    for anti).  The join's key contract holds: 0xFFFFFFFF is the empty-slot sentinel, a build row carrying it is dropped
+    and flagged (DEV_KEY_RANGE: this call raises), a probe row carrying it has no match."""
+    plan = HashJoin(build_keys.numel(), probe_keys.numel(), build_keys.device)
+    plan.build(build_keys)
+    plan.probe(probe_keys)
+    _, cnt, _ = plan.result()
+    return select_range(cnt, 1, 0xFFFFFFFF, negate=anti)
 
 
 class JoinPairs:

@@ -50,6 +50,13 @@ the contract numbers come from bench.py.
   range-join [lg] the band join at 2^lg rows a side (default 24), keys in [1, n], hi = lo + 2: copy + argsort + index + search +
                   pairs (ops.range_join's launches, capacity given) against torch.sort(stable) + two searchsorted + join-pairs'
                   torch expansion, same protocol; both pair columns compared with torch's
+  selection [lg]  the selection vectors (ops.SelectRows: dbench_select_range_u32 of host/select_rows.hpp) against torch on the same
+                  int32 columns, same protocol and floor as sorted-search.  Dense: 2^22, 2^24, 2^26 rows (or 2^lg alone) of uniform
+                  values at selectivities 0, 0.01, 1, 10, 50, 100 % against torch.nonzero((x >= lo) & (x <= hi)), beside the
+                  time of 4n + n/4 + 4m bytes at 8 TB/s; lists of 2^20 and 2^24 rows out of 2^26, sorted and shuffled, against
+                  rows[(col[rows] >= lo) & (col[rows] <= hi)]; the three-predicate chain at 2^26 rows against the torch
+                  conjunction; the semi join 2^24 x 2^24 against torch.isin + nonzero.  Both legs run until the row ids and
+                  their number are usable on the host; every result compared with torch's (SEL_PARTS picks parts)
   launch-join-pairs [lg]  five expansions at 2^lg rows a side (default 24) and five of the one-key shape, nothing else
                   (`rocprofv3 --kernel-trace --stats`)
   launch-sort-pairs [lg]  five 8-bit argsorts of 2^lg full-range keys (default 24) and nothing else (`rocprofv3 --kernel-trace`)
@@ -606,6 +613,114 @@ def range_join(lg):
     print(f"{TAG:10s} range-join n=2^{lg or 24} pairs={total:11d}  {cols}  floor {'holds' if floor else 'MISSED'}  "
           f"{'ok' if ok else 'WRONG'}   " + " ".join(f"{leg}:" + "/".join(f"{t:.1f}" for t in ts) for leg, ts in legs.items()),
           flush=True)
+
+
+def _selection_row(name, mine, vendor, result, reps, floor_applies=True, model_us=None):
+    """one shape of `selection`: alternating legs, the floor, and this code's row ids against torch's"""
+    legs = {"select": [], "torch": []}
+    for _ in range(reps):  # alternating
+        legs["select"].append(median(times(mine, 5)))
+        legs["torch"].append(median(times(vendor, 5)))
+    mine()
+    got, want = result(), vendor()
+    ok = got.numel() == want.numel() and torch.equal(u64(got), want.to(torch.int64))
+    floor = max(legs["select"]) <= min(legs["torch"])
+    cols = "  ".join(f"{leg} {min(ts):9.1f} .. {max(ts):9.1f} us" for leg, ts in legs.items())
+    model = "" if model_us is None else f"  bytes at 8 TB/s {model_us:7.1f} us = {100 * model_us / median(sorted(legs['select'])):3.0f} %"
+    verdict = ("floor " + ("holds" if floor else "MISSED")) if floor_applies else "no floor (below 2^20)"
+    print(f"{TAG:10s} {name:58s} rows={got.numel():10d}  {cols}{model}  {verdict}  {'ok' if ok else 'WRONG'}   "
+          + " ".join(f"{leg}:" + "/".join(f"{t:.1f}" for t in ts) for leg, ts in legs.items()), flush=True)
+
+
+def selection(lg):
+    """dense sizes 2^22, 2^24, 2^26 (or 2^lg alone; below 20 no floor applies), then lists, the chain and the semi join
+    (SEL_PARTS=dense,list,chain,semi picks parts).  Both legs run through the point where the row ids and their number are
+    usable on the host: this code reads its device count, torch's nonzero synchronises by itself."""
+    reps = int(os.environ.get("REPS", "5"))
+    parts = os.environ.get("SEL_PARTS", "dense,list,chain,semi").split(",")
+    shares = (0.0, 0.0001, 0.01, 0.1, 0.5, 1.0)
+
+    def hi_of(share):  # lo = 1 so that share 0 is the empty interval [1, 0]; values below 2^31: torch compares int32
+        return min(int(share * 2**31), 2**31 - 1)
+
+    if "dense" in parts:
+        for lgn in ([lg] if lg else [22, 24, 26]):
+            n = 1 << lgn
+            col = ops.gen_uniform_u32(n, 42, 0, 2**31 - 1)
+            plan = ops.SelectRows(n)
+            for share in shares:
+                hi = hi_of(share)
+
+                def mine():
+                    plan.launch(col, 1, hi)
+                    return plan.count()
+
+                def vendor():
+                    return torch.nonzero((col >= 1) & (col <= hi)).flatten()
+
+                m = mine()
+                _selection_row(f"dense n=2^{lgn} share {100 * share:7.2f} %", mine, vendor, plan.result, reps,
+                               floor_applies=lgn >= 20, model_us=(4 * n + n / 4 + 4 * m) / 8e12 * 1e6)
+            del col, plan
+    n = 1 << 26
+    if "list" in parts:
+        col = ops.gen_uniform_u32(n, 42, 0, 2**31 - 1)
+        for lgm in (20, 24):
+            m = 1 << lgm
+            shuffled = torch.randperm(n, device="cuda")[:m].to(torch.int32)
+            plan = ops.SelectRows(m)
+            for order, rows in (("sorted", torch.sort(shuffled).values), ("shuffled", shuffled)):
+                rows64 = rows.to(torch.int64)
+                for share in (0.01, 0.5):
+                    hi = hi_of(share)
+
+                    def mine():
+                        plan.launch(col, 1, hi, rows=rows)
+                        return plan.count()
+
+                    def vendor():
+                        v = col[rows64]
+                        return rows[(v >= 1) & (v <= hi)]
+
+                    _selection_row(f"list m=2^{lgm} of 2^26 {order:8s} share {100 * share:6.2f} %", mine, vendor, plan.result,
+                                   reps)
+            del plan
+        del col
+    if "chain" in parts:
+        cols = [ops.gen_uniform_u32(n, 50 + i, 0, 2**31 - 1) for i in range(3)]
+        his = [hi_of(0.5), hi_of(0.1), hi_of(0.5)]
+        plan = ops.SelectRows(n)
+
+        def mine():
+            plan.launch(cols[0], 1, his[0])
+            plan.refine(cols[1], 1, his[1])
+            plan.refine(cols[2], 1, his[2])
+            return plan.count()
+
+        def vendor():
+            keep = None
+            for c, hi in zip(cols, his):
+                k = (c >= 1) & (c <= hi)
+                keep = k if keep is None else keep & k
+            return torch.nonzero(keep).flatten()
+
+        _selection_row("chain n=2^26 three predicates (50 %, 10 %, 50 %)", mine, vendor, plan.result, reps)
+        del cols, plan
+    if "semi" in parts:
+        m = 1 << 24
+        build, probe = ops.gen_uniform_u32(m, 42, 1, m), ops.gen_uniform_u32(m, 43, 1, m)
+        join, plan = ops.HashJoin(m, m), ops.SelectRows(m)
+
+        def mine():
+            join.build(build)
+            join.probe(probe)
+            plan.launch(join.cnt, 1, 0xFFFFFFFF)
+            return plan.count()
+
+        def vendor():
+            return torch.nonzero(torch.isin(probe, build)).flatten()
+
+        _selection_row("semi join 2^24 x 2^24, keys in [1, 2^24]", mine, vendor, plan.result, reps)
 
 
 def launch_sort_pairs(lg):
@@ -1310,7 +1425,8 @@ MODES = {"radix": radix, "ramp": ramp, "radix-idle": radix_idle, "radix-stream":
          "groupby-hash": groupby_hash, "sort-pairs": sort_pairs, "launch-sort-pairs": launch_sort_pairs,
          "join-pairs": join_pairs, "launch-join-pairs": launch_join_pairs, "topk": topk, "launch-topk": launch_topk,
          "groupby-sorted": groupby_sorted, "launch-groupby-sorted": launch_groupby_sorted,
-         "window": window, "launch-window": launch_window, "sorted-search": sorted_search, "range-join": range_join}
+         "window": window, "launch-window": launch_window, "sorted-search": sorted_search, "range-join": range_join,
+         "selection": selection}
 
 if __name__ == "__main__":
     if len(sys.argv) < 2 or sys.argv[1] not in MODES:
