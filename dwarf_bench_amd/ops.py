@@ -3,8 +3,10 @@
 PyTorch is plumbing here (device memory, the current HIP stream, torch.distributed); every op is one or
 more calls through a C ABI into hand-written gfx950 kernels: that of include/dbhip*.h into libdbhip.so, and for the
 selection vectors (SelectRows, select_range, semi_join) that of host/select_rows.hpp into libdbench.so, where entry
-points live until they are promoted to include/ (INTEGRATION.md).  Nothing in this module computes on the host or
-falls back to torch ops: without the built libraries the first call raises.
+points live until they are promoted to include/ (INTEGRATION.md); beside it, for the sorted merge and the set
+operations on row-id lists (MergeSorted, merge_sorted, RowSets, union_rows, intersect_rows, difference_rows, select_any),
+that of host/merge_sorted.hpp.  Nothing in this module computes on the host or falls back to torch ops: without the
+built libraries the first call raises.
 """
 from __future__ import annotations
 
@@ -12,7 +14,7 @@ import ctypes as C
 
 import torch
 
-from . import _capi, select_native
+from . import _capi, merge_native, select_native
 
 DEV_OK, DEV_SPIN_TIMEOUT, DEV_KEY_RANGE, DEV_TABLE_FULL, DEV_RANK_ORDER = 0, 1, 2, 4, 8
 
@@ -202,6 +204,14 @@ class SelectRows:
     def count(self) -> int:
         return int(self.counts[self._last].item())
 
+    def output(self) -> tuple[torch.Tensor, torch.Tensor]:
+        """(rows[:capacity], its device count as a one-element int64 view) of the last launch, without synchronising:
+        what another plan (RowSets, refine's own launch) takes as a list and its count inside one captured graph"""
+        if self._last is None:
+            raise ValueError("output: nothing was launched on this plan")
+        at = self._last
+        return self.rows[at][: self.capacity], self.counts[at: at + 1]
+
     def result(self, strict: bool = True) -> torch.Tensor:
         """the int32 row ids of the last launch (a view of the plan's buffer; synchronises).  strict: a row id outside
         the column among the candidates (DEV_KEY_RANGE) raises; otherwise such candidates are just dropped."""
@@ -224,6 +234,189 @@ def select_range(col: torch.Tensor, lo: int, hi: int, rows: torch.Tensor | None 
     plan = SelectRows(col.numel() if rows is None else rows.numel(), col.device)
     plan.launch(col, lo, hi, rows=rows, signed=signed, negate=negate)
     return plan.result()
+
+
+# ---------------------------------------------------------------------------------------------
+# sorted merge and set operations on row-id lists: merge path (host/merge_sorted.hpp, libdbench.so)
+# ---------------------------------------------------------------------------------------------
+def _need_count(count: torch.Tensor | None, name: str) -> None:
+    if count is not None and (not count.is_cuda or count.dtype != torch.int64 or count.numel() != 1):
+        raise ValueError(f"{name}: expected one int64 on the GPU")
+
+
+def _column(t: torch.Tensor | None, count: torch.Tensor | None = None):
+    """-> (address or None, entries, count's address or None) as the C entry points take a column: an empty tensor has
+    no address, and then no count either"""
+    if t is None or t.numel() == 0:
+        return None, 0, None
+    return t.data_ptr(), t.numel(), count.data_ptr() if count is not None else None
+
+
+class MergeSorted:
+    """Reusable plan for the stable merge of two ascending int32 key columns (compared as uint32, or as int32 with
+    signed) of up to a_capacity and b_capacity rows: owns the workspace, the two output columns and the device count.
+    Among equal keys A's rows come before B's.  Values: none (keys only), two int32 columns carried with their keys, or
+    row_ids: the position in the concatenation, r for A's row r and a_keys.numel() + r for B's row r."""
+
+    def __init__(self, a_capacity: int, b_capacity: int, device="cuda"):
+        self.a_capacity, self.b_capacity = int(a_capacity), int(b_capacity)
+        self.ws_bytes = merge_native.workspace_bytes(self.a_capacity, self.b_capacity)
+        if self.ws_bytes == 0:
+            raise ValueError("capacity: at most 2^32 - 1 rows in all")
+        self.ws = _ws(self.ws_bytes, device)
+        rows = max(self.a_capacity + self.b_capacity, 1)
+        self.out_keys = torch.empty(rows, dtype=torch.int32, device=device)
+        self.out_vals = torch.empty(rows, dtype=torch.int32, device=device)
+        self.out_count = torch.zeros(1, dtype=torch.int64, device=device)
+        self._vals = None  # whether the last launch wrote out_vals
+
+    def launch(self, a_keys: torch.Tensor, b_keys: torch.Tensor, a_vals: torch.Tensor | None = None,
+               b_vals: torch.Tensor | None = None, a_count: torch.Tensor | None = None,
+               b_count: torch.Tensor | None = None, signed: bool = False, row_ids: bool = False) -> None:
+        """Asynchronous on the current stream; nothing is read back.  a_count, b_count: device int64 of one element, the
+        rows of that side that count (None: all of them; more than the column holds: all of them)."""
+        _need(a_keys, torch.int32, "a_keys")
+        _need(b_keys, torch.int32, "b_keys")
+        if (a_vals is None) != (b_vals is None):
+            raise ValueError("a_vals, b_vals: both or neither")
+        if row_ids and a_vals is not None:
+            raise ValueError("row_ids: given with value columns")
+        for vals, keys, name in ((a_vals, a_keys, "a_vals"), (b_vals, b_keys, "b_vals")):
+            if vals is not None:
+                _need(vals, torch.int32, name)
+                if vals.numel() != keys.numel():
+                    raise ValueError(f"{name}: {vals.numel()} values for {keys.numel()} keys")
+        _need_count(a_count, "a_count")
+        _need_count(b_count, "b_count")
+        if a_keys.numel() > self.a_capacity or b_keys.numel() > self.b_capacity:
+            raise ValueError(f"{a_keys.numel()} and {b_keys.numel()} rows, the plan holds {self.a_capacity} and "
+                             f"{self.b_capacity}")
+        pa, na, ca = _column(a_keys, a_count)
+        pb, nb, cb = _column(b_keys, b_count)
+        self._vals = row_ids or a_vals is not None
+        flags = (merge_native.SIGNED if signed else 0) | (merge_native.ROW_IDS if row_ids else 0)
+        _capi.check(merge_native.merge(
+            pa, _column(a_vals)[0], ca, na, pb, _column(b_vals)[0], cb, nb, flags, self.out_keys.data_ptr(),
+            self.out_vals.data_ptr() if self._vals else None, self.out_count.data_ptr(), self.ws.data_ptr(), self.ws_bytes,
+            _stream()), "merge_u32")
+
+    def status(self) -> int:
+        return workspace_status(self.ws)
+
+    def count(self) -> int:
+        return int(self.out_count.item())
+
+    def result(self):
+        """(keys, values or None) of the last launch: views of the plan's buffers; synchronises"""
+        if self._vals is None:
+            raise ValueError("result: nothing was launched on this plan")
+        _check_status(self.ws, "merge_u32")
+        m = self.count()
+        return self.out_keys[:m], (self.out_vals[:m] if self._vals else None)
+
+
+def merge_sorted(a_keys: torch.Tensor, b_keys: torch.Tensor, a_vals: torch.Tensor | None = None,
+                 b_vals: torch.Tensor | None = None, signed: bool = False, row_ids: bool = False):
+    """The stable merge of two ascending key columns -> (keys, values or None); see MergeSorted."""
+    _need(a_keys, torch.int32, "a_keys")
+    _need(b_keys, torch.int32, "b_keys")
+    plan = MergeSorted(a_keys.numel(), b_keys.numel(), a_keys.device)
+    plan.launch(a_keys, b_keys, a_vals, b_vals, signed=signed, row_ids=row_ids)
+    return plan.result()
+
+
+SET_OPS = {"union": merge_native.UNION, "intersect": merge_native.INTERSECT, "difference": merge_native.DIFFERENCE}
+
+
+class RowSets:
+    """Reusable plan for the union, intersection and difference (A minus B) of two STRICTLY ascending int32 row-id
+    lists (uint32 order: what SelectRows over all rows of a column returns) of up to a_capacity and b_capacity entries:
+    owns the workspace, the output list and its device count.  The lists' lengths may be device counts
+    (SelectRows.output()), so filters and set operations chain inside one captured graph without a read-back."""
+
+    def __init__(self, a_capacity: int, b_capacity: int, device="cuda"):
+        self.a_capacity, self.b_capacity = int(a_capacity), int(b_capacity)
+        self.ws_bytes = merge_native.workspace_bytes(self.a_capacity, self.b_capacity)
+        if self.ws_bytes == 0:
+            raise ValueError("capacity: at most 2^32 - 1 rows in all")
+        self.ws = _ws(self.ws_bytes, device)
+        self.rows = torch.empty(max(self.a_capacity + self.b_capacity, 1), dtype=torch.int32, device=device)
+        self.out_count = torch.zeros(1, dtype=torch.int64, device=device)
+        self._launched = False
+
+    def launch(self, op, a: torch.Tensor, b: torch.Tensor, a_count: torch.Tensor | None = None,
+               b_count: torch.Tensor | None = None) -> None:
+        """op: "union", "intersect", "difference" or the DBENCH_SETOP_* number.  Asynchronous on the current stream;
+        nothing is read back."""
+        if op not in SET_OPS and op not in SET_OPS.values():
+            raise ValueError(f"op: expected one of {sorted(SET_OPS)}, got {op!r}")
+        _need(a, torch.int32, "a")
+        _need(b, torch.int32, "b")
+        _need_count(a_count, "a_count")
+        _need_count(b_count, "b_count")
+        if a.numel() > self.a_capacity or b.numel() > self.b_capacity:
+            raise ValueError(f"{a.numel()} and {b.numel()} rows, the plan holds {self.a_capacity} and {self.b_capacity}")
+        pa, na, ca = _column(a, a_count)
+        pb, nb, cb = _column(b, b_count)
+        _capi.check(merge_native.setop(SET_OPS.get(op, op), pa, ca, na, pb, cb, nb, self.rows.data_ptr(),
+                                       self.out_count.data_ptr(), self.ws.data_ptr(), self.ws_bytes, _stream()),
+                    "setop_u32")
+        self._launched = True
+
+    def status(self) -> int:
+        return workspace_status(self.ws)
+
+    def count(self) -> int:
+        return int(self.out_count.item())
+
+    def result(self) -> torch.Tensor:
+        """the ascending int32 row ids of the last launch (a view of the plan's buffer; synchronises)"""
+        if not self._launched:
+            raise ValueError("result: nothing was launched on this plan")
+        _check_status(self.ws, "setop_u32")
+        return self.rows[: self.count()]
+
+
+def _set_rows(op: str, a: torch.Tensor, b: torch.Tensor) -> torch.Tensor:
+    _need(a, torch.int32, "a")
+    _need(b, torch.int32, "b")
+    plan = RowSets(a.numel(), b.numel(), a.device)
+    plan.launch(op, a, b)
+    return plan.result()
+
+
+def union_rows(a: torch.Tensor, b: torch.Tensor) -> torch.Tensor:
+    """The rows of either of two strictly ascending row-id lists, ascending, each once."""
+    return _set_rows("union", a, b)
+
+
+def intersect_rows(a: torch.Tensor, b: torch.Tensor) -> torch.Tensor:
+    """The rows of both of two strictly ascending row-id lists, ascending."""
+    return _set_rows("intersect", a, b)
+
+
+def difference_rows(a: torch.Tensor, b: torch.Tensor) -> torch.Tensor:
+    """The rows of the strictly ascending list a that the strictly ascending list b does not hold, ascending."""
+    return _set_rows("difference", a, b)
+
+
+def select_any(col_a: torch.Tensor, lo_a: int, hi_a: int, col_b: torch.Tensor, lo_b: int, hi_b: int,
+               signed: bool = False) -> torch.Tensor:
+    """Row ids r, ascending, with lo_a <= col_a[r] <= hi_a OR lo_b <= col_b[r] <= hi_b: two selections over all rows
+    and their union, the two lists' lengths staying on the device in between."""
+    _bounds(lo_a, hi_a, signed)
+    _bounds(lo_b, hi_b, signed)
+    if col_a.numel() != col_b.numel():  # one row space: the union is over row ids of the same table
+        raise ValueError(f"col_a and col_b: {col_a.numel()} and {col_b.numel()} rows, expected the same number")
+    _need(col_a, torch.int32, "col_a")
+    _need(col_b, torch.int32, "col_b")
+    first, second = SelectRows(col_a.numel(), col_a.device), SelectRows(col_b.numel(), col_b.device)
+    sets = RowSets(col_a.numel(), col_b.numel(), col_a.device)
+    first.launch(col_a, lo_a, hi_a, signed=signed)
+    second.launch(col_b, lo_b, hi_b, signed=signed)
+    (rows_a, count_a), (rows_b, count_b) = first.output(), second.output()
+    sets.launch("union", rows_a, rows_b, count_a, count_b)
+    return sets.result()
 
 
 # ---------------------------------------------------------------------------------------------

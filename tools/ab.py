@@ -57,6 +57,17 @@ the contract numbers come from bench.py.
                   rows[(col[rows] >= lo) & (col[rows] <= hi)]; the three-predicate chain at 2^26 rows against the torch
                   conjunction; the semi join 2^24 x 2^24 against torch.isin + nonzero.  Both legs run until the row ids and
                   their number are usable on the host; every result compared with torch's (SEL_PARTS picks parts)
+  merge [lg]      the merge-path entry points of host/merge_sorted.hpp (ops.MergeSorted, ops.RowSets, select + select + union),
+                  same protocol and floor as sorted-search (one process, profiler off, legs alternating, REPS (default 5)
+                  repetitions of a median of 5, this code's slowest repetition against the comparison's fastest).  Merge with
+                  row ids at 2^22, 2^24, 2^26 output rows (or 2^lg alone): na = nb uniform, all keys equal, A below B, nb = 2^10
+                  against a large A; the comparison is this library's RadixSortPairs argsort of the preloaded concatenation (the
+                  restoring copy runs in front of the timed span); beside it the keys-only and carried-value merges and the
+                  time of their bytes at 8 TB/s.  Set operations on two random strictly ascending lists of 2^20, 2^24, 2^26
+                  rows each against torch.unique(torch.cat), a[torch.isin(a, b, assume_unique=True)] and its negation, both legs
+                  run until the rows and their number are usable on the host.  select + select + union at 2^26 rows against
+                  torch.nonzero(ka | kb) at shares (1 %, 1 %) and (50 %, 50 %).  Every result compared with the comparison
+                  leg's (MERGE_PARTS=merge,sets,any picks parts)
   launch-join-pairs [lg]  five expansions at 2^lg rows a side (default 24) and five of the one-key shape, nothing else
                   (`rocprofv3 --kernel-trace --stats`)
   launch-sort-pairs [lg]  five 8-bit argsorts of 2^lg full-range keys (default 24) and nothing else (`rocprofv3 --kernel-trace`)
@@ -721,6 +732,131 @@ def selection(lg):
             return torch.nonzero(torch.isin(probe, build)).flatten()
 
         _selection_row("semi join 2^24 x 2^24, keys in [1, 2^24]", mine, vendor, plan.result, reps)
+
+
+def _times_after(prep, fn, k, warm=2):
+    """times(), with prep() run in front of every timed span and outside it"""
+    for _ in range(warm):
+        prep()
+        fn()
+    out = []
+    for _ in range(k):
+        prep()
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        fn()
+        b.record()
+        torch.cuda.synchronize()
+        out.append(a.elapsed_time(b) * 1e3)
+    return sorted(out)
+
+
+def _merge_row(name, legs, ok, floor_of=None, model_us=None, extra=""):
+    """one shape of `merge`: the legs' ranges over the repetitions, the floor of floor_of = (mine, comparison)"""
+    cols = "  ".join(f"{leg} {min(ts):9.1f} .. {max(ts):9.1f} us" for leg, ts in legs.items())
+    verdict = ""
+    if floor_of:
+        mine, other = (legs[x] for x in floor_of)
+        verdict = f"  floor {'holds' if max(mine) <= min(other) else 'MISSED'}  x{median(sorted(other)) / median(sorted(mine)):5.2f}"
+        if model_us is not None:
+            verdict += f"  bytes at 8 TB/s {model_us:7.1f} us = {100 * model_us / median(sorted(mine)):3.0f} %"
+    print(f"{TAG:10s} {name:52s} {cols}{verdict}  {'ok' if ok else 'WRONG'}{extra}   "
+          + " ".join(f"{leg}:" + "/".join(f"{t:.1f}" for t in ts) for leg, ts in legs.items()), flush=True)
+
+
+def merge(lg):
+    """MERGE_PARTS=merge,sets,any picks parts; sizes below 2^20 are not measured"""
+    reps = int(os.environ.get("REPS", "5"))
+    parts = os.environ.get("MERGE_PARTS", "merge,sets,any").split(",")
+
+    def ascending(n, seed, step=3):
+        """a strictly ascending int32 list of n rows: random gaps of 1 .. step"""
+        g = torch.Generator(device="cuda")
+        g.manual_seed(seed)
+        return torch.cumsum(torch.randint(1, step + 1, (n,), device="cuda", generator=g, dtype=torch.int32), 0, dtype=torch.int32)
+
+    if "merge" in parts:
+        for lgn in ([lg] if lg else [22, 24, 26]):
+            n = 1 << lgn
+            half = n // 2
+            shapes = [("na = nb uniform", lambda: (ops.gen_uniform_u32(half, 42, 0, 2**31 - 1), ops.gen_uniform_u32(half, 43, 0, 2**31 - 1))),
+                      ("all keys equal", lambda: (torch.full((half,), 7, dtype=torch.int32, device="cuda"),) * 2),
+                      ("A below B", lambda: (torch.arange(half, dtype=torch.int32, device="cuda"),
+                                             torch.arange(half, n, dtype=torch.int32, device="cuda"))),
+                      ("nb = 2^10", lambda: (ops.gen_uniform_u32(n - 1024, 42, 0, 2**31 - 1), ops.gen_uniform_u32(1024, 43, 0, 2**31 - 1)))]
+            for shape, build in shapes:
+                a, b = (torch.sort(x).values.contiguous() for x in build())
+                cat = torch.cat([a, b])
+                va, vb = ops.gen_uniform_u32(a.numel(), 44, 0, 2**31 - 1), ops.gen_uniform_u32(b.numel(), 45, 0, 2**31 - 1)
+                work = cat.clone()
+                plan, sort = ops.MergeSorted(a.numel(), b.numel()), ops.RadixSortPairs(n, 8)
+                legs = {"merge ids": [], "argsort": [], "merge keys": [], "merge pairs": []}
+                for _ in range(reps):  # alternating
+                    legs["merge ids"].append(median(times(lambda: plan.launch(a, b, row_ids=True), 5)))
+                    legs["argsort"].append(median(_times_after(lambda: work.copy_(cat), lambda: sort.launch(work), 5)))
+                    legs["merge keys"].append(median(times(lambda: plan.launch(a, b), 5)))
+                    legs["merge pairs"].append(median(times(lambda: plan.launch(a, b, va, vb), 5)))
+                work.copy_(cat)
+                perm = sort.launch(work)
+                plan.launch(a, b, row_ids=True)
+                keys, ids = plan.result()
+                ok = torch.equal(keys, work) and torch.equal(ids, perm[:n]) and ops.workspace_status(sort.ws) == 0
+                plan.launch(a, b, va, vb)
+                keys, vals = plan.result()
+                ok = ok and torch.equal(keys, work) and torch.equal(vals, torch.cat([va, vb])[u64(perm[:n])])
+                _merge_row(f"merge out=2^{lgn} {shape}", legs, ok, ("merge ids", "argsort"), 12 * n / 8e12 * 1e6,
+                           f"  keys 8n {8 * n / 8e12 * 1e6:.1f} us pairs 16n {16 * n / 8e12 * 1e6:.1f} us")
+                del a, b, cat, va, vb, work, plan, sort, perm, keys, ids, vals
+    if "sets" in parts:
+        for lgn in ([lg] if lg else [20, 24, 26]):
+            n = 1 << lgn
+            a, b = ascending(n, 1), ascending(n, 2)
+            plan = ops.RowSets(n, n)
+            vendors = {"union": lambda: torch.unique(torch.cat((a, b))),
+                       "intersect": lambda: a[torch.isin(a, b, assume_unique=True)],
+                       "difference": lambda: a[~torch.isin(a, b, assume_unique=True)]}
+            for op, vendor in vendors.items():
+                def mine():
+                    plan.launch(op, a, b)
+                    return plan.count()
+
+                legs = {op: [], "torch": []}
+                for _ in range(reps):
+                    legs[op].append(median(times(mine, 5)))
+                    legs["torch"].append(median(times(vendor, 5)))
+                mine()
+                got, want = plan.result(), vendor()
+                ok = got.numel() == want.numel() and torch.equal(got, want)
+                reads = 2 * 8 * n  # count, then the merge again where a tile keeps something
+                _merge_row(f"{op} 2^{lgn} + 2^{lgn} rows -> {got.numel()}", legs, ok, (op, "torch"),
+                           (reads + 4 * got.numel()) / 8e12 * 1e6)
+            del a, b, plan
+    if "any" in parts:
+        n = 1 << 26
+        cols = [ops.gen_uniform_u32(n, 50 + i, 0, 2**31 - 1) for i in range(2)]
+        first, second, sets = ops.SelectRows(n), ops.SelectRows(n), ops.RowSets(n, n)
+        for share in (0.01, 0.5):
+            hi = min(int(share * 2**31), 2**31 - 1)
+
+            def mine():
+                first.launch(cols[0], 1, hi)
+                second.launch(cols[1], 1, hi)
+                (ra, ca), (rb, cb) = first.output(), second.output()
+                sets.launch("union", ra, rb, ca, cb)
+                return sets.count()
+
+            def vendor():
+                return torch.nonzero(((cols[0] >= 1) & (cols[0] <= hi)) | ((cols[1] >= 1) & (cols[1] <= hi))).flatten()
+
+            legs = {"select_any": [], "torch": []}
+            for _ in range(reps):
+                legs["select_any"].append(median(times(mine, 5)))
+                legs["torch"].append(median(times(vendor, 5)))
+            mine()
+            got, want = sets.result(), vendor()
+            ok = got.numel() == want.numel() and torch.equal(u64(got), want.to(torch.int64))
+            _merge_row(f"select_any n=2^26 shares ({100 * share:.0f} %, {100 * share:.0f} %) -> {got.numel()}", legs, ok,
+                       ("select_any", "torch"))
 
 
 def launch_sort_pairs(lg):
@@ -1426,7 +1562,7 @@ MODES = {"radix": radix, "ramp": ramp, "radix-idle": radix_idle, "radix-stream":
          "join-pairs": join_pairs, "launch-join-pairs": launch_join_pairs, "topk": topk, "launch-topk": launch_topk,
          "groupby-sorted": groupby_sorted, "launch-groupby-sorted": launch_groupby_sorted,
          "window": window, "launch-window": launch_window, "sorted-search": sorted_search, "range-join": range_join,
-         "selection": selection}
+         "selection": selection, "merge": merge}
 
 if __name__ == "__main__":
     if len(sys.argv) < 2 or sys.argv[1] not in MODES:
