@@ -5,8 +5,9 @@ more calls through a C ABI into hand-written gfx950 kernels: that of include/dbh
 selection vectors (SelectRows, select_range, semi_join) that of host/select_rows.hpp into libdbench.so, where entry
 points live until they are promoted to include/ (INTEGRATION.md); beside it, for the sorted merge and the set
 operations on row-id lists (MergeSorted, merge_sorted, RowSets, union_rows, intersect_rows, difference_rows, select_any),
-that of host/merge_sorted.hpp.  Nothing in this module computes on the host or falls back to torch ops: without the
-built libraries the first call raises.
+that of host/merge_sorted.hpp, and for late materialisation through a row-id list (TakeRows, take, AggregateRows,
+aggregate_rows) that of host/take_rows.hpp.  Nothing in this module computes on the host or falls back to torch ops:
+without the built libraries the first call raises.
 """
 from __future__ import annotations
 
@@ -14,7 +15,7 @@ import ctypes as C
 
 import torch
 
-from . import _capi, merge_native, select_native
+from . import _capi, merge_native, select_native, take_native
 
 DEV_OK, DEV_SPIN_TIMEOUT, DEV_KEY_RANGE, DEV_TABLE_FULL, DEV_RANK_ORDER = 0, 1, 2, 4, 8
 
@@ -417,6 +418,177 @@ def select_any(col_a: torch.Tensor, lo_a: int, hi_a: int, col_b: torch.Tensor, l
     (rows_a, count_a), (rows_b, count_b) = first.output(), second.output()
     sets.launch("union", rows_a, rows_b, count_a, count_b)
     return sets.result()
+
+
+# ---------------------------------------------------------------------------------------------
+# late materialisation: take and aggregate through a row-id list (host/take_rows.hpp, libdbench.so)
+# ---------------------------------------------------------------------------------------------
+def _fill_word(fill: int) -> int:
+    if isinstance(fill, bool) or not isinstance(fill, int) or not -(1 << 31) <= fill < (1 << 32):
+        raise ValueError(f"fill: expected an int32 or uint32 value, got {fill!r}")
+    return fill & 0xFFFFFFFF
+
+
+def _take_columns(cols, most: int | None):
+    """cols as a list of int32 GPU columns of one length -> (the list, whether a single tensor was given)"""
+    single = torch.is_tensor(cols)
+    cols = [cols] if single else list(cols)
+    if not cols or (most is not None and len(cols) > most):
+        raise ValueError(f"cols: expected 1 to {most} columns, got {len(cols)}" if most is not None else
+                         "cols: expected at least one column")
+    for i, c in enumerate(cols):
+        if not torch.is_tensor(c):
+            raise ValueError(f"cols[{i}]: expected a tensor, got {type(c).__name__}")
+        if c.numel() != cols[0].numel():
+            raise ValueError(f"cols[{i}]: {c.numel()} rows, cols[0] has {cols[0].numel()}: columns of one table")
+    for i, c in enumerate(cols):
+        _need(c, torch.int32, f"cols[{i}]")
+    return cols, single
+
+
+class TakeRows:
+    """Reusable plan that materialises up to n_cols int32 columns through a row-id list of up to `capacity` entries:
+    owns the workspace and n_cols output columns.  The list's length may be a device count (SelectRows.output(), the
+    output of RowSets, JoinPairs.total), so filter -> take is one captured sequence without a read-back.  A row id outside
+    the columns is filled with `fill` and raises DEV_KEY_RANGE; with outer the id 0xFFFFFFFF (-1: the build row of a
+    left-outer join's miss) is filled silently."""
+
+    def __init__(self, capacity: int, n_cols: int = 1, device="cuda"):
+        self.capacity, self.n_cols = int(capacity), int(n_cols)
+        if not 1 <= self.n_cols <= take_native.MAX_COLS:
+            raise ValueError(f"n_cols: expected 1 to {take_native.MAX_COLS}, got {n_cols}")
+        self.ws_bytes = take_native.workspace_bytes(self.capacity)
+        if self.ws_bytes == 0:
+            raise ValueError("capacity: at most 2^32 - 1 entries")
+        self.ws = _ws(self.ws_bytes, device)
+        self.outs = [torch.empty(max(self.capacity, 1), dtype=torch.int32, device=device) for _ in range(self.n_cols)]
+        self._count = None  # the device count of the last launch (None: all entries of its list)
+        self._used = None   # (columns, entries) of the last launch
+
+    def launch(self, cols, rows: torch.Tensor, count: torch.Tensor | None = None, outer: bool = False, fill: int = 0) -> None:
+        """Asynchronous on the current stream; nothing is read back.  cols: an int32 tensor or a sequence of 1..n_cols of
+        them, all of one length; rows: the int32 row-id list; count: a device int64 of one element, the number of entries
+        of `rows` that count (None: all of them; more than the list holds: all of them)."""
+        fill = _fill_word(fill)
+        cols, _ = _take_columns(cols, self.n_cols)
+        _need(rows, torch.int32, "rows")
+        _need_count(count, "count")
+        if rows.numel() > self.capacity:
+            raise ValueError(f"{rows.numel()} entries, the plan holds {self.capacity}")
+        list_ptr, entries, count_ptr = _column(rows, count)
+        n_rows = cols[0].numel()
+        _capi.check(take_native.take(
+            [c.data_ptr() if n_rows else None for c in cols], len(cols), n_rows, list_ptr, count_ptr, entries,
+            take_native.OUTER if outer else 0, fill, [o.data_ptr() for o in self.outs[: len(cols)]], self.ws.data_ptr(),
+            self.ws_bytes, _stream()), "take_u32")
+        self._count = count if entries else None
+        self._used = (len(cols), entries)
+
+    def status(self) -> int:
+        return workspace_status(self.ws)
+
+    def output(self):
+        """(the output columns cut to the capacity, the device count of the last launch or None) without synchronising"""
+        if self._used is None:
+            raise ValueError("output: nothing was launched on this plan")
+        return [o[: self.capacity] for o in self.outs[: self._used[0]]], self._count
+
+    def result(self, strict: bool = True):
+        """the columns of the last launch cut to min(count, entries): views of the plan's buffers; synchronises.
+        strict: a row id outside the columns (DEV_KEY_RANGE) raises; otherwise such entries hold the fill."""
+        if self._used is None:
+            raise ValueError("result: nothing was launched on this plan")
+        if strict:
+            _check_status(self.ws, "take_u32")
+        used, entries = self._used
+        m = entries if self._count is None else min(max(int(self._count.item()), 0), entries)
+        return [o[:m] for o in self.outs[:used]]
+
+
+def take(cols, rows: torch.Tensor, outer: bool = False, fill: int = 0):
+    """cols[c][rows[i]] for every i: a tensor for a tensor, a list for a sequence of int32 columns of one length (more
+    than four run in groups of four).  A row id outside the columns raises; with outer the id -1 gives `fill`."""
+    _fill_word(fill)
+    cols, single = _take_columns(cols, None)
+    _need(rows, torch.int32, "rows")
+    out = []
+    for at in range(0, len(cols), take_native.MAX_COLS):
+        group = cols[at: at + take_native.MAX_COLS]
+        plan = TakeRows(rows.numel(), len(group), rows.device)
+        plan.launch(group, rows, outer=outer, fill=fill)
+        out += plan.result()
+    return out[0] if single else out
+
+
+class AggregateRows:
+    """Reusable plan for COUNT, the 64-bit SUM, MIN and MAX of an int32 column (as uint32, or as int32 with signed) over
+    a row-id list of up to `capacity` entries, or over all its rows (up to `capacity` of them), without materialising
+    the values: owns the workspace and the four device result words."""
+
+    def __init__(self, capacity: int, device="cuda"):
+        self.capacity = int(capacity)
+        self.ws_bytes = take_native.workspace_bytes(self.capacity)
+        if self.ws_bytes == 0:
+            raise ValueError("capacity: at most 2^32 - 1 entries")
+        self.ws = _ws(self.ws_bytes, device)
+        self.out = torch.zeros(4, dtype=torch.int64, device=device)
+        self._signed = None  # of the last launch
+
+    def launch(self, col: torch.Tensor, rows: torch.Tensor | None = None, count: torch.Tensor | None = None,
+               signed: bool = False, outer: bool = False) -> None:
+        """Asynchronous on the current stream; nothing is read back.  rows: an int32 row-id list (None: all rows of col);
+        count: a device int64 of one element, the entries of `rows` that count.  Row ids outside the column are skipped
+        and raise DEV_KEY_RANGE; with outer the id 0xFFFFFFFF is skipped silently."""
+        if rows is None and count is not None:
+            raise ValueError("count: given without rows")
+        _need(col, torch.int32, "col")
+        if rows is not None:
+            _need(rows, torch.int32, "rows")
+        _need_count(count, "count")
+        candidates = col.numel() if rows is None else rows.numel()
+        if candidates > self.capacity:
+            raise ValueError(f"{candidates} candidates, the plan holds {self.capacity}")
+        list_ptr, entries, count_ptr = _column(rows, count)
+        col_ptr, n_rows = (col.data_ptr(), col.numel()) if col.numel() else (None, 0)
+        if rows is not None and not entries:  # an empty list has no address: the call over no rows at all
+            col_ptr, n_rows = None, 0
+        flags = (take_native.SIGNED if signed else 0) | (take_native.OUTER if outer else 0)
+        _capi.check(take_native.aggregate(col_ptr, n_rows, list_ptr, count_ptr, entries, flags, self.out.data_ptr(),
+                                          self.ws.data_ptr(), self.ws_bytes, _stream()), "aggregate_rows_u32")
+        self._signed = bool(signed)
+
+    def status(self) -> int:
+        return workspace_status(self.ws)
+
+    def output(self) -> torch.Tensor:
+        """the four device words (count, sum, min, max: int64 storage of uint64) of the last launch, without synchronising"""
+        if self._signed is None:
+            raise ValueError("output: nothing was launched on this plan")
+        return self.out
+
+    def result(self, strict: bool = True):
+        """(count, sum, min, max) of the last launch as Python ints: the sum mod 2^64 as an unsigned number, or as a
+        two's-complement one with signed; min and max are None when count is 0.  Synchronises.  strict: a row id outside
+        the column among the candidates (DEV_KEY_RANGE) raises; otherwise such candidates are just skipped."""
+        if self._signed is None:
+            raise ValueError("result: nothing was launched on this plan")
+        if strict:
+            _check_status(self.ws, "aggregate_rows_u32")
+        words = [int(w) for w in self.out.tolist()]  # two's complement of the uint64 words
+        if not self._signed:
+            words = [w & 0xFFFFFFFFFFFFFFFF for w in words]
+        n = words[0] & 0xFFFFFFFFFFFFFFFF
+        return n, words[1], (words[2] if n else None), (words[3] if n else None)
+
+
+def aggregate_rows(col: torch.Tensor, rows: torch.Tensor | None = None, signed: bool = False, outer: bool = False):
+    """(COUNT, SUM, MIN, MAX) of col over the row-id list `rows`, or over all its rows; see AggregateRows.result()."""
+    _need(col, torch.int32, "col")
+    if rows is not None:
+        _need(rows, torch.int32, "rows")
+    plan = AggregateRows(col.numel() if rows is None else rows.numel(), col.device)
+    plan.launch(col, rows, signed=signed, outer=outer)
+    return plan.result()
 
 
 # ---------------------------------------------------------------------------------------------

@@ -68,6 +68,16 @@ the contract numbers come from bench.py.
                   run until the rows and their number are usable on the host.  select + select + union at 2^26 rows against
                   torch.nonzero(ka | kb) at shares (1 %, 1 %) and (50 %, 50 %).  Every result compared with the comparison
                   leg's (MERGE_PARTS=merge,sets,any picks parts)
+  take [lg]       late materialisation through a row-id list (ops.TakeRows, ops.AggregateRows: host/take_rows.hpp) out of a
+                  2^26-row column (or 2^lg), same protocol and floor as sorted-search.  Lists: ascending as a selection leaves them
+                  at 1, 10, 50 and 100 % kept, random subsets of 2^20 and 2^24 rows ascending and shuffled, and a permutation of
+                  all rows.  take of 1, 2 and 4 columns against torch.index_select per column; the aggregate against
+                  index_select + sum (int64), min, max, and against this library's own take followed by the same reductions;
+                  the aggregate over all rows against the torch reductions; select -> refine -> aggregate against the boolean
+                  mask form.  The aggregate legs end with the four numbers on the host, the take legs with the columns on the
+                  device.  Beside each row the gather rate (entries x columns / s, the chip's random-gather rate is 53-57 G/s)
+                  and the time of 4m + 4km bytes plus the gathered 128-byte lines at 8 TB/s.  Every result compared with
+                  torch's (TAKE_PARTS=take,aggregate,dense,chain picks parts)
   launch-join-pairs [lg]  five expansions at 2^lg rows a side (default 24) and five of the one-key shape, nothing else
                   (`rocprofv3 --kernel-trace --stats`)
   launch-sort-pairs [lg]  five 8-bit argsorts of 2^lg full-range keys (default 24) and nothing else (`rocprofv3 --kernel-trace`)
@@ -760,6 +770,8 @@ def _merge_row(name, legs, ok, floor_of=None, model_us=None, extra=""):
         verdict = f"  floor {'holds' if max(mine) <= min(other) else 'MISSED'}  x{median(sorted(other)) / median(sorted(mine)):5.2f}"
         if model_us is not None:
             verdict += f"  bytes at 8 TB/s {model_us:7.1f} us = {100 * model_us / median(sorted(mine)):3.0f} %"
+    if callable(extra):
+        extra = extra(legs)
     print(f"{TAG:10s} {name:52s} {cols}{verdict}  {'ok' if ok else 'WRONG'}{extra}   "
           + " ".join(f"{leg}:" + "/".join(f"{t:.1f}" for t in ts) for leg, ts in legs.items()), flush=True)
 
@@ -857,6 +869,109 @@ def merge(lg):
             ok = got.numel() == want.numel() and torch.equal(u64(got), want.to(torch.int64))
             _merge_row(f"select_any n=2^26 shares ({100 * share:.0f} %, {100 * share:.0f} %) -> {got.numel()}", legs, ok,
                        ("select_any", "torch"))
+
+
+def take(lg):
+    """TAKE_PARTS=take,aggregate,dense,chain picks parts; lists below 2^19 entries are not measured"""
+    reps = int(os.environ.get("REPS", "5"))
+    parts = os.environ.get("TAKE_PARTS", "take,aggregate,dense,chain").split(",")
+    n = 1 << (lg or 26)
+    cols = [ops.gen_uniform_u32(n, 60 + i, 0, 2**31 - 1) for i in range(4)]
+
+    def lists():
+        g = torch.Generator(device="cuda")
+        g.manual_seed(5)
+        for share in (0.01, 0.1, 0.5):
+            keep = torch.rand(n, device="cuda", generator=g) < share
+            yield f"ascending {100 * share:3.0f} % kept", torch.nonzero(keep).flatten().to(torch.int32)
+        yield "ascending 100 % kept", torch.arange(n, dtype=torch.int32, device="cuda")
+        perm = torch.randperm(n, device="cuda", generator=g).to(torch.int32)
+        for lgm in (20, 24):
+            if (1 << lgm) < n:
+                yield f"ascending 2^{lgm} random", torch.sort(perm[: 1 << lgm]).values.contiguous()
+                yield f"shuffled  2^{lgm} random", perm[: 1 << lgm].contiguous()
+        yield "shuffled  all rows", perm
+
+    def reduced(v):  # the four numbers on the host after one transfer
+        return [v.numel()] + torch.stack([v.sum(dtype=torch.int64), v.min().to(torch.int64), v.max().to(torch.int64)]).tolist()
+
+    def run(name, legs_fn, ok_fn, floor_of, model_us, extra):
+        legs = {leg: [] for leg in legs_fn}
+        for _ in range(reps):  # alternating
+            for leg, fn in legs_fn.items():
+                legs[leg].append(median(times(fn, 5)))
+        _merge_row(name, legs, ok_fn(), floor_of, model_us, extra)
+
+    if "take" in parts or "aggregate" in parts:
+        for name, rows in lists():
+            m = rows.numel()
+            lines = torch.unique(rows >> 5).numel()  # 128-byte lines of a column the list touches
+            if "take" in parts:
+                for k in (1, 2, 4):
+                    plan = ops.TakeRows(m, k)
+                    mine = lambda: plan.launch(cols[:k], rows)  # noqa: E731
+                    vendor = lambda: [torch.index_select(c, 0, rows) for c in cols[:k]]  # noqa: E731
+
+                    def ok():
+                        mine()
+                        return all(torch.equal(g, w) for g, w in zip(plan.result(), vendor()))
+
+                    model = (4 * m + 4 * k * m + 128 * k * lines) / 8e12 * 1e6
+                    run(f"take k={k} m={m} {name}", {"take": mine, "torch": vendor}, ok, ("take", "torch"), model,
+                        lambda legs: f"  {k * m / median(sorted(legs['take'])) / 1e3:6.1f} G gathers/s")
+                    del plan
+            if "aggregate" in parts:
+                agg, plan = ops.AggregateRows(m), ops.TakeRows(m, 1)
+
+                def mine():
+                    agg.launch(cols[0], rows)
+                    return agg.result()
+
+                def vendor():
+                    return reduced(torch.index_select(cols[0], 0, rows))
+
+                def own_take():
+                    plan.launch(cols[0], rows)
+                    return reduced(plan.outs[0][:m])
+
+                model = (4 * m + 128 * lines) / 8e12 * 1e6
+                run(f"aggregate m={m} {name}", {"aggregate": mine, "torch": vendor, "take+torch": own_take},
+                    lambda: list(mine()) == vendor() == own_take(), ("aggregate", "torch"), model,
+                    lambda legs: f"  {m / median(sorted(legs['aggregate'])) / 1e3:6.1f} G gathers/s  against take+torch "
+                                 f"{'holds' if max(legs['aggregate']) <= min(legs['take+torch']) else 'MISSED'}")
+                del agg, plan
+            del rows
+    if "dense" in parts:
+        for lgn in sorted({20, 24, 26, lg or 26}):
+            if (1 << lgn) > n:
+                continue
+            col = cols[0][: 1 << lgn]
+            agg = ops.AggregateRows(col.numel())
+
+            def mine():
+                agg.launch(col)
+                return agg.result()
+
+            run(f"aggregate over all rows n=2^{lgn}", {"aggregate": mine, "torch": lambda: reduced(col)},
+                lambda: list(mine()) == reduced(col), ("aggregate", "torch"), 4 * col.numel() / 8e12 * 1e6, lambda legs: "")
+            del agg
+    if "chain" in parts:
+        sel, agg = ops.SelectRows(n), ops.AggregateRows(n)
+        for share in (0.01, 0.5):
+            hi = min(int(share ** 0.5 * 2**31), 2**31 - 1)  # two predicates of sqrt(share) each
+
+            def mine():
+                sel.launch(cols[0], 1, hi)
+                sel.refine(cols[1], 1, hi)
+                agg.launch(cols[2], *sel.output())
+                return agg.result()
+
+            def vendor():
+                keep = (cols[0] >= 1) & (cols[0] <= hi) & (cols[1] >= 1) & (cols[1] <= hi)
+                return reduced(cols[2][keep])
+
+            run(f"select -> refine -> aggregate n={n} share {100 * share:.0f} %", {"chain": mine, "torch": vendor},
+                lambda: list(mine()) == vendor(), ("chain", "torch"), None, lambda legs: f"  rows {mine()[0]}")
 
 
 def launch_sort_pairs(lg):
@@ -1562,7 +1677,7 @@ MODES = {"radix": radix, "ramp": ramp, "radix-idle": radix_idle, "radix-stream":
          "join-pairs": join_pairs, "launch-join-pairs": launch_join_pairs, "topk": topk, "launch-topk": launch_topk,
          "groupby-sorted": groupby_sorted, "launch-groupby-sorted": launch_groupby_sorted,
          "window": window, "launch-window": launch_window, "sorted-search": sorted_search, "range-join": range_join,
-         "selection": selection, "merge": merge}
+         "selection": selection, "merge": merge, "take": take}
 
 if __name__ == "__main__":
     if len(sys.argv) < 2 or sys.argv[1] not in MODES:
