@@ -6,8 +6,10 @@ selection vectors (SelectRows, select_range, semi_join) that of host/select_rows
 points live until they are promoted to include/ (INTEGRATION.md); beside it, for the sorted merge and the set
 operations on row-id lists (MergeSorted, merge_sorted, RowSets, union_rows, intersect_rows, difference_rows, select_any),
 that of host/merge_sorted.hpp, and for late materialisation through a row-id list (TakeRows, take, AggregateRows,
-aggregate_rows) that of host/take_rows.hpp.  Nothing in this module computes on the host or falls back to torch ops:
-without the built libraries the first call raises.
+aggregate_rows) that of host/take_rows.hpp, and for dictionary encoding (Dictionary, factorize, dict_combine,
+encode_columns, and the two compositions over several key columns, groupby_columns and join_pairs_columns) that of
+host/dict_encode.hpp.  Nothing in this module computes on the host or falls back to torch ops: without the built libraries
+the first call raises.
 """
 from __future__ import annotations
 
@@ -15,7 +17,7 @@ import ctypes as C
 
 import torch
 
-from . import _capi, merge_native, select_native, take_native
+from . import _capi, dict_native, merge_native, select_native, take_native
 
 DEV_OK, DEV_SPIN_TIMEOUT, DEV_KEY_RANGE, DEV_TABLE_FULL, DEV_RANK_ORDER = 0, 1, 2, 4, 8
 
@@ -589,6 +591,228 @@ def aggregate_rows(col: torch.Tensor, rows: torch.Tensor | None = None, signed: 
     plan = AggregateRows(col.numel() if rows is None else rows.numel(), col.device)
     plan.launch(col, rows, signed=signed, outer=outer)
     return plan.result()
+
+
+# ---------------------------------------------------------------------------------------------
+# dictionary encoding: factorize, multi-column keys (host/dict_encode.hpp, libdbench.so)
+# ---------------------------------------------------------------------------------------------
+DICT_MISS = dict_native.MISS            # the code of a value a dictionary does not hold (-1 as int32): take's "no row" id
+DICT_LDS_SLOTS = dict_native.LDS_SLOTS  # tables up to this many slots (capacities up to half of it) are encoded out of LDS
+DICT_DENSE_GROUPS = 1 << 22             # groupby_columns: composite cardinalities up to this go to the dense group-by
+
+
+class Dictionary:
+    """Reusable order-preserving dictionary of one int32 column (values ordered as uint32, or as int32 with signed) with up
+    to `capacity` distinct values (0: n, always enough for a column of n rows; the build sorts `capacity` padded entries
+    whatever the column holds, so a caller who knows a bound passes it).  Owns the workspace, which holds the table value
+    -> code between build and encode, the key column and the device count.  A code is the index of the value in `keys`;
+    DICT_MISS stands for a value the dictionary does not hold."""
+
+    def __init__(self, n: int, capacity: int = 0, device="cuda"):
+        self.n = int(n)
+        self.capacity = int(capacity) if capacity else max(self.n, 1)
+        self.ws_bytes = dict_native.workspace_bytes(self.capacity)
+        if self.ws_bytes == 0:
+            raise ValueError("capacity: 1 to 2^31 - 1 distinct values")
+        self.ws = _ws(self.ws_bytes, device)
+        self.keys = torch.empty(self.capacity, dtype=torch.int32, device=device)
+        self.count_dev = torch.zeros(1, dtype=torch.int64, device=device)  # the number of keys, for combine and take
+        self._signed = None  # of the last build
+
+    def build(self, col: torch.Tensor, count: torch.Tensor | None = None, signed: bool = False) -> None:
+        """Asynchronous on the current stream; nothing is read back.  count: a device int64 of one element, the rows of
+        `col` that count.  More than `capacity` distinct values raise DEV_TABLE_FULL in the workspace."""
+        _need(col, torch.int32, "col")
+        _need_count(count, "count")
+        ptr, rows, count_ptr = _column(col, count)
+        _capi.check(dict_native.build(ptr, rows, count_ptr, self.capacity, dict_native.SIGNED if signed else 0,
+                                      self.keys.data_ptr(), self.count_dev.data_ptr(), self.ws.data_ptr(), self.ws_bytes,
+                                      _stream()), "dict_build_u32")
+        self._signed = bool(signed)
+
+    def _built(self, what: str) -> None:
+        if self._signed is None:
+            raise ValueError(f"{what}: nothing was built on this plan")
+
+    def encode(self, col: torch.Tensor, count: torch.Tensor | None = None, out: torch.Tensor | None = None,
+               misses: torch.Tensor | None = None) -> torch.Tensor:
+        """-> the codes of col's rows (a new int32 column, or `out`); asynchronous, nothing is read back, the dictionary
+        is only read.  Rows behind `count` are not written.  misses: a device int64 of one element for the number of
+        rows whose value the dictionary does not hold."""
+        self._built("encode")
+        _need(col, torch.int32, "col")
+        _need_count(count, "count")
+        _need_count(misses, "misses")
+        if out is None:
+            out = torch.empty(col.numel(), dtype=torch.int32, device=col.device)
+        else:
+            _need(out, torch.int32, "out")
+            if out.numel() != col.numel():
+                raise ValueError(f"out: {out.numel()} rows, col has {col.numel()}")
+        ptr, rows, count_ptr = _column(col, count)
+        _capi.check(dict_native.encode(ptr, rows, count_ptr, out.data_ptr() if rows else None,
+                                       misses.data_ptr() if misses is not None else None, self.ws.data_ptr(), self.ws_bytes,
+                                       _stream()), "dict_encode_u32")
+        return out
+
+    def status(self) -> int:
+        return workspace_status(self.ws)
+
+    def count(self) -> int:
+        """the number of distinct values of the last build; synchronises and raises on a device status"""
+        self._built("count")
+        _check_status(self.ws, "dict_build_u32")
+        return int(self.count_dev.item())
+
+    def result(self) -> torch.Tensor:
+        """the distinct values in order: a view of the plan's key column cut to their number; synchronises and raises on
+        a device status (DEV_TABLE_FULL: more distinct values than the capacity)"""
+        return self.keys[: self.count()]
+
+    def decode(self, codes: torch.Tensor, fill: int = 0) -> torch.Tensor:
+        """the values of `codes`: take through the keys, DICT_MISS giving `fill`"""
+        self._built("decode")
+        return take(self.result(), codes, outer=True, fill=fill)
+
+
+def factorize(col: torch.Tensor, signed: bool = False, capacity: int | None = None):
+    """-> (codes, uniques) with uniques the distinct values in order and uniques[codes] == col: the answer of
+    numpy.unique(col, return_inverse=True) on the uint32 (signed: int32) view.  capacity: a bound on the number of
+    distinct values (None: the number of rows); more than that raise."""
+    _need(col, torch.int32, "col")
+    plan = Dictionary(col.numel(), capacity or 0, col.device)
+    plan.build(col, signed=signed)
+    codes = plan.encode(col)
+    return codes, plan.result()
+
+
+def dict_combine(outer: torch.Tensor, inner: torch.Tensor, outer_card: torch.Tensor, inner_card: torch.Tensor,
+                 count: torch.Tensor | None = None, out: torch.Tensor | None = None, ws: torch.Tensor | None = None):
+    """-> (out, ws): out[i] = outer[i] * inner_card + inner[i], DICT_MISS where either code is; asynchronous, nothing is
+    read back.  The cardinalities are device int64 of one element (Dictionary.count_dev).  out may be `outer` itself.  A
+    product of the cardinalities above 0xFFFFFFFF raises DEV_KEY_RANGE in ws (256 bytes, made here when not given) and
+    leaves DICT_MISS everywhere."""
+    _need(outer, torch.int32, "outer")
+    _need(inner, torch.int32, "inner")
+    for name, t in (("outer_card", outer_card), ("inner_card", inner_card)):
+        if t is None:
+            raise ValueError(f"{name}: expected one int64 on the GPU")
+        _need_count(t, name)
+    _need_count(count, "count")
+    if inner.numel() != outer.numel():
+        raise ValueError(f"inner: {inner.numel()} rows, outer has {outer.numel()}")
+    if out is None:
+        out = torch.empty(outer.numel(), dtype=torch.int32, device=outer.device)
+    else:
+        _need(out, torch.int32, "out")
+        if out.numel() != outer.numel():
+            raise ValueError(f"out: {out.numel()} rows, outer has {outer.numel()}")
+    if ws is None:
+        ws = _ws(256, outer.device)
+    rows = outer.numel()
+    _capi.check(dict_native.combine(outer.data_ptr() if rows else None, inner.data_ptr() if rows else None, rows,
+                                    count.data_ptr() if count is not None and rows else None, outer_card.data_ptr(),
+                                    inner_card.data_ptr(), out.data_ptr() if rows else None, ws.data_ptr(), ws.numel(),
+                                    _stream()), "dict_combine_u32")
+    return out, ws
+
+
+def _key_columns(cols, least: int, name: str = "cols"):
+    cols = list(cols)
+    if len(cols) < least:
+        raise ValueError(f"{name}: expected {'two or more' if least == 2 else 'at least one'} columns, got {len(cols)}")
+    for i, c in enumerate(cols):
+        if not torch.is_tensor(c):
+            raise ValueError(f"{name}[{i}]: expected a tensor, got {type(c).__name__}")
+        if c.numel() != cols[0].numel():
+            raise ValueError(f"{name}[{i}]: {c.numel()} rows, {name}[0] has {cols[0].numel()}: columns of one table")
+    for i, c in enumerate(cols):
+        _need(c, torch.int32, f"{name}[{i}]")
+    return cols
+
+
+def _combine_codes(codes, cards, device):
+    """the codes of several columns folded left to right -> (composite, its cardinality); raises on overflow"""
+    composite, card = codes[0], cards[0]
+    for inner, inner_card in zip(codes[1:], cards[1:]):
+        oc, ic = (torch.tensor([c], dtype=torch.int64, device=device) for c in (card, inner_card))
+        composite, ws = dict_combine(composite, inner, oc, ic)
+        if workspace_status(ws) != DEV_OK:
+            raise _capi.DbhipError(f"dict_combine_u32: {card} x {inner_card} composite keys do not fit 32 bits "
+                                   f"(device status {DEV_KEY_RANGE:#x})")
+        card *= inner_card
+    return composite, card
+
+
+def _encode_columns(cols, signed: bool, least: int):
+    cols = _key_columns(cols, least)
+    pairs = [factorize(c, signed) for c in cols]
+    uniques = [u for _, u in pairs]
+    composite, card = _combine_codes([c for c, _ in pairs], [u.numel() for u in uniques], cols[0].device)
+    return composite, uniques, card
+
+
+def encode_columns(cols, signed: bool = False):
+    """Two or more int32 columns of one table -> (codes, [uniques per column], cardinality): every column is factorized
+    and the codes are combined left to right, so codes order the rows as the tuples (cols[0][i], cols[1][i], ...) do,
+    equal tuples have equal codes, and all codes lie below cardinality = the product of the columns' numbers of distinct
+    values.  A cardinality above 0xFFFFFFFF raises."""
+    return _encode_columns(cols, signed, 2)
+
+
+def groupby_columns(cols, vals: torch.Tensor, signed: bool = False, dense_groups: int | None = None):
+    """GROUP BY cols[0], cols[1], ... SUM(vals), COUNT(*): -> ([key columns], sums, counts), one row per distinct tuple, in
+    the tuples' lexicographic order; SUM wraps at 32 bits as in both group-bys.  The composite code of encode_columns is the
+    key of the dense groupby_sum while its cardinality is at most dense_groups (None: DICT_DENSE_GROUPS), of groupby_hash
+    followed by a sort of the groups otherwise; the key columns come back from the composite by divide / modulo and a
+    take through each column's uniques."""
+    cols = _key_columns(cols, 1)
+    _need(vals, torch.int32, "vals")
+    if vals.numel() != cols[0].numel():
+        raise ValueError(f"vals: {vals.numel()} rows, cols[0] has {cols[0].numel()}")
+    composite, uniques, card = _encode_columns(cols, signed, 1)
+    limit = DICT_DENSE_GROUPS if dense_groups is None else int(dense_groups)
+    if card == 0:  # no rows
+        groups = sums = counts = composite
+    elif card <= limit:
+        all_sums = groupby_sum(composite, vals, card)
+        all_counts = groupby_sum(composite, torch.ones_like(vals), card)
+        groups = select_range(all_counts, 1, 0xFFFFFFFF)  # the tuples that occur, ascending
+        sums, counts = take([all_sums, all_counts], groups)
+    else:
+        keys, sums, counts = groupby_hash(composite, vals)
+        groups = keys.clone()
+        order = radix_argsort_(groups)  # groups: the composites ascending
+        sums, counts = take([sums, counts], order)
+    rest = groups.to(torch.int64) & 0xFFFFFFFF
+    key_cols = []
+    for u in reversed(uniques):
+        d = max(u.numel(), 1)
+        key_cols.append(take(u, (rest % d).to(torch.int32)) if rest.numel() else u[:0])
+        rest = rest // d
+    return key_cols[::-1], sums, counts
+
+
+def join_pairs_columns(build_cols, probe_cols, left_outer: bool = False):
+    """The equi-join ON build.c0 = probe.c0 AND build.c1 = probe.c1 ...: -> (build_rows, probe_rows) as join_pairs gives
+    them, probe rows ascending (left_outer: and one pair with build row -1 per probe row without a match).  The
+    dictionaries are built on the build side's columns and the probe side is encoded through them: a probe value the build
+    side does not hold becomes DICT_MISS, and so does the row's composite, which matches nothing."""
+    build_cols, probe_cols = list(build_cols), list(probe_cols)
+    if len(build_cols) != len(probe_cols):
+        raise ValueError(f"probe_cols: {len(probe_cols)} columns, build_cols has {len(build_cols)}")
+    build_cols, probe_cols = _key_columns(build_cols, 1, "build_cols"), _key_columns(probe_cols, 1, "probe_cols")
+    build_codes, probe_codes, cards = [], [], []
+    for b, p in zip(build_cols, probe_cols):
+        plan = Dictionary(b.numel(), 0, b.device)
+        plan.build(b)
+        build_codes.append(plan.encode(b))
+        probe_codes.append(plan.encode(p))
+        cards.append(plan.count())
+    device = build_cols[0].device
+    build_key, _ = _combine_codes(build_codes, cards, device)
+    probe_key, _ = _combine_codes(probe_codes, cards, device)
+    return join_pairs(build_key, probe_key, left_outer=left_outer, ordered=True)
 
 
 # ---------------------------------------------------------------------------------------------

@@ -78,6 +78,15 @@ the contract numbers come from bench.py.
                   device.  Beside each row the gather rate (entries x columns / s, the chip's random-gather rate is 53-57 G/s)
                   and the time of 4m + 4km bytes plus the gathered 128-byte lines at 8 TB/s.  Every result compared with
                   torch's (TAKE_PARTS=take,aggregate,dense,chain picks parts)
+  dict [lg]       dictionary encoding (ops.Dictionary, ops.groupby_columns: host/dict_encode.hpp) at 2^20, 2^24 and 2^26 rows (or
+                  2^lg alone), same protocol and floor as sorted-search, over columns of 1, 64, 4096 (the encode kernel's LDS body),
+                  2^20 and all-distinct values (its global body) spread over the 32 bits.  factorize (build + encode, the
+                  capacity the number of distinct values) against torch.unique(sorted=True, return_inverse=True), and beside it
+                  the same with capacity = n, whose build sorts n padded entries whatever the column holds; encode alone against
+                  torch.searchsorted on the sorted uniques, with the time of its 8n bytes at 8 TB/s; GROUP BY two columns SUM,
+                  COUNT (ops.groupby_columns, up to 2^DICT_GROUPBY_LG rows, default 24) against torch.unique(dim=0,
+                  return_inverse=True) + scatter_add.  Every result compared with torch's (DICT_PARTS=factorize,encode,groupby
+                  and DICT_CARDS=1,64,4096,1048576,0 pick parts and cardinalities; 0 = all distinct)
   launch-join-pairs [lg]  five expansions at 2^lg rows a side (default 24) and five of the one-key shape, nothing else
                   (`rocprofv3 --kernel-trace --stats`)
   launch-sort-pairs [lg]  five 8-bit argsorts of 2^lg full-range keys (default 24) and nothing else (`rocprofv3 --kernel-trace`)
@@ -974,6 +983,96 @@ def take(lg):
                 lambda: list(mine()) == vendor(), ("chain", "torch"), None, lambda legs: f"  rows {mine()[0]}")
 
 
+def dict_encoding(lg):
+    """DICT_PARTS=factorize,encode,groupby picks parts; DICT_CARDS=64,4096,... picks cardinalities (0: all rows distinct,
+    1: the one-key column)"""
+    reps = int(os.environ.get("REPS", "5"))
+    parts = os.environ.get("DICT_PARTS", "factorize,encode,groupby").split(",")
+    cards = [int(c) for c in os.environ.get("DICT_CARDS", "1,64,4096,1048576,0").split(",")]
+    g = torch.Generator(device="cuda")
+    g.manual_seed(7)
+
+    def spread(t):  # distinct int64 values -> distinct 32-bit patterns all over the range (an odd multiplier is a bijection)
+        return bits32((t * 2654435761) % 2**32)
+
+    def column(n, card):
+        if card == 0:
+            return spread(torch.randperm(n, device="cuda", generator=g))
+        values = spread(torch.randperm(max(card, 2) * 4, device="cuda", generator=g)[:card])
+        return values[torch.randint(0, card, (n,), device="cuda", generator=g)].contiguous()
+
+    def run(name, legs_fn, ok_fn, floor_of, model_us=None, extra=""):
+        legs = {leg: [] for leg in legs_fn}
+        for _ in range(reps):  # alternating
+            for leg, fn in legs_fn.items():
+                legs[leg].append(median(times(fn, 5)))
+        _merge_row(name, legs, ok_fn(), floor_of, model_us, extra)
+
+    for lgn in ([lg] if lg else [20, 24, 26]):
+        n = 1 << lgn
+        for card in cards:
+            if card > n:
+                continue
+            d = card or n
+            label = f"n=2^{lgn} d={'n' if card == 0 else card}"
+            col = column(n, card)
+            if "factorize" in parts or "encode" in parts:
+                # the order is int32's on both sides: what torch.unique gives for an int32 column
+                bound, whole = ops.Dictionary(n, d), (ops.Dictionary(n) if d < n else None)
+                codes = torch.empty(n, dtype=torch.int32, device="cuda")
+
+                def mine(plan=bound):
+                    plan.build(col, signed=True)
+                    plan.encode(col, out=codes)
+
+                vendor = lambda: torch.unique(col, sorted=True, return_inverse=True)  # noqa: E731
+
+                def ok(plan=bound):
+                    mine(plan)
+                    uniques, inverse = vendor()
+                    return torch.equal(plan.result(), uniques) and torch.equal(codes.to(torch.int64), inverse)
+
+                if "factorize" in parts:
+                    legs = {"factorize": mine, "torch": vendor}
+                    if whole is not None:  # capacity = n: the build sorts n padded entries whatever d is
+                        legs["capacity=n"] = lambda: mine(whole)
+                    run(f"factorize {label}", legs, lambda: ok() and (whole is None or ok(whole)), ("factorize", "torch"), None,
+                        lambda legs: f"  capacity=n costs x{median(sorted(legs['capacity=n'])) / median(sorted(legs['factorize'])):.2f}"
+                        if "capacity=n" in legs else "")
+                if "encode" in parts:
+                    mine()
+                    uniques = bound.result().clone()
+                    enc = lambda: bound.encode(col, out=codes)  # noqa: E731
+                    search = lambda: torch.searchsorted(uniques, col)  # noqa: E731
+                    body = "LDS" if 2 * d <= ops.DICT_LDS_SLOTS else "global"
+                    run(f"encode ({body} body) {label}", {"encode": enc, "torch": search},
+                        lambda: (enc(), torch.equal(codes.to(torch.int64), search()))[1], ("encode", "torch"), 8 * n / 8e12 * 1e6)
+                del bound, whole, codes
+            if "groupby" in parts and card != 0 and lgn <= int(os.environ.get("DICT_GROUPBY_LG", "24")):
+                # two key columns of about sqrt(d) values each: about d groups
+                side = max(int(round(d ** 0.5)), 1)
+                a, b = column(n, side), column(n, side)
+                vals = ops.gen_uniform_u32(n, 9, 0, 2**31 - 1)
+                vals64 = vals.to(torch.int64)
+
+                def mine_groups():
+                    return ops.groupby_columns([a, b], vals, signed=True)
+
+                def vendor_groups():
+                    rows, inverse = torch.unique(torch.stack([a, b], dim=1), dim=0, return_inverse=True)
+                    return rows, torch.zeros(rows.shape[0], dtype=torch.int64, device="cuda").scatter_add_(0, inverse.flatten(), vals64)
+
+                def ok_groups():
+                    (ka, kb), sums, _ = mine_groups()
+                    rows, want = vendor_groups()
+                    return torch.equal(ka, rows[:, 0]) and torch.equal(kb, rows[:, 1]) and torch.equal(u64(sums), want % 2**32)
+
+                run(f"group by two columns n=2^{lgn} {side} x {side}", {"groupby_columns": mine_groups, "torch": vendor_groups},
+                    ok_groups, ("groupby_columns", "torch"))
+                del a, b, vals, vals64
+            del col
+
+
 def launch_sort_pairs(lg):
     n = 1 << (lg or 24)
     keys0 = ops.gen_uniform_u32(n, 42, 0, 2**32 - 1)
@@ -1677,7 +1776,7 @@ MODES = {"radix": radix, "ramp": ramp, "radix-idle": radix_idle, "radix-stream":
          "join-pairs": join_pairs, "launch-join-pairs": launch_join_pairs, "topk": topk, "launch-topk": launch_topk,
          "groupby-sorted": groupby_sorted, "launch-groupby-sorted": launch_groupby_sorted,
          "window": window, "launch-window": launch_window, "sorted-search": sorted_search, "range-join": range_join,
-         "selection": selection, "merge": merge, "take": take}
+         "selection": selection, "merge": merge, "take": take, "dict": dict_encoding}
 
 if __name__ == "__main__":
     if len(sys.argv) < 2 or sys.argv[1] not in MODES:
