@@ -8,7 +8,8 @@ operations on row-id lists (MergeSorted, merge_sorted, RowSets, union_rows, inte
 that of host/merge_sorted.hpp, and for late materialisation through a row-id list (TakeRows, take, AggregateRows,
 aggregate_rows) that of host/take_rows.hpp, and for dictionary encoding (Dictionary, factorize, dict_combine,
 encode_columns, and the two compositions over several key columns, groupby_columns and join_pairs_columns) that of
-host/dict_encode.hpp.  Nothing in this module computes on the host or falls back to torch ops: without the built libraries
+host/dict_encode.hpp, and for bit-packed columns (PackedColumn, BitPack, pack, unpack, select_range_packed, and SelectRows on
+a PackedColumn) that of host/bitpack.hpp.  Nothing in this module computes on the host or falls back to torch ops: without the built libraries
 the first call raises.
 """
 from __future__ import annotations
@@ -17,7 +18,7 @@ import ctypes as C
 
 import torch
 
-from . import _capi, dict_native, merge_native, select_native, take_native
+from . import _capi, bitpack_native, dict_native, merge_native, select_native, take_native
 
 DEV_OK, DEV_SPIN_TIMEOUT, DEV_KEY_RANGE, DEV_TABLE_FULL, DEV_RANK_ORDER = 0, 1, 2, 4, 8
 
@@ -157,16 +158,23 @@ class SelectRows:
         self.ws_bytes = select_native.workspace_bytes(self.capacity)
         if self.ws_bytes == 0:
             raise ValueError("capacity: at most 2^32 - 1 candidates")
+        # one workspace for plain and packed columns: whichever query is larger
+        self.ws_bytes = max(self.ws_bytes, bitpack_native.workspace_bytes(self.capacity))
         self.ws = _ws(self.ws_bytes, device)
         self.rows = [torch.empty(max(self.capacity, 1), dtype=torch.int32, device=device) for _ in range(2)]
         self.counts = torch.zeros(2, dtype=torch.int64, device=device)
         self._last = None  # index of the buffer the last launch wrote
 
-    def launch(self, col: torch.Tensor, lo: int, hi: int, rows: torch.Tensor | None = None,
+    def launch(self, col, lo: int, hi: int, rows: torch.Tensor | None = None,
                count: torch.Tensor | None = None, signed: bool = False, negate: bool = False) -> None:
-        """Asynchronous on the current stream; nothing is read back.  rows: an int32 row-id list (None: all rows of
+        """Asynchronous on the current stream; nothing is read back.  col: an int32 column, or a PackedColumn, which is
+        filtered in its packed form (lo and hi are values, not codes).  rows: an int32 row-id list (None: all rows of
         col); count: a device int64 of one element, the number of entries of `rows` that count (None: all of them)."""
-        _need(col, torch.int32, "col")
+        packed = col if isinstance(col, PackedColumn) else None
+        if packed is not None:
+            col = _need_packed(packed, "col")  # the packed words; the row count comes from the column itself
+        else:
+            _need(col, torch.int32, "col")
         lo, hi = _bounds(lo, hi, signed)
         if rows is not None:
             _need(rows, torch.int32, "rows")
@@ -174,17 +182,26 @@ class SelectRows:
             raise ValueError("count: given without rows")
         if count is not None and (not count.is_cuda or count.dtype != torch.int64 or count.numel() != 1):
             raise ValueError("count: expected one int64 on the GPU")
-        candidates = col.numel() if rows is None else rows.numel()
+        n_col = col.numel() if packed is None else packed.n_rows
+        candidates = n_col if rows is None else rows.numel()
         if candidates > self.capacity:
             raise ValueError(f"{candidates} candidates, the plan holds {self.capacity}")
         into = 0 if self._last is None else 1 - self._last
         if rows is not None and rows.untyped_storage().data_ptr() == self.rows[into].untyped_storage().data_ptr():
             into = 1 - into  # the list is a view of that buffer: write the other one
-        col_ptr, col_n, list_ptr, count_ptr = col.data_ptr() if col.numel() else None, col.numel(), None, None
+        col_ptr, col_n, list_ptr, count_ptr = col.data_ptr() if n_col else None, n_col, None, None
         if rows is not None and rows.numel():
             list_ptr, count_ptr = rows.data_ptr(), count.data_ptr() if count is not None else None
         elif rows is not None:  # an empty list has no address: the call over no rows at all
             col_ptr, col_n = None, 0
+        if packed is not None:
+            flags = (bitpack_native.SIGNED if signed else 0) | (bitpack_native.NEGATE if negate else 0)
+            _capi.check(bitpack_native.select_range(
+                col_ptr, col_n, packed.width, packed.base, list_ptr, count_ptr, rows.numel() if list_ptr else 0, lo, hi,
+                flags, self.rows[into].data_ptr(), self.counts[into:].data_ptr(), self.ws.data_ptr(), self.ws_bytes,
+                _stream()), "bitpack_select_range_u32")
+            self._last = into
+            return
         flags = (select_native.SIGNED if signed else 0) | (select_native.NEGATE if negate else 0)
         _capi.check(select_native.select_range(
             col_ptr, col_n, list_ptr, count_ptr, rows.numel() if list_ptr else 0, lo, hi, flags,
@@ -192,7 +209,7 @@ class SelectRows:
             "select_range_u32")
         self._last = into
 
-    def refine(self, col: torch.Tensor, lo: int, hi: int, signed: bool = False, negate: bool = False) -> None:
+    def refine(self, col, lo: int, hi: int, signed: bool = False, negate: bool = False) -> None:
         """the rows of the last launch that also pass this predicate on `col`: its output list and its device count are
         the candidates, nothing is read back in between"""
         if self._last is None:
@@ -658,6 +675,12 @@ class Dictionary:
     def status(self) -> int:
         return workspace_status(self.ws)
 
+    def packed_width(self) -> int:
+        """the width at which every code of this dictionary fits (codes are below the capacity), known without a
+        read-back: BitPack(n, d.packed_width()) behind encode is one captured sequence.  DICT_MISS does not fit below 32
+        bits: packing it raises DEV_KEY_RANGE."""
+        return max(1, (self.capacity - 1).bit_length())
+
     def count(self) -> int:
         """the number of distinct values of the last build; synchronises and raises on a device status"""
         self._built("count")
@@ -813,6 +836,175 @@ def join_pairs_columns(build_cols, probe_cols, left_outer: bool = False):
     build_key, _ = _combine_codes(build_codes, cards, device)
     probe_key, _ = _combine_codes(probe_codes, cards, device)
     return join_pairs(build_key, probe_key, left_outer=left_outer, ordered=True)
+
+
+# ---------------------------------------------------------------------------------------------
+# bit-packed columns: pack, unpack, filter on packed codes (host/bitpack.hpp, libdbench.so)
+# ---------------------------------------------------------------------------------------------
+def _width(width) -> int:
+    if isinstance(width, bool) or not isinstance(width, int) or not 1 <= width <= 32:
+        raise ValueError(f"width: expected an int in 1..32, got {width!r}")
+    return width
+
+
+def _base_word(base) -> int:
+    if isinstance(base, bool) or not isinstance(base, int) or not -(1 << 31) <= base < (1 << 32):
+        raise ValueError(f"base: expected an int32 or uint32 value, got {base!r}")
+    return base & 0xFFFFFFFF
+
+
+class PackedColumn:
+    """A column of n_rows 32-bit values held in `width` bits per row (host/bitpack.hpp): row i is base + code i mod 2^32,
+    code i the bits [i * width, i * width + width) of the little-endian bit stream over the int32 words of `packed`, which
+    start on a 16-byte boundary and are padded with zero bits to whole 16-byte chunks."""
+
+    def __init__(self, packed: torch.Tensor, n_rows: int, width: int, base: int = 0):
+        self.width, self.base, self.n_rows = _width(width), _base_word(base), int(n_rows)
+        if not 0 <= self.n_rows < (1 << 32):
+            raise ValueError("n_rows: at most 2^32 - 1 rows")
+        words = bitpack_native.words(self.n_rows, self.width)
+        if not torch.is_tensor(packed) or packed.dtype != torch.int32 or not packed.is_contiguous():
+            raise ValueError("packed: expected a contiguous torch.int32 tensor")
+        if packed.numel() < words:
+            raise ValueError(f"packed: {packed.numel()} words, {self.n_rows} rows of {self.width} bits take {words}")
+        if packed.numel() and packed.data_ptr() % 16:
+            raise ValueError(f"packed: the words must start on a 16-byte boundary (got offset {packed.data_ptr() % 16})")
+        self.packed = packed[:words]
+
+    @property
+    def nbytes(self) -> int:
+        """the bytes of the packed words (a 32-bit column of as many rows takes 4 * n_rows)"""
+        return 4 * self.packed.numel()
+
+    def __len__(self) -> int:
+        return self.n_rows
+
+
+def _need_packed(pc, name: str) -> torch.Tensor:
+    if not isinstance(pc, PackedColumn):
+        raise ValueError(f"{name}: expected a PackedColumn, got {type(pc).__name__}")
+    _need(pc.packed, torch.int32, f"{name}.packed")
+    return pc.packed
+
+
+class BitPack:
+    """Reusable plan that packs int32 columns of up to `capacity` rows at `width` bits over `base`: owns the workspace and
+    the packed words.  The number of rows may be a device count (the count of Dictionary.encode, SelectRows.output()), so
+    encode -> pack is one captured sequence without a read-back.  A row whose code (value - base mod 2^32) does not fit
+    keeps its low bits and raises DEV_KEY_RANGE."""
+
+    def __init__(self, capacity: int, width: int, base: int = 0, device="cuda"):
+        self.capacity, self.width, self.base = int(capacity), _width(width), _base_word(base)
+        self.ws_bytes = bitpack_native.workspace_bytes(self.capacity)
+        if self.ws_bytes == 0:
+            raise ValueError("capacity: at most 2^32 - 1 rows")
+        self.ws = _ws(self.ws_bytes, device)
+        self.packed = torch.zeros(max(bitpack_native.words(self.capacity, self.width), 4), dtype=torch.int32, device=device)
+        self._count = None  # the device count of the last launch (None: all rows of its column)
+        self._rows = None   # the rows of the column of the last launch
+
+    def launch(self, col: torch.Tensor, count: torch.Tensor | None = None) -> None:
+        """Asynchronous on the current stream; nothing is read back.  count: a device int64 of one element, the rows of
+        `col` that count (None: all of them); the words behind the packed form of those rows are not written."""
+        _need(col, torch.int32, "col")
+        _need_count(count, "count")
+        if col.numel() > self.capacity:
+            raise ValueError(f"{col.numel()} rows, the plan holds {self.capacity}")
+        ptr, rows, count_ptr = _column(col, count)
+        _capi.check(bitpack_native.pack(ptr, rows, count_ptr, self.width, self.base, self.packed.data_ptr() if rows else None,
+                                        self.ws.data_ptr(), self.ws_bytes, _stream()), "bitpack_pack_u32")
+        self._count = count if rows else None
+        self._rows = rows
+
+    def status(self) -> int:
+        return workspace_status(self.ws)
+
+    def output(self) -> PackedColumn:
+        """the packed column of the last launch at ALL rows of its input, without synchronising: what select and unpack
+        take inside one captured graph.  Rows behind a device count hold whatever the buffer held before."""
+        if self._rows is None:
+            raise ValueError("output: nothing was launched on this plan")
+        return PackedColumn(self.packed, self._rows, self.width, self.base)
+
+    def result(self, strict: bool = True) -> PackedColumn:
+        """the packed column of the last launch cut to min(count, rows): a view of the plan's words; synchronises.
+        strict: a row that did not fit (DEV_KEY_RANGE) raises; otherwise it holds its code's low bits."""
+        if self._rows is None:
+            raise ValueError("result: nothing was launched on this plan")
+        if strict:
+            _check_status(self.ws, "bitpack_pack_u32")
+        m = self._rows if self._count is None else min(max(int(self._count.item()), 0), self._rows)
+        return PackedColumn(self.packed, m, self.width, self.base)
+
+
+def pack(col: torch.Tensor, width: int | None = None, base: int | None = None, signed: bool = False) -> PackedColumn:
+    """col in `width` bits per row over `base`.  width None: the minimum and maximum come from aggregate_rows (one
+    read-back; ordered as uint32, or as int32 with signed), base = the minimum unless given (it must not exceed it) and
+    width = bit_length(maximum - base), at least 1.  width given: base defaults to 0.  A value that does not fit raises."""
+    _need(col, torch.int32, "col")
+    if base is not None:
+        _base_word(base)
+    if width is None:
+        n, _, least, most = aggregate_rows(col, signed=signed)
+        if base is None:
+            base = least if n else 0
+        elif n and base > least:
+            raise ValueError(f"base: {base} is above the column's minimum {least}")
+        width = max(1, (most - base).bit_length()) if n else 1
+    plan = BitPack(col.numel(), _width(width), _base_word(0 if base is None else base), col.device)
+    plan.launch(col)
+    return plan.result()
+
+
+def unpack(pc: PackedColumn, rows: torch.Tensor | None = None, count: torch.Tensor | None = None, outer: bool = False,
+           fill: int = 0, out: torch.Tensor | None = None, ws: torch.Tensor | None = None) -> torch.Tensor:
+    """The values of a packed column: all rows (rows None), or pc[rows[i]] for every entry of an int32 row-id list, with
+    the rules of take: a row id outside the column gives `fill` and raises; with outer the id -1 gives `fill` silently.
+    count: a device int64 of one element, the entries of `rows` that count.  Without ws the call synchronises, raises on
+    a device status and returns the values cut to the count; with ws (256 bytes or more, which then holds the status
+    word) it is asynchronous, nothing is read back, and `out` comes back in full."""
+    if not isinstance(pc, PackedColumn):
+        raise ValueError(f"pc: expected a PackedColumn, got {type(pc).__name__}")
+    fill = _fill_word(fill)
+    packed = _need_packed(pc, "pc")
+    if rows is None and count is not None:
+        raise ValueError("count: given without rows")
+    if rows is not None:
+        _need(rows, torch.int32, "rows")
+    _need_count(count, "count")
+    entries = pc.n_rows if rows is None else rows.numel()
+    if out is None:
+        out = torch.empty(entries, dtype=torch.int32, device=packed.device)
+    else:
+        _need(out, torch.int32, "out")
+        if out.numel() != entries:
+            raise ValueError(f"out: {out.numel()} rows, expected {entries}")
+    eager = ws is None
+    if eager:
+        ws = _ws(bitpack_native.workspace_bytes(0), packed.device)
+    list_ptr, listed, count_ptr = _column(rows, count)
+    if rows is None or listed:  # (an empty list has no address: nothing to do)
+        _capi.check(bitpack_native.unpack(packed.data_ptr() if pc.n_rows else None, pc.n_rows, pc.width, pc.base, list_ptr,
+                                          count_ptr, listed, bitpack_native.OUTER if outer else 0, fill,
+                                          out.data_ptr() if entries else None, ws.data_ptr(), ws.numel(), _stream()),
+                    "bitpack_unpack_u32")
+    if not eager:
+        return out
+    _check_status(ws, "bitpack_unpack_u32")
+    return out if count is None or not listed else out[: min(max(int(count.item()), 0), entries)]
+
+
+def select_range_packed(pc: PackedColumn, lo: int, hi: int, rows: torch.Tensor | None = None, signed: bool = False,
+                        negate: bool = False) -> torch.Tensor:
+    """select_range on a packed column, filtered in its packed form: row ids r with lo <= pc[r] <= hi (lo and hi are
+    values, base + code), with the same rules for rows, signed and negate."""
+    _bounds(lo, hi, signed)
+    packed = _need_packed(pc, "pc")
+    if rows is not None:
+        _need(rows, torch.int32, "rows")
+    plan = SelectRows(pc.n_rows if rows is None else rows.numel(), packed.device)
+    plan.launch(pc, lo, hi, rows=rows, signed=signed, negate=negate)
+    return plan.result()
 
 
 # ---------------------------------------------------------------------------------------------

@@ -115,6 +115,15 @@ the contract numbers come from bench.py.
                   spread empty slot (DBHIP_SLAB_SPREAD 0 / default / 1); every build checked
   xscan [lg]      exclusive scan of 2^lg uint32, aligned (one launch) and offset by one element (three launches)
   graph [lg]      direct launches vs hipGraph replay of sort and join at 2^14..2^20 rows, or 2^lg alone (host wall clock)
+  bitpack [lg]    bit-packed columns (ops.BitPack, ops.unpack, ops.SelectRows on a PackedColumn: host/bitpack.hpp) at 2^lg rows
+                  (default 26; one process per size: 20, 24, 26), same protocol as sorted-search (legs alternating, REPS
+                  repetitions of a median of 5, HIP events, every leg's result checked), widths 4, 8, 12, 16, 24, 32
+                  (BITPACK_WIDTHS).  select: the dense range filter on the packed codes against dbench_select_range_u32 on the
+                  decoded 32-bit column at 0 / 1 / 50 / 100 % kept, with the share of n width / 8 + n / 4 + 4 m bytes at
+                  8 TB/s; the floor (this code's slowest repetition against the plain select's fastest) applies at widths up
+                  to 16, wider ones are reported.  Report only: pack and the dense unpack against their bytes and against
+                  torch.clone of the 32-bit column; unpack through lists of 1 % and 50 % of the rows, ascending and shuffled,
+                  against dbench_take_u32 on the decoded column.  BITPACK_PARTS=select,pack,unpack,take picks parts
   launch-join [lg] / launch-sort [lg] / launch-all
                   a few untimed calls and nothing else: the program to put behind `rocprofv3 --kernel-trace --stats` or
                   `--pmc` (tools/pmc_kernel_counters.sh); tools/prof_show.py prints the tables
@@ -1073,6 +1082,74 @@ def dict_encoding(lg):
             del col
 
 
+def bitpack(lg):
+    """BITPACK_PARTS=select,pack,unpack,take picks parts; BITPACK_WIDTHS=4,8,... picks widths"""
+    reps = int(os.environ.get("REPS", "5"))
+    parts = os.environ.get("BITPACK_PARTS", "select,pack,unpack,take").split(",")
+    widths = [int(w) for w in os.environ.get("BITPACK_WIDTHS", "4,8,12,16,24,32").split(",")]
+    n = 1 << (lg or 26)
+    us = lambda nbytes: nbytes / 8e12 * 1e6  # noqa: E731
+
+    def run(name, legs_fn, ok, floor_of, model_us, report=None):
+        legs = {leg: [] for leg in legs_fn}
+        for _ in range(reps):  # alternating
+            for leg, fn in legs_fn.items():
+                legs[leg].append(median(times(fn, 5)))
+        extra = ""
+        if report:  # no floor: the ratio and the bytes all the same
+            mine, other = (median(sorted(legs[x])) for x in report)
+            extra = f"  (no floor) x{other / mine:5.2f}  bytes at 8 TB/s {model_us:7.1f} us = {100 * model_us / mine:3.0f} %"
+        _merge_row(name, legs, ok, floor_of, model_us, extra)
+
+    g = torch.Generator(device="cuda")
+    g.manual_seed(9)
+    perm = torch.randperm(n, device="cuda", generator=g).to(torch.int32)
+    for width in widths:
+        codes = ops.gen_uniform_u32(n, 70 + width, 0, 2**width - 1)  # the decoded column; base 0
+        packer = ops.BitPack(n, width)
+        packer.launch(codes)
+        pc = packer.result()
+        if "select" in parts:
+            packed_plan, plain_plan = ops.SelectRows(n), ops.SelectRows(n)
+            for share in (0, 0.01, 0.5, 1.0):
+                lo, hi = (1, 0) if share == 0 else (0, 2**32 - 1) if share == 1.0 else (0, max(int(share * 2**width) - 1, 0))
+                mine = lambda: packed_plan.launch(pc, lo, hi)  # noqa: E731
+                plain = lambda: plain_plan.launch(codes, lo, hi)  # noqa: E731
+                mine(), plain()
+                ok = torch.equal(packed_plan.result(), plain_plan.result())
+                m = packed_plan.count()
+                floor = width <= 16
+                run(f"select n=2^{lg or 26} width {width:2d} kept {100 * m / n:5.1f} %", {"packed": mine, "plain": plain}, ok,
+                    ("packed", "plain") if floor else None, us(n * width / 8 + n / 4 + 4 * m), None if floor else ("packed", "plain"))
+            del packed_plan, plain_plan
+        if "pack" in parts:
+            ok = torch.equal(ops.unpack(pc), codes)
+            run(f"pack n=2^{lg or 26} width {width:2d}", {"pack": lambda: packer.launch(codes), "clone": lambda: torch.clone(codes)},
+                ok, None, us(4 * n + n * width / 8), ("pack", "clone"))
+        if "unpack" in parts:
+            out, ws = torch.empty(n, dtype=torch.int32, device="cuda"), torch.zeros(256, dtype=torch.uint8, device="cuda")
+            ops.unpack(pc, out=out, ws=ws)
+            ok = torch.equal(out, codes) and ops.workspace_status(ws) == 0
+            run(f"unpack n=2^{lg or 26} width {width:2d}", {"unpack": lambda: ops.unpack(pc, out=out, ws=ws), "clone": lambda: torch.clone(codes)},
+                ok, None, us(4 * n + n * width / 8), ("unpack", "clone"))
+            del out
+        if "take" in parts:
+            for share in (0.01, 0.5):
+                m = int(share * n)
+                for order, rows in (("ascending", torch.sort(perm[:m]).values.contiguous()), ("shuffled", perm[:m].contiguous())):
+                    out, ws = torch.empty(m, dtype=torch.int32, device="cuda"), torch.zeros(256, dtype=torch.uint8, device="cuda")
+                    taker = ops.TakeRows(m, 1)
+                    mine = lambda: ops.unpack(pc, rows, out=out, ws=ws)  # noqa: E731
+                    plain = lambda: taker.launch(codes, rows)  # noqa: E731
+                    mine(), plain()
+                    ok = torch.equal(out, taker.result()[0]) and ops.workspace_status(ws) == 0
+                    lines = torch.unique(rows >> 5).numel()  # 128-byte lines of the 32-bit column the list touches
+                    run(f"take n=2^{lg or 26} width {width:2d} m={m} {order}", {"unpack": mine, "take": plain}, ok, None,
+                        us(8 * m + 128 * lines * width / 32), ("unpack", "take"))
+                    del out, taker, rows
+        del codes, packer, pc
+
+
 def launch_sort_pairs(lg):
     n = 1 << (lg or 24)
     keys0 = ops.gen_uniform_u32(n, 42, 0, 2**32 - 1)
@@ -1776,7 +1853,7 @@ MODES = {"radix": radix, "ramp": ramp, "radix-idle": radix_idle, "radix-stream":
          "join-pairs": join_pairs, "launch-join-pairs": launch_join_pairs, "topk": topk, "launch-topk": launch_topk,
          "groupby-sorted": groupby_sorted, "launch-groupby-sorted": launch_groupby_sorted,
          "window": window, "launch-window": launch_window, "sorted-search": sorted_search, "range-join": range_join,
-         "selection": selection, "merge": merge, "take": take, "dict": dict_encoding}
+         "selection": selection, "merge": merge, "take": take, "dict": dict_encoding, "bitpack": bitpack}
 
 if __name__ == "__main__":
     if len(sys.argv) < 2 or sys.argv[1] not in MODES:
