@@ -4,6 +4,8 @@
 //            fill_async, launch_status
 //   device:  lane_id, mbcnt, wg_barrier_lds_only, the wave scan and reductions (add, 64-bit add, min, max),
 //            block_exclusive_scan, the hashes (mix64, fmix32, murmur3_x86_32_u32)
+// The row-id operators of host/ share more on top of this: host/rowlist.hpp (begin_call, the one scan of counts to
+// positions, clamped_count, load_ragged, the range predicate) and host/call_checks.hpp (overlap, words_past_16, fits_32).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stddef.h>

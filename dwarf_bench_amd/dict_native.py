@@ -6,12 +6,8 @@ header's comment.  No fallback: a missing library raises."""
 from __future__ import annotations
 
 import ctypes as C
-from pathlib import Path
 
-from . import _capi
-
-_LIB = Path(__file__).resolve().parent / "_lib" / "libdbench.so"
-_lib = None
+from ._dbench import lib  # noqa: F401  the one handle of libdbench.so, every family's ENTRY_POINTS bound
 
 # the #defines of dict_encode.hpp (tests/test_dict_host.py holds the two together)
 SIGNED = 1
@@ -25,21 +21,6 @@ ENTRY_POINTS = {
     "dbench_dict_encode_u32": (_int, [_vp, _sz, _vp, _vp, _vp, _vp, _sz, _vp]),
     "dbench_dict_combine_u32": (_int, [_vp, _vp, _sz, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
 }
-
-
-def lib() -> C.CDLL:
-    global _lib
-    if _lib is None:
-        if not _LIB.exists():
-            raise _capi.DbhipError(f"{_LIB} is missing: run `python -m dwarf_bench_amd.build`")
-        _capi.lib()  # libdbhip.so first (RTLD_GLOBAL), same HIP runtime as torch
-        h = C.CDLL(str(_LIB), mode=C.RTLD_GLOBAL)
-        for name, (res, args) in ENTRY_POINTS.items():
-            fn = getattr(h, name)  # AttributeError if the .so does not export the symbol
-            fn.restype = res
-            fn.argtypes = args
-        _lib = h
-    return _lib
 
 
 def slots(capacity: int) -> int:

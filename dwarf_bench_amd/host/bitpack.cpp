@@ -18,19 +18,18 @@
 //           codes that reach into it (bitpack_group_word), and stores 16 bytes.  One lane per output word, no atomics.
 //   unpack  dense: stage, extract, add the base, store.  Through a list: a lane loads its row id, bounds-checks it and
 //           gathers the one or two words of the code from global memory (row 0 stands in for an id that does not count).
-//   select  mark / scan / write as in select_rows.cpp, with the mask layout above.  The dense mark kernel is the only
-//           reader of the packed column; the decoded column never exists.
+//   select  mark / scan / write as in select_rows.cpp, with the mask layout above; the predicate and the scan are the
+//           same text (rowlist.hpp).  The dense mark kernel is the only reader of the packed column; the decoded column
+//           never exists.
 #include "bitpack.hpp"
 
 #include <type_traits>
 
 #include "bitpack_layout.hpp"
-#include "dbhip_common.hpp"
+#include "rowlist.hpp"
 
 namespace {
 using namespace dbhip;
-
-typedef unsigned long long u64;
 
 constexpr unsigned kBpSegment = DBENCH_BITPACK_SEGMENT_ROWS;
 constexpr unsigned kBpTile = DBENCH_BITPACK_TILE_ROWS;
@@ -44,19 +43,9 @@ constexpr int kPackThreads = kPackWaves * kWave;
 constexpr int kPackLoads = kBpTile / kWave;          // rows of a lane
 constexpr unsigned kPackGroups = kBpTile / 32;       // groups of a tile: x width = its output words
 constexpr unsigned kPackStride = 33;                 // LDS words per group of 32 codes
-constexpr int kBpScanThreads = 256;
 constexpr int kBpAhead = 8;  // steps of the mark kernels whose loads are in flight together
 static_assert(kBpSteps == kWave && kBpSteps % kBpAhead == 0, "a lane keeps one mask word of its wave's segment");
 static_assert(kBpSegGroups % 4 == 0 && kPackGroups % 4 == 0, "segments and tiles start on a 16-byte chunk at any width");
-
-__device__ __forceinline__ size_t clamped_count(const u64 *count, size_t capacity) {
-  size_t m = capacity;
-  if (count) {
-    const u64 given = *count;
-    if (given < m) m = static_cast<size_t>(given);
-  }
-  return m;
-}
 
 // what one wave wrote to its piece of LDS is visible to all its lanes behind this
 __device__ __forceinline__ void wave_lds_sync() {
@@ -92,16 +81,6 @@ __device__ __forceinline__ void stage_words(const unsigned *__restrict__ packed,
     }
   }
   wave_lds_sync();
-}
-
-struct BpPred {
-  unsigned flip, lo, hi;  // x is inside iff lo <= (x ^ flip) <= hi, lo and hi already flipped (0x80000000 for int32)
-  bool negate;
-};
-
-__device__ __forceinline__ bool bp_keep(unsigned x, const BpPred &p) {
-  const unsigned y = x ^ p.flip;
-  return (y >= p.lo && y <= p.hi) != p.negate;
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -208,7 +187,7 @@ template <bool kList>
 __global__ __launch_bounds__(kBpThreads) void bp_mark_kernel(const unsigned *__restrict__ packed, unsigned n_rows,
                                                              unsigned width, unsigned base,
                                                              const unsigned *__restrict__ rows, size_t m_host,
-                                                             const u64 *in_count, BpPred p, unsigned *status,
+                                                             const u64 *in_count, RangePred p, unsigned *status,
                                                              unsigned *__restrict__ cnt, u64 *__restrict__ masks,
                                                              size_t segments) {
   extern __shared__ __attribute__((aligned(16))) unsigned s_dyn[];
@@ -236,7 +215,7 @@ __global__ __launch_bounds__(kBpThreads) void bp_mark_kernel(const unsigned *__r
 #pragma unroll
         for (int k = 0; k < kBpAhead; ++k) {
           const bool valid = decltype(whole)::value || (j0 + k) * kWave + lane < here;
-          const u64 b = __ballot(valid && bp_keep(x[k], p));
+          const u64 b = __ballot(valid && range_keep(x[k], p));
           total += static_cast<unsigned>(__popcll(b));
           if (lane == static_cast<unsigned>(j0 + k)) mine = b;
         }
@@ -268,7 +247,7 @@ __global__ __launch_bounds__(kBpThreads) void bp_mark_kernel(const unsigned *__r
           const unsigned i = (j0 + k) * kWave + lane;
           const bool valid = i < here, inside = r[k] < n_rows;
           bad = bad || (valid && !inside);
-          const u64 b = __ballot(valid && inside && bp_keep(x[k], p));
+          const u64 b = __ballot(valid && inside && range_keep(x[k], p));
           total += static_cast<unsigned>(__popcll(b));
           if (lane == static_cast<unsigned>(j0 + k)) mine = b;
         }
@@ -278,29 +257,6 @@ __global__ __launch_bounds__(kBpThreads) void bp_mark_kernel(const unsigned *__r
   }
   masks[seg * kBpSteps + lane] = mine;
   if (lane == 0) cnt[seg] = total;
-}
-
-// one workgroup: cnt[segment] -> pos[segment] = matches in front of the segment; *out_count = all matches.
-// Both arrays are padded to 256 bytes, so a thread's four entries are always inside them.
-__global__ __launch_bounds__(kBpScanThreads) void bp_scan_kernel(const unsigned *__restrict__ cnt, unsigned *__restrict__ pos,
-                                                                 size_t segments, u64 *out_count) {
-  __shared__ unsigned s_wsum[kBpScanThreads / kWave];
-  unsigned run = 0;  // total of the rounds so far (the same in every thread)
-  for (size_t at = 0; at < segments; at += 4 * kBpScanThreads) {
-    const size_t i = at + 4 * threadIdx.x;
-    u32x4 c = {0u, 0u, 0u, 0u};
-    if (i < segments) {
-      c = *reinterpret_cast<const u32x4 *>(cnt + i);
-      if (i + 1 >= segments) c.y = 0u;
-      if (i + 2 >= segments) c.z = 0u;
-      if (i + 3 >= segments) c.w = 0u;
-    }
-    unsigned round_total;
-    const unsigned head = run + block_exclusive_scan<kBpScanThreads>(c.x + c.y + c.z + c.w, s_wsum, round_total);
-    if (i < segments) *reinterpret_cast<u32x4 *>(pos + i) = u32x4{head, head + c.x, head + c.x + c.y, head + c.x + c.y + c.z};
-    run += round_total;
-  }
-  if (threadIdx.x == 0) *out_count = run;
 }
 
 // a wave writes its segment's kept row ids, in candidate order, from pos[segment] on
@@ -337,15 +293,7 @@ __global__ __launch_bounds__(kBpThreads) void bp_write_kernel(const unsigned *__
   }
 }
 
-bool overlap(const void *p, size_t p_bytes, const void *q, size_t q_bytes) {
-  if (!p || !q || !p_bytes || !q_bytes) return false;
-  const uintptr_t a = reinterpret_cast<uintptr_t>(p), b = reinterpret_cast<uintptr_t>(q);
-  return a < b + q_bytes && b < a + p_bytes;
-}
-
 bool width_ok(unsigned width) { return width >= 1 && width <= 32; }
-bool size_ok(size_t n) { return n < (1ull << 32); }
-uintptr_t addr(const void *p) { return reinterpret_cast<uintptr_t>(p); }
 size_t lds_bytes(unsigned width) { return sizeof(unsigned) * kBpWaves * (kBpSegGroups * width + kBpPad); }  // at most 32 KiB + 32
 
 }  // namespace
@@ -355,26 +303,21 @@ extern "C" size_t dbench_bitpack_words(size_t n_rows, unsigned width) {
 }
 
 extern "C" size_t dbench_bitpack_workspace_bytes(size_t capacity) {
-  if (!size_ok(capacity)) return 0;
+  if (!fits_32(capacity)) return 0;
   return static_cast<size_t>(bitpack_layout(capacity).total);
 }
 
 extern "C" int dbench_bitpack_pack_u32(const uint32_t *col, size_t capacity, const uint64_t *count, unsigned width,
                                        uint32_t base, uint32_t *out_packed, void *workspace, size_t workspace_bytes,
                                        void *stream) {
-  if (!width_ok(width) || !size_ok(capacity)) return DBHIP_EINVAL;
+  if (!width_ok(width) || !fits_32(capacity)) return DBHIP_EINVAL;
   if (capacity && (!col || !out_packed)) return DBHIP_EINVAL;
   if ((addr(col) & 3u) || (addr(out_packed) & 15u) || (addr(count) & 7u)) return DBHIP_EINVAL;
   const size_t out_bytes = 4 * static_cast<size_t>(bitpack_words(capacity, width));
   if (overlap(out_packed, out_bytes, col, 4 * capacity) || overlap(out_packed, out_bytes, count, 8)) return DBHIP_EINVAL;
-  if (!ws_ok(workspace, workspace_bytes, static_cast<size_t>(bitpack_layout(0).total))) return DBHIP_EWORKSPACE;
-  const DeviceInfo &dev = current_device_info();
-  if (!dev.ok) return DBHIP_ENODEVICE;
-
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  // the status word is cleared by a launch of its own, in front of the one that can raise it
-  const hipError_t e = fill_async(workspace, 0, kWsHeader, s);
-  if (e != hipSuccess) return static_cast<int>(e);
+  const int rc = begin_call(workspace, workspace_bytes, static_cast<size_t>(bitpack_layout(0).total), s);
+  if (rc != DBHIP_OK) return rc;
   if (!capacity) return launch_status();
   const size_t tiles = (capacity + kBpTile - 1) / kBpTile;
   const unsigned grid = static_cast<unsigned>((tiles + kPackWaves - 1) / kPackWaves);
@@ -389,7 +332,7 @@ extern "C" int dbench_bitpack_unpack_u32(const uint32_t *packed, size_t n_rows, 
                                          void *stream) {
   if (!width_ok(width) || (flags & ~DBENCH_BITPACK_OUTER)) return DBHIP_EINVAL;
   const bool list = rows != nullptr;
-  if (!size_ok(n_rows) || (list && !size_ok(capacity))) return DBHIP_EINVAL;  // 32-bit row ids and positions
+  if (!fits_32(n_rows) || (list && !fits_32(capacity))) return DBHIP_EINVAL;  // 32-bit row ids and positions
   if (count && !rows) return DBHIP_EINVAL;
   const size_t entries = list ? capacity : n_rows;
   if ((n_rows && entries && !packed) || (entries && !out)) return DBHIP_EINVAL;
@@ -398,15 +341,11 @@ extern "C" int dbench_bitpack_unpack_u32(const uint32_t *packed, size_t n_rows, 
   if (overlap(out, 4 * entries, packed, packed_bytes) || overlap(out, 4 * entries, rows, 4 * entries) ||
       overlap(out, 4 * entries, count, 8))
     return DBHIP_EINVAL;
-  if (!ws_ok(workspace, workspace_bytes, static_cast<size_t>(bitpack_layout(0).total))) return DBHIP_EWORKSPACE;
-  const DeviceInfo &dev = current_device_info();
-  if (!dev.ok) return DBHIP_ENODEVICE;
-
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  unsigned *status = static_cast<unsigned *>(workspace);
-  const hipError_t e = fill_async(workspace, 0, kWsHeader, s);
-  if (e != hipSuccess) return static_cast<int>(e);
+  const int rc = begin_call(workspace, workspace_bytes, static_cast<size_t>(bitpack_layout(0).total), s);
+  if (rc != DBHIP_OK) return rc;
   if (!entries) return launch_status();
+  unsigned *status = static_cast<unsigned *>(workspace);
   const size_t segments = (entries + kBpSegment - 1) / kBpSegment;
   const unsigned grid = static_cast<unsigned>((segments + kBpWaves - 1) / kBpWaves);
   const unsigned n = static_cast<unsigned>(n_rows);
@@ -425,7 +364,7 @@ extern "C" int dbench_bitpack_select_range_u32(const uint32_t *packed, size_t n_
                                                uint32_t lo, uint32_t hi, int flags, uint32_t *out_rows, uint64_t *out_count,
                                                void *workspace, size_t workspace_bytes, void *stream) {
   if (!width_ok(width) || (flags & ~(DBENCH_BITPACK_SIGNED | DBENCH_BITPACK_NEGATE))) return DBHIP_EINVAL;
-  if (!size_ok(n_rows) || !size_ok(in_capacity)) return DBHIP_EINVAL;  // 32-bit row ids and counts
+  if (!fits_32(n_rows) || !fits_32(in_capacity)) return DBHIP_EINVAL;  // 32-bit row ids and counts
   if ((n_rows && !packed) || !out_count || (in_count && !in_rows)) return DBHIP_EINVAL;
   if ((addr(packed) & 15u) || ((addr(in_rows) | addr(out_rows)) & 3u) || ((addr(in_count) | addr(out_count)) & 7u))
     return DBHIP_EINVAL;
@@ -435,23 +374,20 @@ extern "C" int dbench_bitpack_select_range_u32(const uint32_t *packed, size_t n_
   if (overlap(out_rows, 4 * candidates, packed, packed_bytes) || overlap(out_rows, 4 * candidates, in_rows, 4 * in_capacity))
     return DBHIP_EINVAL;
   const BitpackLayout l = bitpack_layout(candidates);
-  if (!ws_ok(workspace, workspace_bytes, static_cast<size_t>(l.total))) return DBHIP_EWORKSPACE;
-  const DeviceInfo &dev = current_device_info();
-  if (!dev.ok) return DBHIP_ENODEVICE;
-
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  const int rc = begin_call(workspace, workspace_bytes, static_cast<size_t>(l.total), s);
+  if (rc != DBHIP_OK) return rc;
+
   char *ws = static_cast<char *>(workspace);
   unsigned *status = reinterpret_cast<unsigned *>(ws);
   unsigned *cnt = reinterpret_cast<unsigned *>(ws + l.cnt);
   unsigned *pos = reinterpret_cast<unsigned *>(ws + l.pos);
   u64 *masks = reinterpret_cast<u64 *>(ws + l.masks);
-  const hipError_t e = fill_async(workspace, 0, kWsHeader, s);
-  if (e != hipSuccess) return static_cast<int>(e);
 
   const size_t segments = static_cast<size_t>(l.segments);
   const unsigned grid = static_cast<unsigned>((segments + kBpWaves - 1) / kBpWaves);
   const unsigned flip = (flags & DBENCH_BITPACK_SIGNED) ? 0x80000000u : 0u;
-  const BpPred p{flip, lo ^ flip, hi ^ flip, (flags & DBENCH_BITPACK_NEGATE) != 0};
+  const RangePred p{flip, lo ^ flip, hi ^ flip, (flags & DBENCH_BITPACK_NEGATE) != 0};
   const unsigned n = static_cast<unsigned>(n_rows);
   if (segments) {
     if (list)
@@ -462,7 +398,8 @@ extern "C" int dbench_bitpack_select_range_u32(const uint32_t *packed, size_t n_
                          static_cast<const unsigned *>(nullptr), n_rows, static_cast<const u64 *>(nullptr), p, status, cnt,
                          masks, segments);
   }
-  hipLaunchKernelGGL(bp_scan_kernel, dim3(1), dim3(kBpScanThreads), 0, s, cnt, pos, segments, reinterpret_cast<u64 *>(out_count));
+  // (the write kernels stop at `candidates` as well)
+  launch_rowlist_scan(cnt, pos, segments, candidates, reinterpret_cast<u64 *>(out_count), s);
   if (segments && out_rows) {
     if (list)
       hipLaunchKernelGGL((bp_write_kernel<true>), dim3(grid), dim3(kBpThreads), 0, s, in_rows, cnt, pos, masks, segments,

@@ -1,11 +1,11 @@
 // dict_encode.cpp — dictionary encoding on gfx950 (dict_encode.hpp holds the contract, dict_layout.hpp the hash, the
 // workspace regions and the two probe loops, which the kernels below run on global and LDS pointers).
 //
-// The load shape is that of take_rows.cpp.  Positions are counted from the 16-byte boundary in front of the column: row i
-// sits at v = i + a, a = 0..3 words, so every 16-byte load of rows is aligned whatever the pointer's alignment; a lane
-// holds four consecutive rows, and the groups that straddle the ends of the column are handled word by word.  An output
-// that sits at the same distance from a 16-byte boundary as the column is written with 16-byte stores, any other word
-// by word.  Nothing outside the arrays is touched.
+// The load shape is that of take_rows.cpp (the positions and the device count are rowlist.hpp's).  Positions are
+// counted from the 16-byte boundary in front of the column: row i sits at v = i + a, a = 0..3 words, so every 16-byte
+// load of rows is aligned whatever the pointer's alignment; a lane holds four consecutive rows, and the groups that
+// straddle the ends of the column are handled word by word.  An output that sits at the same distance from a 16-byte
+// boundary as the column is written with 16-byte stores, any other word by word.  Nothing outside the arrays is touched.
 //   build    clear -> insert -> compact -> dbhip_radix_sort -> finalize, five dependent steps, no workgroup waits for
 //            another.  insert: a lane drops a row that repeats the row before it, then asks the workgroup's LDS filter
 //            (1024 entries, (valid, key), direct mapped by the key's hash): a key the workgroup has inserted costs one LDS
@@ -19,13 +19,11 @@
 //   combine  one streaming kernel, four rows per lane.
 #include "dict_encode.hpp"
 
-#include "dbhip_common.hpp"
 #include "dict_layout.hpp"
+#include "rowlist.hpp"
 
 namespace {
 using namespace dbhip;
-
-typedef unsigned long long u64;
 
 constexpr unsigned kDictMagic = 0x44494354u;  // "DICT": a header some build of this file wrote
 constexpr u64 kEmptySlot = static_cast<u64>(DBENCH_DICT_EMPTY) << 32;  // (key 0, code EMPTY)
@@ -73,16 +71,8 @@ struct LiveSlots {
   }
 };
 
-// m = min(*count, n), read on the device
-__device__ __forceinline__ size_t clamped_count(const u64 *count, size_t n) {
-  size_t m = n;
-  if (count) {
-    const u64 given = *count;
-    if (given < m) m = static_cast<size_t>(given);
-  }
-  return m;
-}
-
+// (valid_four, load_four and store_four are not rowlist.hpp's load_ragged: they carry a `vec` flag, and the validity is
+// computed once for a load and a store)
 // bit q: position v0 + q holds a row, that is, lies in [a, vend)
 __device__ __forceinline__ unsigned valid_four(unsigned a, size_t v0, size_t vend) {
   if (v0 >= a && v0 + 4 <= vend) return 0xfu;
@@ -340,14 +330,6 @@ __global__ __launch_bounds__(kCombThreads) void dict_combine_kernel(const unsign
   store_four(out, a, v0, valid, vec_out, x);
 }
 
-bool overlap(const void *p, size_t p_bytes, const void *q, size_t q_bytes) {
-  if (!p || !q || !p_bytes || !q_bytes) return false;
-  const uintptr_t a = reinterpret_cast<uintptr_t>(p), b = reinterpret_cast<uintptr_t>(q);
-  return a < b + q_bytes && b < a + p_bytes;
-}
-
-unsigned words_past_16(const void *p) { return static_cast<unsigned>((reinterpret_cast<uintptr_t>(p) >> 2) & 3u); }
-
 bool capacity_ok(size_t capacity) { return capacity >= 1 && capacity < (1ull << 31); }
 
 DictLayout layout_of(size_t capacity) { return dict_layout(capacity, dbhip_radix_sort_workspace_bytes(capacity, 8)); }
@@ -363,20 +345,18 @@ extern "C" int dbench_dict_build_u32(const uint32_t *col, size_t n, const uint64
                                      uint32_t *out_keys, uint64_t *out_count, void *workspace, size_t workspace_bytes,
                                      void *stream) {
   if (flags & ~DBENCH_DICT_SIGNED) return DBHIP_EINVAL;
-  if (!capacity_ok(capacity) || n >= (1ull << 32)) return DBHIP_EINVAL;
+  if (!capacity_ok(capacity) || !fits_32(n)) return DBHIP_EINVAL;
   if ((n && !col) || !out_keys || !out_count) return DBHIP_EINVAL;
-  const uintptr_t words = reinterpret_cast<uintptr_t>(col) | reinterpret_cast<uintptr_t>(out_keys);
-  const uintptr_t longs = reinterpret_cast<uintptr_t>(count) | reinterpret_cast<uintptr_t>(out_count);
-  if ((words & 3u) || (longs & 7u)) return DBHIP_EINVAL;
+  if (((addr(col) | addr(out_keys)) & 3u) || ((addr(count) | addr(out_count)) & 7u)) return DBHIP_EINVAL;
   if (overlap(out_keys, 4 * capacity, col, 4 * n) || overlap(out_keys, 4 * capacity, count, 8) ||
       overlap(out_count, 8, col, 4 * n) || overlap(out_count, 8, count, 8) || overlap(out_count, 8, out_keys, 4 * capacity))
     return DBHIP_EINVAL;
   const DictLayout l = layout_of(capacity);
-  if (!ws_ok(workspace, workspace_bytes, l.total)) return DBHIP_EWORKSPACE;
-  const DeviceInfo &dev = current_device_info();
-  if (!dev.ok) return DBHIP_ENODEVICE;
-
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  const int ready = begin_call(workspace, workspace_bytes, l.total, s, false);  // dict_clear_kernel writes the header
+  if (ready != DBHIP_OK) return ready;
+  const DeviceInfo &dev = current_device_info();
+
   char *ws = static_cast<char *>(workspace);
   DictHeader *hdr = reinterpret_cast<DictHeader *>(ws);
   u64 *table = reinterpret_cast<u64 *>(ws + l.table);
@@ -411,19 +391,18 @@ extern "C" int dbench_dict_build_u32(const uint32_t *col, size_t n, const uint64
 
 extern "C" int dbench_dict_encode_u32(const uint32_t *col, size_t n, const uint64_t *count, uint32_t *out_codes,
                                       uint64_t *out_misses, const void *workspace, size_t workspace_bytes, void *stream) {
-  if (n >= (1ull << 32)) return DBHIP_EINVAL;
+  if (!fits_32(n)) return DBHIP_EINVAL;
   if (n && (!col || !out_codes)) return DBHIP_EINVAL;
-  const uintptr_t words = reinterpret_cast<uintptr_t>(col) | reinterpret_cast<uintptr_t>(out_codes);
-  const uintptr_t longs = reinterpret_cast<uintptr_t>(count) | reinterpret_cast<uintptr_t>(out_misses);
-  if ((words & 3u) || (longs & 7u)) return DBHIP_EINVAL;
+  if (((addr(col) | addr(out_codes)) & 3u) || ((addr(count) | addr(out_misses)) & 7u)) return DBHIP_EINVAL;
   if (overlap(out_codes, 4 * n, col, 4 * n) || overlap(out_codes, 4 * n, count, 8) || overlap(out_codes, 4 * n, out_misses, 8) ||
       overlap(out_misses, 8, col, 4 * n) || overlap(out_misses, 8, count, 8))
     return DBHIP_EINVAL;
-  if (!ws_ok(workspace, workspace_bytes, dbench_dict_workspace_bytes(1))) return DBHIP_EWORKSPACE;
-  const DeviceInfo &dev = current_device_info();
-  if (!dev.ok) return DBHIP_ENODEVICE;
-
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  // (the workspace is the dictionary: read, never cleared)
+  const int rc = begin_call(const_cast<void *>(workspace), workspace_bytes, dbench_dict_workspace_bytes(1), s, false);
+  if (rc != DBHIP_OK) return rc;
+  const DeviceInfo &dev = current_device_info();
+
   if (out_misses) {
     const hipError_t e = fill_async(out_misses, 0, 8, s);
     if (e != hipSuccess) return static_cast<int>(e);
@@ -440,22 +419,16 @@ extern "C" int dbench_dict_encode_u32(const uint32_t *col, size_t n, const uint6
 extern "C" int dbench_dict_combine_u32(const uint32_t *outer, const uint32_t *inner, size_t n, const uint64_t *count,
                                        const uint64_t *outer_card, const uint64_t *inner_card, uint32_t *out, void *workspace,
                                        size_t workspace_bytes, void *stream) {
-  if (n >= (1ull << 32)) return DBHIP_EINVAL;
+  if (!fits_32(n)) return DBHIP_EINVAL;
   if ((n && (!outer || !inner || !out)) || !outer_card || !inner_card) return DBHIP_EINVAL;
-  const uintptr_t words = reinterpret_cast<uintptr_t>(outer) | reinterpret_cast<uintptr_t>(inner) | reinterpret_cast<uintptr_t>(out);
-  const uintptr_t longs = reinterpret_cast<uintptr_t>(count) | reinterpret_cast<uintptr_t>(outer_card) |
-                          reinterpret_cast<uintptr_t>(inner_card);
-  if ((words & 3u) || (longs & 7u)) return DBHIP_EINVAL;
+  if (((addr(outer) | addr(inner) | addr(out)) & 3u) || ((addr(count) | addr(outer_card) | addr(inner_card)) & 7u))
+    return DBHIP_EINVAL;
   if ((out != outer && overlap(out, 4 * n, outer, 4 * n)) || overlap(out, 4 * n, inner, 4 * n) || overlap(out, 4 * n, count, 8) ||
       overlap(out, 4 * n, outer_card, 8) || overlap(out, 4 * n, inner_card, 8))
     return DBHIP_EINVAL;
-  if (!ws_ok(workspace, workspace_bytes, kWsHeader)) return DBHIP_EWORKSPACE;
-  const DeviceInfo &dev = current_device_info();
-  if (!dev.ok) return DBHIP_ENODEVICE;
-
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  const hipError_t e = fill_async(workspace, 0, kWsHeader, s);
-  if (e != hipSuccess) return static_cast<int>(e);
+  const int rc = begin_call(workspace, workspace_bytes, kWsHeader, s);
+  if (rc != DBHIP_OK) return rc;
   const unsigned a = n ? words_past_16(outer) : 0u;
   const size_t tiles = (n + a + kCombTile - 1) / kCombTile;
   // (one workgroup at least: the cardinalities are judged for an empty column too)

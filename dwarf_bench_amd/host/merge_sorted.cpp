@@ -13,16 +13,16 @@
 //              values are then gathered by source index (consecutive outputs come from at most two consecutive runs
 //              of the inputs), or are the row ids themselves.
 //   count / scan / write  the set operations: the tile body with a keep flag per merged element -> kept per tile ->
-//              first output position per tile and *out_count (one workgroup, the shape of sel_scan_kernel) -> the tile
-//              body again, the kept keys compacted through LDS and stored.
+//              first output position per tile and *out_count (one workgroup, launch_rowlist_scan of rowlist.hpp) -> the
+//              tile body again, the kept keys compacted through LDS and stored.
 // The keep flag is local to the element because A stands first on ties and the lists are strict: an A element met
 // with B's cursor at j has a partner iff j < cb and B[j] equals it; a B element met with A's cursor at i has one iff
 // i > 0 and A[i - 1] equals it.  The two neighbours that may lie in another tile (A[a0 - 1] and B[b0 + bn]) are read
 // from global memory into two halo words of the LDS image.
 #include "merge_sorted.hpp"
 
-#include "dbhip_common.hpp"
 #include "merge_path.hpp"
+#include "rowlist.hpp"
 
 namespace {
 using namespace dbhip;
@@ -30,7 +30,6 @@ using namespace dbhip;
 constexpr unsigned kMpTile = DBENCH_MERGE_TILE_ROWS;
 constexpr int kMpThreads = 256;
 constexpr int kMpItems = kMpTile / kMpThreads;  // a thread's merged elements
-constexpr int kMpScanThreads = 256;             // four counts each: 1024 tiles a round
 static_assert(kMpItems == 8 && kMpItems * kMpThreads == kMpTile, "a thread stores its items as two 16-byte vectors");
 static_assert(kMpTile <= 65536, "source indices inside a tile are 16 bits");
 
@@ -51,9 +50,7 @@ MpLayout mp_layout(size_t rows) {
 }
 
 __device__ __forceinline__ unsigned mp_count(const unsigned long long *given, unsigned capacity) {
-  if (!given) return capacity;
-  const unsigned long long g = *given;
-  return g < capacity ? static_cast<unsigned>(g) : capacity;
+  return static_cast<unsigned>(clamped_count(given, capacity));
 }
 
 __global__ __launch_bounds__(kMpThreads) void mp_partition_kernel(const unsigned *__restrict__ a,
@@ -235,58 +232,8 @@ __global__ __launch_bounds__(kMpThreads) void mp_setop_kernel(int op, const unsi
   }
 }
 
-// one workgroup: cnt[tile] -> pos[tile] = kept elements in front of the tile; *out_count = all of them, at most
-// `bound`.  Both arrays are padded to 256 bytes, so a thread's four entries are always inside them.
-__global__ __launch_bounds__(kMpScanThreads) void mp_scan_kernel(const unsigned *__restrict__ cnt,
-                                                                 unsigned *__restrict__ pos, size_t tiles,
-                                                                 unsigned long long bound, unsigned long long *out_count) {
-  __shared__ unsigned s_wsum[kMpScanThreads / kWave];
-  // total of the rounds so far (the same in every thread).  A tile keeps at most its own merged elements and the tiles'
-  // elements add up to ca + cb < 2^32, so no sum here leaves 32 bits, whatever the inputs hold
-  unsigned run = 0;
-  for (size_t base = 0; base < tiles; base += 4 * kMpScanThreads) {
-    const size_t i = base + 4 * threadIdx.x;
-    u32x4 c = {0u, 0u, 0u, 0u};
-    if (i < tiles) {
-      c = *reinterpret_cast<const u32x4 *>(cnt + i);
-      if (i + 1 >= tiles) c.y = 0u;
-      if (i + 2 >= tiles) c.z = 0u;
-      if (i + 3 >= tiles) c.w = 0u;
-    }
-    unsigned round_total;
-    const unsigned first = run + block_exclusive_scan<kMpScanThreads>(c.x + c.y + c.z + c.w, s_wsum, round_total);
-    if (i < tiles) *reinterpret_cast<u32x4 *>(pos + i) = u32x4{first, first + c.x, first + c.x + c.y, first + c.x + c.y + c.z};
-    run += round_total;
-  }
-  // of unsorted inputs an element can be counted in two tiles: the count stays within the output's room
-  if (threadIdx.x == 0) *out_count = run < bound ? run : bound;
-}
-
-struct Range {
-  const void *p;
-  size_t bytes;
-};
-
-bool overlap(const Range &x, const Range &y) {
-  if (!x.p || !y.p || !x.bytes || !y.bytes) return false;
-  const uintptr_t a = reinterpret_cast<uintptr_t>(x.p), b = reinterpret_cast<uintptr_t>(y.p);
-  return a < b + y.bytes && b < a + x.bytes;
-}
-
-// an output overlapping an input or another output
-bool outputs_overlap(const Range *outs, int n_outs, const Range *ins, int n_ins) {
-  for (int i = 0; i < n_outs; ++i) {
-    for (int j = 0; j < n_ins; ++j)
-      if (overlap(outs[i], ins[j])) return true;
-    for (int j = i + 1; j < n_outs; ++j)
-      if (overlap(outs[i], outs[j])) return true;
-  }
-  return false;
-}
-
 bool sizes_ok(size_t a_capacity, size_t b_capacity) {
-  const size_t lim = 1ull << 32;
-  return a_capacity < lim && b_capacity < lim && a_capacity + b_capacity < lim;
+  return fits_32(a_capacity) && fits_32(b_capacity) && fits_32(a_capacity + b_capacity);
 }
 
 }  // namespace
@@ -311,28 +258,22 @@ extern "C" int dbench_merge_u32(const uint32_t *a_keys, const uint32_t *a_vals, 
   } else if ((a_capacity && !a_vals) || (b_capacity && !b_vals)) {
     return DBHIP_EINVAL;
   }
-  const uintptr_t words = reinterpret_cast<uintptr_t>(a_keys) | reinterpret_cast<uintptr_t>(a_vals) |
-                          reinterpret_cast<uintptr_t>(b_keys) | reinterpret_cast<uintptr_t>(b_vals) |
-                          reinterpret_cast<uintptr_t>(out_keys) | reinterpret_cast<uintptr_t>(out_vals);
-  const uintptr_t counts = reinterpret_cast<uintptr_t>(a_count) | reinterpret_cast<uintptr_t>(b_count) |
-                           reinterpret_cast<uintptr_t>(out_count);
+  const uintptr_t words = addr(a_keys) | addr(a_vals) | addr(b_keys) | addr(b_vals) | addr(out_keys) | addr(out_vals);
+  const uintptr_t counts = addr(a_count) | addr(b_count) | addr(out_count);
   if ((words & 3u) || (counts & 7u)) return DBHIP_EINVAL;
   const Range outs[] = {{out_keys, 4 * rows}, {out_vals, 4 * rows}, {out_count, 8}};
   const Range ins[] = {{a_keys, 4 * a_capacity}, {a_vals, 4 * a_capacity}, {a_count, 8},
                        {b_keys, 4 * b_capacity}, {b_vals, 4 * b_capacity}, {b_count, 8}};
   if (outputs_overlap(outs, 3, ins, 6)) return DBHIP_EINVAL;
   const MpLayout l = mp_layout(rows);
-  if (!ws_ok(workspace, workspace_bytes, l.total)) return DBHIP_EWORKSPACE;
-  const DeviceInfo &dev = current_device_info();
-  if (!dev.ok) return DBHIP_ENODEVICE;
-
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  const int rc = begin_call(workspace, workspace_bytes, l.total, s);
+  if (rc != DBHIP_OK) return rc;
+
   char *base = static_cast<char *>(workspace);
   unsigned *part = reinterpret_cast<unsigned *>(base + l.part);
   const unsigned long long *na = reinterpret_cast<const unsigned long long *>(a_count);
   const unsigned long long *nb = reinterpret_cast<const unsigned long long *>(b_count);
-  const hipError_t e = fill_async(workspace, 0, kWsHeader, s);
-  if (e != hipSuccess) return static_cast<int>(e);
 
   const unsigned tiles = static_cast<unsigned>(l.tiles), ac = static_cast<unsigned>(a_capacity),
                  bc = static_cast<unsigned>(b_capacity);
@@ -355,10 +296,7 @@ extern "C" int dbench_setop_u32(int op, const uint32_t *a, const uint64_t *a_cou
   if (!sizes_ok(a_capacity, b_capacity)) return DBHIP_EINVAL;
   if ((a_capacity && !a) || (b_capacity && !b) || !out_count) return DBHIP_EINVAL;
   if ((a_count && !a) || (b_count && !b)) return DBHIP_EINVAL;
-  const uintptr_t words = reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(b) | reinterpret_cast<uintptr_t>(out);
-  const uintptr_t counts = reinterpret_cast<uintptr_t>(a_count) | reinterpret_cast<uintptr_t>(b_count) |
-                           reinterpret_cast<uintptr_t>(out_count);
-  if ((words & 3u) || (counts & 7u)) return DBHIP_EINVAL;
+  if (((addr(a) | addr(b) | addr(out)) & 3u) || ((addr(a_count) | addr(b_count) | addr(out_count)) & 7u)) return DBHIP_EINVAL;
   const size_t rows = a_capacity + b_capacity;
   const size_t bound = op == DBENCH_SETOP_UNION ? rows
                        : op == DBENCH_SETOP_INTERSECT ? (a_capacity < b_capacity ? a_capacity : b_capacity)
@@ -367,19 +305,16 @@ extern "C" int dbench_setop_u32(int op, const uint32_t *a, const uint64_t *a_cou
   const Range ins[] = {{a, 4 * a_capacity}, {a_count, 8}, {b, 4 * b_capacity}, {b_count, 8}};
   if (outputs_overlap(outs, 2, ins, 4)) return DBHIP_EINVAL;
   const MpLayout l = mp_layout(rows);
-  if (!ws_ok(workspace, workspace_bytes, l.total)) return DBHIP_EWORKSPACE;
-  const DeviceInfo &dev = current_device_info();
-  if (!dev.ok) return DBHIP_ENODEVICE;
-
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  const int rc = begin_call(workspace, workspace_bytes, l.total, s);
+  if (rc != DBHIP_OK) return rc;
+
   char *base = static_cast<char *>(workspace);
   unsigned *part = reinterpret_cast<unsigned *>(base + l.part);
   unsigned *cnt = reinterpret_cast<unsigned *>(base + l.cnt);
   unsigned *pos = reinterpret_cast<unsigned *>(base + l.pos);
   const unsigned long long *na = reinterpret_cast<const unsigned long long *>(a_count);
   const unsigned long long *nb = reinterpret_cast<const unsigned long long *>(b_count);
-  const hipError_t e = fill_async(workspace, 0, kWsHeader, s);
-  if (e != hipSuccess) return static_cast<int>(e);
 
   const unsigned tiles = static_cast<unsigned>(l.tiles), ac = static_cast<unsigned>(a_capacity),
                  bc = static_cast<unsigned>(b_capacity);
@@ -389,8 +324,7 @@ extern "C" int dbench_setop_u32(int op, const uint32_t *a, const uint64_t *a_cou
     hipLaunchKernelGGL(mp_setop_kernel<false>, dim3(tiles), dim3(kMpThreads), 0, s, op, a, na, ac, b, nb, bc, part, cnt,
                        static_cast<const unsigned *>(nullptr), static_cast<unsigned *>(nullptr), 0u);
   }
-  hipLaunchKernelGGL(mp_scan_kernel, dim3(1), dim3(kMpScanThreads), 0, s, cnt, pos, static_cast<size_t>(tiles),
-                     static_cast<unsigned long long>(bound), reinterpret_cast<unsigned long long *>(out_count));
+  launch_rowlist_scan(cnt, pos, tiles, bound, reinterpret_cast<unsigned long long *>(out_count), s);
   if (tiles && out)
     hipLaunchKernelGGL(mp_setop_kernel<true>, dim3(tiles), dim3(kMpThreads), 0, s, op, a, na, ac, b, nb, bc, part, cnt, pos,
                        out, static_cast<unsigned>(bound));

@@ -7,15 +7,16 @@
 //          consecutive candidates per group of 256 (one 16-byte load of the column, or of the row ids followed by four
 //          4-byte gathers), evaluates the predicate and ballots it; the 64 ballots of the segment are its match mask
 //          (one coalesced 512-byte store) and their population count is the segment's match count.
-//   scan   one workgroup: counts -> first output positions, and *out_count.
+//   scan   one workgroup: counts -> first output positions, and *out_count (launch_rowlist_scan).
 //   write  a wave whose segment has matches reads the masks back (not the column), ranks every match with mbcnt over
 //          the group's four ballots plus the wave's running position, and stores the row ids.
 // Positions are counted from the 16-byte boundary in front of the column (or the list): candidate i sits at v = i + a,
 // a = 0..3 words, so every 16-byte load is aligned whatever the pointer's alignment; the two vectors that straddle the
-// ends of the array are read word by word, and nothing outside the arrays is touched.
+// ends of the array are read word by word, and nothing outside the arrays is touched.  The predicate, the ragged load,
+// the device count, the scan and the host checks are those of every row-id operator (rowlist.hpp, call_checks.hpp).
 #include "select_rows.hpp"
 
-#include "dbhip_common.hpp"
+#include "rowlist.hpp"
 
 namespace {
 using namespace dbhip;
@@ -28,7 +29,6 @@ constexpr int kSelWaves = 2;
 constexpr int kSelThreads = kSelWaves * kWave;
 constexpr int kSelGroups = kSelSegment / (4 * kWave);  // groups of 256 candidates: four per lane
 constexpr int kSelWords = kSelSegment / kWave;         // mask words of a segment, one per lane
-constexpr int kSelScanThreads = 256;  // four counts each: 1024 segments (2^22 candidates) a round
 static_assert(kSelWords == kWave && kSelGroups * 4 == kSelWords, "a lane keeps one mask word of its wave's segment");
 
 struct SelLayout {
@@ -46,32 +46,18 @@ SelLayout sel_layout(size_t candidates) {
   return l;
 }
 
-struct SelPred {
-  unsigned flip, lo, hi;  // x is inside iff lo <= (x ^ flip) <= hi, lo and hi already flipped (0x80000000 for int32)
-  bool negate;
-};
-
-__device__ __forceinline__ bool sel_keep(unsigned x, const SelPred &p) {
-  const unsigned y = x ^ p.flip;
-  return (y >= p.lo && y <= p.hi) != p.negate;
-}
-
 // kList: `src` is the row-id list (gathered through into col), otherwise the column itself.  m_host candidates at
 // most (n_col in dense mode); in list mode *in_count (nullable) lowers it on the device.
 template <bool kList>
 __global__ __launch_bounds__(kSelThreads) void sel_mark_kernel(const unsigned *__restrict__ col, unsigned n_col,
                                                                const unsigned *__restrict__ src, size_t m_host,
-                                                               const unsigned long long *in_count, unsigned a, SelPred p,
+                                                               const unsigned long long *in_count, unsigned a, RangePred p,
                                                                unsigned *status, unsigned *__restrict__ cnt,
                                                                unsigned long long *__restrict__ masks, size_t segments) {
   const unsigned lane = threadIdx.x & (kWave - 1), wave = threadIdx.x / kWave;
   const size_t seg = static_cast<size_t>(blockIdx.x) * kSelWaves + wave;
   if (seg >= segments) return;  // uniform over the wave; no barrier below
-  size_t m = m_host;
-  if (kList && in_count) {
-    const unsigned long long given = *in_count;
-    if (given < m) m = given;
-  }
+  const size_t m = kList ? clamped_count(in_count, m_host) : m_host;
   const size_t vfirst = seg * kSelSegment, vend = a + m;  // positions [a, vend) hold candidates
   unsigned long long mine = 0;  // mask word `lane` of the segment
   unsigned total = 0;           // matches of the segment (wave-uniform)
@@ -104,7 +90,7 @@ __global__ __launch_bounds__(kSelThreads) void sel_mark_kernel(const unsigned *_
   auto vote = [&](int g, const unsigned (&x)[4], unsigned ok) {
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
-      const unsigned long long b = __ballot(((ok >> q) & 1u) && sel_keep(x[q], p));
+      const unsigned long long b = __ballot(((ok >> q) & 1u) && range_keep(x[q], p));
       total += static_cast<unsigned>(__popcll(b));
       if (lane == static_cast<unsigned>(4 * g + q)) mine = b;
     }
@@ -136,6 +122,8 @@ __global__ __launch_bounds__(kSelThreads) void sel_mark_kernel(const unsigned *_
 #pragma unroll 1
     for (int g = 0; g < kSelGroups; ++g) {
       const size_t v0 = vfirst + static_cast<size_t>(g) * (4 * kWave) + 4 * lane;
+      // load_ragged's text (rowlist.hpp), a deliberate copy: through the call sel_mark_kernel<true> comes out with the
+      // operands of four s_and_b64 exchanged, and the rule is same instruction text or the parent's body
       u32x4 e = {0u, 0u, 0u, 0u};
       unsigned valid = 0;
       if (v0 >= a && v0 + 4 <= vend) {
@@ -156,30 +144,6 @@ __global__ __launch_bounds__(kSelThreads) void sel_mark_kernel(const unsigned *_
   masks[seg * kSelWords + lane] = mine;
   if (lane == 0) cnt[seg] = total;
   if (kList && __ballot(bad) != 0 && lane == 0) atomicOr(status, DBHIP_DEV_KEY_RANGE);
-}
-
-// one workgroup: cnt[segment] -> pos[segment] = matches in front of the segment; *out_count = all matches.
-// Both arrays are padded to 256 bytes, so a thread's four entries are always inside them.
-__global__ __launch_bounds__(kSelScanThreads) void sel_scan_kernel(const unsigned *__restrict__ cnt,
-                                                                   unsigned *__restrict__ pos, size_t segments,
-                                                                   unsigned long long *out_count) {
-  __shared__ unsigned s_wsum[kSelScanThreads / kWave];
-  unsigned run = 0;  // total of the rounds so far (the same in every thread)
-  for (size_t base = 0; base < segments; base += 4 * kSelScanThreads) {
-    const size_t i = base + 4 * threadIdx.x;
-    u32x4 c = {0u, 0u, 0u, 0u};
-    if (i < segments) {
-      c = *reinterpret_cast<const u32x4 *>(cnt + i);
-      if (i + 1 >= segments) c.y = 0u;
-      if (i + 2 >= segments) c.z = 0u;
-      if (i + 3 >= segments) c.w = 0u;
-    }
-    unsigned round_total;
-    const unsigned first = run + block_exclusive_scan<kSelScanThreads>(c.x + c.y + c.z + c.w, s_wsum, round_total);
-    if (i < segments) *reinterpret_cast<u32x4 *>(pos + i) = u32x4{first, first + c.x, first + c.x + c.y, first + c.x + c.y + c.z};
-    run += round_total;
-  }
-  if (threadIdx.x == 0) *out_count = run;
 }
 
 // a wave writes its segment's kept row ids, in candidate order, from pos[segment] on
@@ -241,18 +205,10 @@ __global__ __launch_bounds__(kSelThreads) void sel_write_kernel(const unsigned *
   }
 }
 
-bool overlap(const void *p, size_t p_bytes, const void *q, size_t q_bytes) {
-  if (!p || !q || !p_bytes || !q_bytes) return false;
-  const uintptr_t a = reinterpret_cast<uintptr_t>(p), b = reinterpret_cast<uintptr_t>(q);
-  return a < b + q_bytes && b < a + p_bytes;
-}
-
-unsigned words_past_16(const void *p) { return static_cast<unsigned>((reinterpret_cast<uintptr_t>(p) >> 2) & 3u); }
-
 }  // namespace
 
 extern "C" size_t dbench_select_workspace_bytes(size_t candidates) {
-  if (candidates >= (1ull << 32)) return 0;
+  if (!fits_32(candidates)) return 0;
   return sel_layout(candidates).total;
 }
 
@@ -260,37 +216,30 @@ extern "C" int dbench_select_range_u32(const uint32_t *col, size_t n_col, const 
                                        size_t in_capacity, uint32_t lo, uint32_t hi, int flags, uint32_t *out_rows,
                                        uint64_t *out_count, void *workspace, size_t workspace_bytes, void *stream) {
   if (flags & ~(DBENCH_SELECT_SIGNED | DBENCH_SELECT_NEGATE)) return DBHIP_EINVAL;
-  if (n_col >= (1ull << 32) || in_capacity >= (1ull << 32)) return DBHIP_EINVAL;  // 32-bit row ids and counts
+  if (!fits_32(n_col) || !fits_32(in_capacity)) return DBHIP_EINVAL;  // 32-bit row ids and counts
   if ((n_col && !col) || !out_count || (in_count && !in_rows)) return DBHIP_EINVAL;
-  const uintptr_t words = reinterpret_cast<uintptr_t>(col) | reinterpret_cast<uintptr_t>(in_rows) |
-                          reinterpret_cast<uintptr_t>(out_rows);
-  const uintptr_t counts = reinterpret_cast<uintptr_t>(in_count) | reinterpret_cast<uintptr_t>(out_count);
-  if ((words & 3u) || (counts & 7u)) return DBHIP_EINVAL;
+  if (((addr(col) | addr(in_rows) | addr(out_rows)) & 3u) || ((addr(in_count) | addr(out_count)) & 7u)) return DBHIP_EINVAL;
   const bool list = in_rows != nullptr;
   const size_t candidates = list ? in_capacity : n_col;
   if (overlap(out_rows, 4 * candidates, col, 4 * n_col) || overlap(out_rows, 4 * candidates, in_rows, 4 * in_capacity))
     return DBHIP_EINVAL;
   const SelLayout l = sel_layout(candidates);
-  if (!ws_ok(workspace, workspace_bytes, l.total)) return DBHIP_EWORKSPACE;
-  const DeviceInfo &dev = current_device_info();
-  if (!dev.ok) return DBHIP_ENODEVICE;
-
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  const int rc = begin_call(workspace, workspace_bytes, l.total, s);
+  if (rc != DBHIP_OK) return rc;
+
   char *base = static_cast<char *>(workspace);
   unsigned *status = reinterpret_cast<unsigned *>(base);
   unsigned *cnt = reinterpret_cast<unsigned *>(base + l.cnt);
   unsigned *pos = reinterpret_cast<unsigned *>(base + l.pos);
   unsigned long long *masks = reinterpret_cast<unsigned long long *>(base + l.masks);
   unsigned long long *total = reinterpret_cast<unsigned long long *>(out_count);
-  // the status word is cleared by a launch of its own, in front of the one that can raise it
-  const hipError_t e = fill_async(workspace, 0, kWsHeader, s);
-  if (e != hipSuccess) return static_cast<int>(e);
 
   const unsigned a = candidates ? words_past_16(list ? in_rows : col) : 0u;
   const size_t segments = candidates ? (candidates + a + kSelSegment - 1) / kSelSegment : 0;  // <= l.segments
   const unsigned grid = static_cast<unsigned>((segments + kSelWaves - 1) / kSelWaves);
   const unsigned flip = (flags & DBENCH_SELECT_SIGNED) ? 0x80000000u : 0u;
-  const SelPred p{flip, lo ^ flip, hi ^ flip, (flags & DBENCH_SELECT_NEGATE) != 0};
+  const RangePred p{flip, lo ^ flip, hi ^ flip, (flags & DBENCH_SELECT_NEGATE) != 0};
   if (segments) {
     if (list)
       hipLaunchKernelGGL((sel_mark_kernel<true>), dim3(grid), dim3(kSelThreads), 0, s, col, static_cast<unsigned>(n_col),
@@ -300,7 +249,7 @@ extern "C" int dbench_select_range_u32(const uint32_t *col, size_t n_col, const 
       hipLaunchKernelGGL((sel_mark_kernel<false>), dim3(grid), dim3(kSelThreads), 0, s, col, static_cast<unsigned>(n_col),
                          col, n_col, static_cast<const unsigned long long *>(nullptr), a, p, status, cnt, masks, segments);
   }
-  hipLaunchKernelGGL(sel_scan_kernel, dim3(1), dim3(kSelScanThreads), 0, s, cnt, pos, segments, total);
+  launch_rowlist_scan(cnt, pos, segments, candidates, total, s);  // the write kernels stop at `candidates` as well
   if (segments && out_rows) {
     if (list)
       hipLaunchKernelGGL((sel_write_kernel<true>), dim3(grid), dim3(kSelThreads), 0, s, in_rows, in_capacity, a, cnt, pos,

@@ -2,12 +2,13 @@
 // of up to four 32-bit columns through a row-id list, and COUNT / 64-bit SUM / MIN / MAX of a column over a row-id list or
 // over all its rows.
 //
-// The load shape is that of sel_mark_kernel<list> (select_rows.cpp).  Positions are counted from the 16-byte boundary in
-// front of the list: entry i sits at v = i + a, a = 0..3 words, so every 16-byte load of row ids is aligned whatever the
-// pointer's alignment.  A wave owns one segment of 1024 positions at a time, a lane four consecutive entries per group of
-// 256; each entry is bounds-checked, and the gathers are unconditional (row 0 stands in for an entry that does not
-// count), so they are independent of each other and all issued before the first use.  The two segments that straddle the
-// ends of the list are handled word by word; nothing outside the arrays is touched.
+// The load shape is that of sel_mark_kernel<list> (select_rows.cpp), its shared text is rowlist.hpp's.  Positions are
+// counted from the 16-byte boundary in front of the list: entry i sits at v = i + a, a = 0..3 words, so every 16-byte load
+// of row ids is aligned whatever the pointer's alignment.  A wave owns one segment of 1024 positions at a time, a lane
+// four consecutive entries per group of 256; each entry is bounds-checked, and the gathers are unconditional (row 0
+// stands in for an entry that does not count), so they are independent of each other and all issued before the first
+// use.  The two segments that straddle the ends of the list are handled word by word; nothing outside the arrays is
+// touched.
 //   take       one launch, a wave per segment.  An output is written in position order: a lane stores its four words
 //              per column with one 16-byte store where the output has the list's phase (the same words past a 16-byte
 //              boundary); where it has not, the lanes pass the words that belong to their right neighbour's aligned
@@ -17,12 +18,10 @@
 //              dependent launch of one workgroup folds the records into out[4].  No workgroup waits for another.
 #include "take_rows.hpp"
 
-#include "dbhip_common.hpp"
+#include "rowlist.hpp"
 
 namespace {
 using namespace dbhip;
-
-typedef unsigned long long u64;
 
 constexpr unsigned kTakeSegment = DBENCH_TAKE_SEGMENT_ROWS;
 constexpr int kTakeMaxCols = DBENCH_TAKE_MAX_COLS;
@@ -61,37 +60,6 @@ struct TakeCols {
   unsigned *out[kTakeMaxCols];
   unsigned shift[kTakeMaxCols];  // (words of out[c] past a 16-byte boundary - those of the list) mod 4
 };
-
-// m = min(*count, capacity), read on the device
-__device__ __forceinline__ size_t clamped_count(const u64 *count, size_t capacity) {
-  size_t m = capacity;
-  if (count) {
-    const u64 given = *count;
-    if (given < m) m = static_cast<size_t>(given);
-  }
-  return m;
-}
-
-// this lane's four entries at positions v0 .. v0+3, word by word: bit q of `valid` says that position v0 + q holds an
-// entry, that is, lies in [a, vend)
-__device__ __forceinline__ u32x4 load_ragged(const unsigned *__restrict__ src, unsigned a, size_t v0, size_t vend,
-                                             unsigned &valid) {
-  u32x4 e = {0u, 0u, 0u, 0u};
-  valid = 0;
-  if (v0 >= a && v0 + 4 <= vend) {
-    e = *reinterpret_cast<const u32x4 *>(src + (v0 - a));
-    valid = 0xfu;
-  } else {
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      if (v0 + q >= a && v0 + q < vend) {
-        e[q] = src[v0 + q - a];
-        valid |= 1u << q;
-      }
-    }
-  }
-  return e;
-}
 
 // the bounds check of a lane's four row ids: -> bit q of the result: entry q is valid and names a row of the column;
 // row[q] = the row to gather (row 0 for an entry that does not count); bad: a valid entry that is neither a row nor,
@@ -351,14 +319,6 @@ __global__ __launch_bounds__(kAggFoldThreads) void agg_fold_kernel(const AggReco
   }
 }
 
-bool overlap(const void *p, size_t p_bytes, const void *q, size_t q_bytes) {
-  if (!p || !q || !p_bytes || !q_bytes) return false;
-  const uintptr_t a = reinterpret_cast<uintptr_t>(p), b = reinterpret_cast<uintptr_t>(q);
-  return a < b + q_bytes && b < a + p_bytes;
-}
-
-unsigned words_past_16(const void *p) { return static_cast<unsigned>((reinterpret_cast<uintptr_t>(p) >> 2) & 3u); }
-
 template <int kCols>
 void launch_take(unsigned grid, hipStream_t s, const TakeCols &t, unsigned n_rows, const unsigned *rows, size_t capacity,
                  const u64 *count, unsigned a, bool outer, unsigned fill, unsigned *status, size_t segments) {
@@ -369,7 +329,7 @@ void launch_take(unsigned grid, hipStream_t s, const TakeCols &t, unsigned n_row
 }  // namespace
 
 extern "C" size_t dbench_take_workspace_bytes(size_t capacity) {
-  if (capacity >= (1ull << 32)) return 0;
+  if (!fits_32(capacity)) return 0;
   return take_layout(capacity).total;
 }
 
@@ -378,14 +338,14 @@ extern "C" int dbench_take_u32(const uint32_t *const *cols, size_t n_cols, size_
                                void *workspace, size_t workspace_bytes, void *stream) {
   if (flags & ~DBENCH_TAKE_OUTER) return DBHIP_EINVAL;  // unknown bits, and DBENCH_TAKE_SIGNED: take moves bit patterns
   if (n_cols < 1 || n_cols > DBENCH_TAKE_MAX_COLS || !cols || !outs) return DBHIP_EINVAL;
-  if (n_rows >= (1ull << 32) || capacity >= (1ull << 32)) return DBHIP_EINVAL;  // 32-bit row ids and positions
+  if (!fits_32(n_rows) || !fits_32(capacity)) return DBHIP_EINVAL;  // 32-bit row ids and positions
   if ((capacity && !rows) || (count && !rows)) return DBHIP_EINVAL;
-  uintptr_t words = reinterpret_cast<uintptr_t>(rows);
+  uintptr_t words = addr(rows);
   for (size_t c = 0; c < n_cols; ++c) {
     if ((n_rows && capacity && !cols[c]) || !outs[c]) return DBHIP_EINVAL;
-    words |= reinterpret_cast<uintptr_t>(cols[c]) | reinterpret_cast<uintptr_t>(outs[c]);
+    words |= addr(cols[c]) | addr(outs[c]);
   }
-  if ((words & 3u) || (reinterpret_cast<uintptr_t>(count) & 7u)) return DBHIP_EINVAL;
+  if ((words & 3u) || (addr(count) & 7u)) return DBHIP_EINVAL;
   for (size_t c = 0; c < n_cols; ++c) {
     if (overlap(outs[c], 4 * capacity, rows, 4 * capacity) || overlap(outs[c], 4 * capacity, count, 8)) return DBHIP_EINVAL;
     for (size_t k = 0; k < n_cols; ++k) {
@@ -393,16 +353,12 @@ extern "C" int dbench_take_u32(const uint32_t *const *cols, size_t n_cols, size_
       if (k < c && overlap(outs[c], 4 * capacity, outs[k], 4 * capacity)) return DBHIP_EINVAL;
     }
   }
-  if (!ws_ok(workspace, workspace_bytes, take_layout(capacity).total)) return DBHIP_EWORKSPACE;
-  const DeviceInfo &dev = current_device_info();
-  if (!dev.ok) return DBHIP_ENODEVICE;
-
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  unsigned *status = static_cast<unsigned *>(workspace);
-  // the status word is cleared by a launch of its own, in front of the one that can raise it
-  const hipError_t e = fill_async(workspace, 0, kWsHeader, s);
-  if (e != hipSuccess) return static_cast<int>(e);
+  const int rc = begin_call(workspace, workspace_bytes, take_layout(capacity).total, s);
+  if (rc != DBHIP_OK) return rc;
   if (!capacity) return launch_status();
+
+  unsigned *status = static_cast<unsigned *>(workspace);
 
   const unsigned a = words_past_16(rows);
   const size_t segments = (capacity + a + kTakeSegment - 1) / kTakeSegment;
@@ -429,25 +385,20 @@ extern "C" int dbench_aggregate_rows_u32(const uint32_t *col, size_t n_rows, con
                                          size_t capacity, int flags, uint64_t *out, void *workspace,
                                          size_t workspace_bytes, void *stream) {
   if (flags & ~(DBENCH_TAKE_OUTER | DBENCH_TAKE_SIGNED)) return DBHIP_EINVAL;
-  if (n_rows >= (1ull << 32) || capacity >= (1ull << 32)) return DBHIP_EINVAL;  // 32-bit row ids and positions
+  if (!fits_32(n_rows) || !fits_32(capacity)) return DBHIP_EINVAL;  // 32-bit row ids and positions
   const bool list = rows != nullptr;
   if ((n_rows && (list ? capacity != 0 : true) && !col) || (count && !rows) || !out) return DBHIP_EINVAL;
-  const uintptr_t words = reinterpret_cast<uintptr_t>(col) | reinterpret_cast<uintptr_t>(rows);
-  const uintptr_t longs = reinterpret_cast<uintptr_t>(count) | reinterpret_cast<uintptr_t>(out);
-  if ((words & 3u) || (longs & 7u)) return DBHIP_EINVAL;
+  if (((addr(col) | addr(rows)) & 3u) || ((addr(count) | addr(out)) & 7u)) return DBHIP_EINVAL;
   const size_t candidates = list ? capacity : n_rows;
   if (overlap(out, 32, col, 4 * n_rows) || overlap(out, 32, rows, 4 * capacity) || overlap(out, 32, count, 8))
     return DBHIP_EINVAL;
   // the aggregate over all rows asks for the smallest workspace and takes the partial records the given one holds
-  if (!ws_ok(workspace, workspace_bytes, take_layout(list ? capacity : 0).total)) return DBHIP_EWORKSPACE;
-  const DeviceInfo &dev = current_device_info();
-  if (!dev.ok) return DBHIP_ENODEVICE;
-
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  const int rc = begin_call(workspace, workspace_bytes, take_layout(list ? capacity : 0).total, s);
+  if (rc != DBHIP_OK) return rc;
+
   unsigned *status = static_cast<unsigned *>(workspace);
   AggRecord *parts = reinterpret_cast<AggRecord *>(static_cast<char *>(workspace) + kWsHeader);
-  const hipError_t e = fill_async(workspace, 0, kWsHeader, s);
-  if (e != hipSuccess) return static_cast<int>(e);
 
   const unsigned a = candidates ? words_past_16(list ? rows : col) : 0u;
   const size_t segments = candidates ? (candidates + a + kTakeSegment - 1) / kTakeSegment : 0;

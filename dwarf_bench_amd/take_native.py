@@ -5,12 +5,8 @@ fill, the "no row" id, workspace layout) is the header's comment.  No fallback: 
 from __future__ import annotations
 
 import ctypes as C
-from pathlib import Path
 
-from . import _capi
-
-_LIB = Path(__file__).resolve().parent / "_lib" / "libdbench.so"
-_lib = None
+from ._dbench import lib  # noqa: F401  the one handle of libdbench.so, every family's ENTRY_POINTS bound
 
 # the #defines of take_rows.hpp (tests/test_take_host.py holds the two together)
 MAX_COLS = 4
@@ -25,21 +21,6 @@ ENTRY_POINTS = {
     "dbench_take_u32": (_int, [_vp, _sz, _sz, _vp, _vp, _sz, _int, _u32, _vp, _vp, _sz, _vp]),
     "dbench_aggregate_rows_u32": (_int, [_vp, _sz, _vp, _vp, _sz, _int, _vp, _vp, _sz, _vp]),
 }
-
-
-def lib() -> C.CDLL:
-    global _lib
-    if _lib is None:
-        if not _LIB.exists():
-            raise _capi.DbhipError(f"{_LIB} is missing: run `python -m dwarf_bench_amd.build`")
-        _capi.lib()  # libdbhip.so first (RTLD_GLOBAL), same HIP runtime as torch
-        h = C.CDLL(str(_LIB), mode=C.RTLD_GLOBAL)
-        for name, (res, args) in ENTRY_POINTS.items():
-            fn = getattr(h, name)  # AttributeError if the .so does not export the symbol
-            fn.restype = res
-            fn.argtypes = args
-        _lib = h
-    return _lib
 
 
 def workspace_bytes(capacity: int) -> int:

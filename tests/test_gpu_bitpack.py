@@ -346,6 +346,28 @@ def test_select_through_lists(m):
     assert expect_select(empty, 0, 8, 0, 0, 0xFFFFFFFF, rows=np.array([0, 5], U)).size == 0  # an empty column keeps nothing
 
 
+def test_select_second_round_of_the_scan():
+    """1025 segments: the scan (launch_rowlist_scan, 1024 counts a round) runs a second round, and the one row of the last
+    segment lands behind everything the first round counted.  Width 1, a 512 KiB column; the kept rows lie in the first
+    segment, in segment 1023 and in segment 1024, mirrored, so that the reversed list keeps entries in the same three"""
+    n, width, base = 1024 * SEG + 1, 1, 7
+    front = np.array([0, 5, SEG - 1], np.int64)
+    ones = np.r_[front, n - 1 - front]
+    assert sorted(set(ones // SEG)) == [0, 1023, 1024] and (ones // SEG == 1024).sum() == 1
+    codes = np.zeros(n, U)
+    codes[ones] = 1
+    packed = bm.pack_codes(codes, width)
+    assert packed.size * 4 == 512 * 1024 + 16 and bn.workspace_bytes(n) >= 256 + 2 * 4 * 1025
+    got = expect_select(packed, n, width, base, base + 1, base + 1, out_off=1)
+    assert np.array_equal(got, np.sort(ones).astype(U))
+    rows = np.arange(n - 1, -1, -1, dtype=np.int64).astype(U)  # the same length, back to front
+    got = expect_select(packed, n, width, base, base + 1, base + 1, rows=rows, list_off=3, out_off=2, fill=FILLS[1])
+    assert np.array_equal(got, np.sort(ones)[::-1].astype(U))
+    # (the other side of the predicate: every segment of both rounds is full but for the six rows)
+    _, total, st = call_select(packed, n, width, base, base + 1, base + 1, flags=bn.NEGATE, want_rows=False)
+    assert (total, st) == (n - ones.size, 0)
+
+
 def test_a_dirty_workspace_changes_nothing():
     n, width, base = 2 * SEG + 77, 12, 1000
     values = make_codes(n, width, "random") + U(base)
