@@ -283,3 +283,96 @@ def test_fuzz_slab():
         assert np.array_equal(ok, np.where(hit, probe, np.uint32(0xFFFFFFFF))), (n, buckets)
         assert np.array_equal(op_, np.where(hit, pv, np.uint32(0xFFFFFFFF)))
         assert (ob[~hit] == 0xFFFFFFFF).all() and np.array_equal(keys[ob[hit]], probe[hit])
+
+
+# ---- the row-id operators: the seeded draws of tests/fuzz_testlib.py ------------------------------------------------------
+# Every dimension of a draw is drawn on its own (tests/test_fuzz_draws_host.py shows, without a GPU, that each set holds
+# every category and rejects a list of defective backends).  Each draw runs once through the raw entry point on guarded
+# buffers and is compared exactly with the operator's numpy model; the draws of a sweep share one guarded workspace that
+# starts as random bytes and is never cleared; every fourth draw also goes through the tensor front door.
+def _sweep(name):
+    from tests import fuzz_gpu_testlib as fg
+    from tests.test_fuzz_draws_host import DRAWS
+    s = fg.sweep(name)
+    assert s.calls == DRAWS[name] and s.doors == -(-s.calls // 4)
+
+
+def test_fuzz_sort_pairs():
+    """dbhip_radix_sort_pairs_u32 and _i32, carried values and the argsort, both digit widths, every key distribution:
+    the stable order of numpy"""
+    _sweep("sort_pairs")
+
+
+def test_fuzz_sorted_search_and_range_join():
+    """the fence ladder built into the shared workspace and the search through it: column sizes at fan-out 64 and every
+    allowed top_entries, each top_entries, the column off its boundary, lo, hi or both, hi below lo, either output NULL;
+    every fourth draw through ops.sorted_search and ops.range_join"""
+    _sweep("sorted_search")
+
+
+def test_fuzz_join_pairs():
+    """dbhip_join_pairs_u32 on the (ids, pos, cnt) of a join, with and without probe row ids, every column at its own
+    offset, capacities below, at and above the total and the count-only call, ranges that leave the id buffer, totals
+    beyond 2^32"""
+    _sweep("join_pairs")
+
+
+def test_fuzz_topk():
+    """dbhip_topk_u32 and _i32: n at the segment's and the chunk's seams, k from 0 to n + 5, largest, signed, sorted, every
+    key distribution (ties at the k-th key by ascending row)"""
+    _sweep("topk")
+
+
+def test_fuzz_reduce_by_key():
+    """dbhip_reduce_by_key_u32: run lengths 1, about 1.5, about 40 and one run, a key that returns, each output column
+    given or NULL, capacities below, at and above the number of runs and the count-only call, sums past 2^32"""
+    _sweep("reduce_by_key")
+
+
+def test_fuzz_scan_by_key():
+    """dbhip_scan_by_key_u32: the same run shapes, each output column given or NULL, signed and unsigned values at both
+    ends of the range"""
+    _sweep("scan_by_key")
+
+
+def test_fuzz_dictionary():
+    """dbench_dict_build_u32 and the encode of another column through the dictionary it left: capacities below, at and
+    above the number of distinct values, both orders, both device counts, present and absent values, the miss count"""
+    _sweep("dict")
+
+
+def test_fuzz_select():
+    """dbench_select_range_u32 over all rows and through lists: sizes at the segment's seams and one draw of more than
+    1024 segments, offsets of column, list and output, every kind of device count, signed, negate, the count alone"""
+    _sweep("select")
+
+
+def test_fuzz_merge_and_set_operations():
+    """dbench_setop_u32 (one draw of more than 1024 tiles) and dbench_merge_u32 in its three value modes: sizes at the
+    tile's seams split every way over A and B, both device counts, duplicates across the tile edges, both orders"""
+    _sweep("merge")
+
+
+def test_fuzz_take_and_aggregate():
+    """dbench_take_u32 of one to four columns and dbench_aggregate_rows_u32: every column, list and output at its own
+    offset, row ids outside the column with and without OUTER, sums past 2^32, values at both ends of the signed range"""
+    _sweep("take")
+
+
+def test_fuzz_bitpack():
+    """pack, unpack and the filter on packed codes: widths 1 to 32 over a base, rows that do not fit, codes across word
+    edges, lists with ids outside the column, one filter of more than 1024 segments"""
+    _sweep("bitpack")
+
+
+def test_fuzz_row_id_queries():
+    """twenty random plans of 3 to 6 steps over 2 to 4 columns of up to 2^17 rows - select, refine, union / intersect /
+    difference of two earlier lists, take, aggregate, the filter on a packed copy of a column, encode and decode through a
+    dictionary - every count on the device until the one synchronisation at the end, against the same plan in numpy"""
+    from tests import fuzz_gpu_testlib as fg
+    from tests import fuzz_testlib as ft
+    plans = list(ft.plan_draws(np.random.default_rng(211)))
+    assert len(plans) == 20 and {s["step"] for p in plans for s in p["steps"]} == set(ft.PLAN_STEPS)
+    for plan in plans:
+        assert 3 <= len(plan["steps"]) <= 6 and 2 <= len(plan["cols"]) <= 4 and plan["n"] <= 1 << 17
+        fg.check_plan(plan, fg.run_plan(plan))

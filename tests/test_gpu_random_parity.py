@@ -1,6 +1,10 @@
 """A short randomized parity run (tools/fuzz_gpu.py; beside the seeded oracle sweep of test_gpu_fuzz.py): sizes, alignments and value distributions outside the fixed lists
 of the other test files — both scan entry points, both digit widths of the sort, group-by, exclusive scan, reduce and
-both join forms, the hash group-by, the cuckoo and the slab tables against numpy."""
+both join forms, the hash group-by, the cuckoo and the slab tables against numpy; the key-value sort and argsort, join
+pairs, top-k, reduce- and scan-by-key, the sorted search and range join, the selection vectors, merge and the set
+operations, take and aggregate, the dictionary and the bit-packed columns on the draws of tests/fuzz_testlib.py (which the
+tool imports, with tests/fuzz_gpu_testlib.py: one definition for the sweeps and the tool), and random query plans over the
+row-id operators, against their numpy models."""
 import subprocess
 import sys
 from pathlib import Path

@@ -1,17 +1,27 @@
 """development aid: randomized parity runs of the HIP paths against numpy (sizes, alignments, value distributions the
-fixed test lists do not cover).  python tools/fuzz_gpu.py [seconds] [seed]"""
+fixed test lists do not cover).  The eleven newer operators (sort pairs, join pairs, top-k, reduce- and scan-by-key,
+sorted search, select, merge and set operations, take and aggregate, dictionary, bit-packed columns) run the draws of
+tests/fuzz_testlib.py through tests/fuzz_gpu_testlib.py on guarded buffers, a few per round, on one never-cleared
+workspace per operator, and one random query plan over the row-id operators per round: the tool needs the repository's
+tests directory beside it.  python tools/fuzz_gpu.py [seconds] [seed]"""
 import sys, os, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
 import torch
 from dwarf_bench_amd import ops
+from tests import fuzz_gpu_testlib as fg
+from tests import fuzz_testlib as ft
 
 budget = float(sys.argv[1]) if len(sys.argv) > 1 else 60.0
 seed = int(sys.argv[2]) if len(sys.argv) > 2 else 1
 rng = np.random.default_rng(seed)
 t_end = time.time() + budget
 done = {"scan": 0, "dense": 0, "sort": 0, "groupby": 0, "xscan": 0, "reduce": 0, "join": 0, "radix_join": 0, "crowded": 0, "ujoin": 0,
-        "groupby_hash": 0, "cuckoo": 0, "slab": 0}
+        "groupby_hash": 0, "cuckoo": 0, "slab": 0, "plans": 0}
+done.update({name: 0 for name in ft.OPERATORS})
+ROW_ID_DRAWS = 4  # per operator and round
+sweeps = {name: (fg.Sweep(name, 1 << 20, seed), fg.endless(name, 1000 * seed + 7)) for name in ft.OPERATORS}
+plans = ft.plan_draws(np.random.default_rng(seed), plans=1 << 30)
 
 
 def rand_n():
@@ -241,6 +251,18 @@ while time.time() < t_end:
         lv, lf = (t.cpu().numpy().view(np.uint32) for t in st_.lookup(torch.from_numpy(uq.view(np.int32)).cuda()))
         assert lf.all() and np.array_equal(sk[lv], uq), ("slab lookup", ns, buckets)
         done["slab"] += 1
+    # ---- the row-id operators: seeded draws with every dimension drawn on its own, and one random query plan
+    for name, (sweep, cases) in sweeps.items():
+        for _ in range(ROW_ID_DRAWS):
+            case = next(cases)
+            try:
+                sweep.step(case)
+            except AssertionError as e:
+                raise AssertionError(f"{name}: {fg.describe(case)}: {e}") from e
+            done[name] += 1
+    plan = next(plans)
+    fg.check_plan(plan, fg.run_plan(plan))
+    done["plans"] += 1
     if it % 10 == 0:
         print(f"{it} iterations {done}", flush=True)
 print("fuzz ok", it, done)
