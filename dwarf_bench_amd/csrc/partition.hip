@@ -5,7 +5,9 @@
 // 512+ buckets; both histograms from ONE read of the keys up to 81920 partitions, above that level 0 leaves every row's
 // level-1 bucket as a 16-bit column for the level-1 histogram to read instead of the pairs).  partition.hpp holds what
 // callers need: the hashes, the geometry, the layout of `meta`, and the plan (jl_side_plan) that jl_partition_side
-// launches.
+// launches.  Of the histograms, jl_hist1 and jl_hist1d stream through jl_stream, and they and jl_hist0 flush through
+// jl_hist_flush_add; jl_hist0's stream, jl_hist_fused / fused16 and the two reduces are spelled out ("what the
+// histogram kernels share" below).
 #include "dbhip_common.hpp"
 #include "partition.hpp"
 
@@ -35,6 +37,35 @@ __host__ __device__ __forceinline__ size_t jl_group_rows(size_t n, unsigned tile
   return (tiles + kJlGroups - 1) / kJlGroups * tile;
 }
 
+// ---- what the histogram kernels share -------------------------------------------------------------------------------
+// All five zero an LDS histogram, let workgroup w of a group stride over a row range with several independent loads per
+// lane per step, count each row, and flush.  The stream and the flush below are that text once for the kernels that
+// compile to the same instructions through them (profiles/r23_partition_isa.txt); jl_hist0's stream, both
+// fused kernels and the two reduces come out with a branch or two registers the other way round, and keep their text.
+
+// Workgroup `w` of `wgs` strides over the elements [lo, hi) of `src`: LOADS independent loads per lane per step, all of
+// a step issued before the first use, each(element) for every element in range.
+template <auto THREADS, int LOADS, class T, class Each>
+__device__ __forceinline__ void jl_stream(const T *src, size_t lo, size_t hi, unsigned w, unsigned wgs, Each each) {
+  for (size_t i = lo + static_cast<size_t>(w) * LOADS * THREADS + threadIdx.x; i < hi;
+       i += static_cast<size_t>(wgs) * LOADS * THREADS) {
+    T v[LOADS];
+#pragma unroll
+    for (int j = 0; j < LOADS; ++j) v[j] = i + j * THREADS < hi ? src[i + j * THREADS] : T{};
+#pragma unroll
+    for (int j = 0; j < LOADS; ++j)
+      if (i + j * THREADS < hi) each(v[j]);
+  }
+}
+
+// the non-zero counters of the LDS histogram onto the 64-bit global counters dst[0 .. words)
+template <auto THREADS>
+__device__ __forceinline__ void jl_hist_flush_add(const unsigned *s_hist, unsigned words, unsigned long long *dst) {
+  __syncthreads();
+  for (unsigned i = threadIdx.x; i < words; i += THREADS)
+    if (s_hist[i]) atomicAdd(&dst[i], static_cast<unsigned long long>(s_hist[i]));
+}
+
 template <bool RANK>
 __global__ __launch_bounds__(kJlThreads) void jl_hist0_kernel(const unsigned *__restrict__ keys, size_t n, size_t group_rows,
                                                               unsigned parts, unsigned k2_shift,
@@ -47,6 +78,8 @@ __global__ __launch_bounds__(kJlThreads) void jl_hist0_kernel(const unsigned *__
   if (lo >= hi) return;
   for (unsigned i = threadIdx.x; i < k1; i += kJlThreads) s_hist[i] = 0;
   __syncthreads();
+  // (jl_stream<kJlThreads, 4>, kept inline: through it the loop steps its index and address differently, 246
+  //  instructions for 251)
   for (size_t i = lo + static_cast<size_t>(w) * 4 * kJlThreads + threadIdx.x; i < hi;
        i += static_cast<size_t>(kJlHistWgPerGroup) * 4 * kJlThreads) {  // four independent loads per lane per step
     unsigned k[4];
@@ -56,9 +89,7 @@ __global__ __launch_bounds__(kJlThreads) void jl_hist0_kernel(const unsigned *__
     for (int j = 0; j < 4; ++j)
       if (i + j * kJlThreads < hi) atomicAdd(&s_hist[jl_pid_sel<RANK>(k[j], parts) >> k2_shift], 1u);
   }
-  __syncthreads();
-  for (unsigned i = threadIdx.x; i < k1; i += kJlThreads)
-    if (s_hist[i]) atomicAdd(&counts_g[static_cast<size_t>(group) * k1 + i], static_cast<unsigned long long>(s_hist[i]));
+  jl_hist_flush_add<kJlThreads>(s_hist, k1, counts_g + static_cast<size_t>(group) * k1);
 }
 
 // ---- both levels' histograms in ONE read of the keys (parts <= 32768: the counters fit 128 KiB of LDS) --------------
@@ -72,6 +103,9 @@ constexpr unsigned kJlFusedThreads = 1024;  // kJlGroups x kJlFusedWgPerGroup wo
 #endif
 constexpr int kJlHistLoads = DBHIP_JL_HIST_LOADS;  // 16-byte key loads in flight per lane of the fused16 histogram
 
+// (Kept whole, as is jl_hist_fused16_kernel: with its zeroing, a stream, the ragged tail or the flush in a function of
+//  its own either kernel tests `lo < hi && aligned` or `w == 0` with the opposite branch, or swaps two registers of the
+//  store loop.  The two differ in the counter and in the unaligned path: four loads in flight here, one there.)
 __global__ __launch_bounds__(kJlFusedThreads) void jl_hist_fused_kernel(const unsigned *__restrict__ keys, size_t n, size_t group_rows,
                                                                         unsigned parts, unsigned *__restrict__ wgcnt) {
   extern __shared__ unsigned s_hist[];
@@ -190,6 +224,9 @@ __global__ __launch_bounds__(kJlFusedThreads) void jl_hist_fused16_kernel(const 
 // reduce of the packed rows; ADDS to counts1 / counts0g (zeroed with the metadata, and possibly holding the carries
 // the histogram kernel settled): one thread per WORD (two partitions) for the column sums, one wave per (row, bucket)
 // for the level-0 counts — the sum of both halves of a bucket's words
+// (One kernel with jl_hist_reduce_kernel below but for how a word is read and `+=` against `=`; as one
+//  `template <bool kPacked>` body that one kept its text and this one set up `words * 28` and `words * 32` in the
+//  other order — as it does when this very body is moved into a function unchanged.  Two kernels stay.)
 __global__ __launch_bounds__(256) void jl_hist_reduce16_kernel(const unsigned *__restrict__ wgcnt, unsigned parts, unsigned k1,
                                                                unsigned k2, unsigned long long *counts0g,
                                                                unsigned long long *counts1) {
@@ -559,18 +596,10 @@ __global__ __launch_bounds__(kJlThreads) void jl_hist1_kernel(const u32x2 *__res
   if (lo + static_cast<size_t>(w) * 4 * kJlThreads >= hi) return;
   for (unsigned i = threadIdx.x; i < k2; i += kJlThreads) s_hist[i] = 0;
   __syncthreads();
-  for (size_t i = lo + static_cast<size_t>(w) * 4 * kJlThreads + threadIdx.x; i < hi;
-       i += static_cast<size_t>(kJlHist1WgPerBucket) * 4 * kJlThreads) {
-    unsigned k[4];  // the level-0 output is (key, row id) pairs: the histogram reads them whole (8 bytes per row)
-#pragma unroll
-    for (int j = 0; j < 4; ++j) k[j] = i + j * kJlThreads < hi ? rows[i + j * kJlThreads].x : 0u;
-#pragma unroll
-    for (int j = 0; j < 4; ++j)
-      if (i + j * kJlThreads < hi) atomicAdd(&s_hist[jl_pid(k[j], parts) & (k2 - 1)], 1u);
-  }
-  __syncthreads();
-  for (unsigned i = threadIdx.x; i < k2; i += kJlThreads)
-    if (s_hist[i]) atomicAdd(&counts1[static_cast<size_t>(bucket) * k2 + i], static_cast<unsigned long long>(s_hist[i]));
+  // the level-0 output is (key, row id) pairs: the histogram reads them whole (8 bytes per row)
+  jl_stream<kJlThreads, 4>(rows, lo, hi, w, kJlHist1WgPerBucket,
+                           [&](u32x2 row) { atomicAdd(&s_hist[jl_pid(row.x, parts) & (k2 - 1)], 1u); });
+  jl_hist_flush_add<kJlThreads>(s_hist, k2, counts1 + static_cast<size_t>(bucket) * k2);
 }
 
 // The same histogram from the 16-bit level-1 bucket column the level-0 scatter wrote beside its pairs (jl_scatter_tile
@@ -595,28 +624,15 @@ __global__ __launch_bounds__(kJlThreads) void jl_hist1d_kernel(const unsigned sh
     for (size_t i = lo + threadIdx.x; i < a; i += kJlThreads) atomicAdd(&s_hist[digits[i] & mask], 1u);
     for (size_t i = b + threadIdx.x; i < hi; i += kJlThreads) atomicAdd(&s_hist[digits[i] & mask], 1u);
   }
-  const u32x4 *vec = reinterpret_cast<const u32x4 *>(digits);
-  const size_t va = a / 8, vb = b / 8;
-  for (size_t v = va + static_cast<size_t>(w) * 2 * kJlThreads + threadIdx.x; v < vb;
-       v += static_cast<size_t>(kJlHist1WgPerBucket) * 2 * kJlThreads) {
-    u32x4 x[2];
-    const bool second = v + kJlThreads < vb;
-    x[0] = vec[v];
-    x[1] = second ? vec[v + kJlThreads] : u32x4{0u, 0u, 0u, 0u};
+  jl_stream<kJlThreads, 2>(reinterpret_cast<const u32x4 *>(digits), a / 8, b / 8, w, kJlHist1WgPerBucket, [&](u32x4 x) {
+    const unsigned word[4] = {x.x, x.y, x.z, x.w};
 #pragma unroll
-    for (int j = 0; j < 2; ++j) {
-      if (j == 1 && !second) break;
-      const unsigned word[4] = {x[j].x, x[j].y, x[j].z, x[j].w};
-#pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        atomicAdd(&s_hist[word[q] & mask], 1u);
-        atomicAdd(&s_hist[(word[q] >> 16) & mask], 1u);
-      }
+    for (int q = 0; q < 4; ++q) {
+      atomicAdd(&s_hist[word[q] & mask], 1u);
+      atomicAdd(&s_hist[(word[q] >> 16) & mask], 1u);
     }
-  }
-  __syncthreads();
-  for (unsigned i = threadIdx.x; i < k2; i += kJlThreads)
-    if (s_hist[i]) atomicAdd(&counts1[static_cast<size_t>(bucket) * k2 + i], static_cast<unsigned long long>(s_hist[i]));
+  });
+  jl_hist_flush_add<kJlThreads>(s_hist, k2, counts1 + static_cast<size_t>(bucket) * k2);
 }
 
 // Level-1 scatter: a PERSISTENT grid of the resident workgroups over the "virtual tiles" (every level-0 bucket cut into
@@ -798,23 +814,24 @@ int jl_partition_side(const unsigned *keys, const unsigned *row_ids, size_t n, c
   // switched, level 0 followed once the level-1 histogram read pairs instead of a keys-only column)
   const unsigned k2_shift = g.log2_k2;
   const size_t group_rows = jl_group_rows(n, jl_shape_rows(plan.t0));
-  if (plan.hist == kJlHistFused16) {
-    const size_t lds = static_cast<size_t>(parts / 2) * sizeof(unsigned);
-    const hipError_t ea = hipFuncSetAttribute(reinterpret_cast<const void *>(jl_hist_fused16_kernel),
+  if (plan.hist == kJlHistFused16 || plan.hist == kJlHistFused) {
+    // a workgroup per row of wgcnt, `words` words each; the reduce: a thread per word + a wave per (row, bucket)
+    const bool packed = plan.hist == kJlHistFused16;
+    const unsigned words = packed ? parts / 2 : parts;
+    const size_t lds = static_cast<size_t>(words) * sizeof(unsigned);
+    const dim3 grid(kJlGroups * kJlFusedWgPerGroup), threads(kJlFusedThreads);
+    const hipError_t ea = hipFuncSetAttribute(packed ? reinterpret_cast<const void *>(jl_hist_fused16_kernel)
+                                                     : reinterpret_cast<const void *>(jl_hist_fused_kernel),
                                               hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds));
     if (ea != hipSuccess) return static_cast<int>(ea);
-    hipLaunchKernelGGL(jl_hist_fused16_kernel, dim3(kJlGroups * kJlFusedWgPerGroup), dim3(kJlFusedThreads), lds, s, keys, n,
-                       group_rows, parts, g.log2_k2, k1, fused_scratch, counts0, counts1);
-    const unsigned red_grid = (parts / 2 + 255) / 256 + (kJlGroups * kJlFusedWgPerGroup * k1 + 3) / 4;
-    hipLaunchKernelGGL(jl_hist_reduce16_kernel, dim3(red_grid), dim3(256), 0, s, fused_scratch, parts, k1, k2, counts0, counts1);
-  } else if (plan.hist == kJlHistFused) {
-    const hipError_t ea = hipFuncSetAttribute(reinterpret_cast<const void *>(jl_hist_fused_kernel),
-                                              hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(parts * sizeof(unsigned)));
-    if (ea != hipSuccess) return static_cast<int>(ea);
-    hipLaunchKernelGGL(jl_hist_fused_kernel, dim3(kJlGroups * kJlFusedWgPerGroup), dim3(kJlFusedThreads),
-                       parts * sizeof(unsigned), s, keys, n, group_rows, parts, fused_scratch);
-    const unsigned red_grid = (parts + 255) / 256 + (kJlGroups * kJlFusedWgPerGroup * k1 + 3) / 4;
-    hipLaunchKernelGGL(jl_hist_reduce_kernel, dim3(red_grid), dim3(256), 0, s, fused_scratch, parts, k1, k2, counts0, counts1);
+    if (packed)
+      hipLaunchKernelGGL(jl_hist_fused16_kernel, grid, threads, lds, s, keys, n, group_rows, parts, g.log2_k2, k1, fused_scratch,
+                         counts0, counts1);
+    else
+      hipLaunchKernelGGL(jl_hist_fused_kernel, grid, threads, lds, s, keys, n, group_rows, parts, fused_scratch);
+    const unsigned red_grid = (words + 255) / 256 + (kJlGroups * kJlFusedWgPerGroup * k1 + 3) / 4;
+    hipLaunchKernelGGL(packed ? jl_hist_reduce16_kernel : jl_hist_reduce_kernel, dim3(red_grid), dim3(256), 0, s, fused_scratch,
+                       parts, k1, k2, counts0, counts1);
   } else {
     hipLaunchKernelGGL(jl_hist0_kernel<false>, dim3(kJlGroups * kJlHistWgPerGroup), dim3(kJlThreads),
                        k1 * sizeof(unsigned), s, keys, n, group_rows, parts, k2_shift, k1, counts0);
