@@ -9,7 +9,8 @@ that of host/merge_sorted.hpp, and for late materialisation through a row-id lis
 aggregate_rows) that of host/take_rows.hpp, and for dictionary encoding (Dictionary, factorize, dict_combine,
 encode_columns, and the two compositions over several key columns, groupby_columns and join_pairs_columns) that of
 host/dict_encode.hpp, and for bit-packed columns (PackedColumn, BitPack, pack, unpack, select_range_packed, and SelectRows on
-a PackedColumn) that of host/bitpack.hpp.  Nothing in this module computes on the host or falls back to torch ops: without the built libraries
+a PackedColumn) that of host/bitpack.hpp, and for the Bloom filter (BloomFilter, bloom_words, bloom_build, select_in_bloom,
+SelectRows.launch_in and refine_in, semi_join with bloom_bits) that of host/bloom_filter.hpp.  Nothing in this module computes on the host or falls back to torch ops: without the built libraries
 the first call raises.
 """
 from __future__ import annotations
@@ -18,7 +19,7 @@ import ctypes as C
 
 import torch
 
-from . import _capi, bitpack_native, dict_native, merge_native, select_native, take_native
+from . import _capi, bitpack_native, bloom_native, dict_native, merge_native, select_native, take_native
 
 DEV_OK, DEV_SPIN_TIMEOUT, DEV_KEY_RANGE, DEV_TABLE_FULL, DEV_RANK_ORDER = 0, 1, 2, 4, 8
 
@@ -217,6 +218,46 @@ class SelectRows:
         at = self._last
         self.launch(col, lo, hi, rows=self.rows[at][: self.capacity], count=self.counts[at: at + 1], signed=signed,
                     negate=negate)
+
+    def launch_in(self, bloom: "BloomFilter", col: torch.Tensor, rows: torch.Tensor | None = None,
+                  count: torch.Tensor | None = None, negate: bool = False) -> None:
+        """launch() with the predicate "the Bloom filter may hold col[r]" (no false negatives; negate: "it certainly does
+        not"): the same candidates, buffers, device counts and workspace, so a chain may mix range, packed and Bloom
+        steps.  Asynchronous on the current stream; nothing is read back."""
+        if not isinstance(bloom, BloomFilter):
+            raise ValueError(f"bloom: expected a BloomFilter, got {type(bloom).__name__}")
+        _need(col, torch.int32, "col")
+        if bloom.filter.device != col.device:
+            raise ValueError(f"bloom: the filter lives on {bloom.filter.device}, col on {col.device}")
+        if rows is not None:
+            _need(rows, torch.int32, "rows")
+        elif count is not None:
+            raise ValueError("count: given without rows")
+        _need_count(count, "count")
+        n_col = col.numel()
+        candidates = n_col if rows is None else rows.numel()
+        if candidates > self.capacity:
+            raise ValueError(f"{candidates} candidates, the plan holds {self.capacity}")
+        into = 0 if self._last is None else 1 - self._last
+        if rows is not None and rows.untyped_storage().data_ptr() == self.rows[into].untyped_storage().data_ptr():
+            into = 1 - into  # the list is a view of that buffer: write the other one
+        col_ptr, col_n, list_ptr, count_ptr = col.data_ptr() if n_col else None, n_col, None, None
+        if rows is not None and rows.numel():
+            list_ptr, count_ptr = rows.data_ptr(), count.data_ptr() if count is not None else None
+        elif rows is not None:  # an empty list has no address: the call over no rows at all
+            col_ptr, col_n = None, 0
+        _capi.check(bloom_native.probe(
+            bloom.filter.data_ptr(), bloom.n_words, bloom.seed, col_ptr, col_n, list_ptr, count_ptr,
+            rows.numel() if list_ptr else 0, bloom_native.NEGATE if negate else 0, self.rows[into].data_ptr(),
+            self.counts[into:].data_ptr(), self.ws.data_ptr(), self.ws_bytes, _stream()), "bloom_probe_u32")
+        self._last = into
+
+    def refine_in(self, bloom: "BloomFilter", col: torch.Tensor, negate: bool = False) -> None:
+        """the rows of the last launch whose value in `col` the Bloom filter may hold (negate: certainly does not hold)"""
+        if self._last is None:
+            raise ValueError("refine_in: nothing was launched on this plan")
+        at = self._last
+        self.launch_in(bloom, col, rows=self.rows[at][: self.capacity], count=self.counts[at: at + 1], negate=negate)
 
     def status(self) -> int:
         return workspace_status(self.ws)
@@ -437,6 +478,84 @@ def select_any(col_a: torch.Tensor, lo_a: int, hi_a: int, col_b: torch.Tensor, l
     (rows_a, count_a), (rows_b, count_b) = first.output(), second.output()
     sets.launch("union", rows_a, rows_b, count_a, count_b)
     return sets.result()
+
+
+# ---------------------------------------------------------------------------------------------
+# Bloom filter: build from keys, probe into row-id lists (host/bloom_filter.hpp, libdbench.so)
+# ---------------------------------------------------------------------------------------------
+def bloom_words(n_keys: int, bits_per_key: int = 16) -> int:
+    """the 64-bit words of a filter for n_keys keys: max(1, ceil(n_keys * bits_per_key / 64))"""
+    if isinstance(n_keys, bool) or not isinstance(n_keys, int) or n_keys < 0:
+        raise ValueError(f"n_keys: expected a count, got {n_keys!r}")
+    if isinstance(bits_per_key, bool) or not isinstance(bits_per_key, int) or not 1 <= bits_per_key <= 64:
+        raise ValueError(f"bits_per_key: expected an int in [1, 64], got {bits_per_key!r}")
+    words = bloom_native.words(n_keys, bits_per_key) if n_keys < (1 << 64) else 0
+    if words == 0:
+        raise ValueError(f"n_keys: {n_keys} keys at {bits_per_key} bits need 2^32 filter words or more")
+    return words
+
+
+class BloomFilter:
+    """A Bloom filter of n_words 64-bit words over 32-bit keys (one word and up to four bits per key; the format is
+    host/bloom_filter.hpp's): owns the filter (an int64 tensor) and the 256-byte workspace of build().  What
+    SelectRows.launch_in and refine_in test rows against."""
+
+    def __init__(self, n_words: int, seed: int = 0, device="cuda"):
+        if isinstance(n_words, bool) or not isinstance(n_words, int) or not 1 <= n_words < (1 << 32):
+            raise ValueError(f"n_words: expected an int in [1, 2^32 - 1], got {n_words!r}")
+        if isinstance(seed, bool) or not isinstance(seed, int) or not 0 <= seed < (1 << 32):
+            raise ValueError(f"seed: expected a uint32, got {seed!r}")
+        self.n_words, self.seed = n_words, seed
+        self.filter = torch.zeros(n_words, dtype=torch.int64, device=device)
+        self.ws_bytes = 256
+        self.ws = _ws(self.ws_bytes, device)
+
+    def build(self, col: torch.Tensor, rows: torch.Tensor | None = None, count: torch.Tensor | None = None,
+              accumulate: bool = False) -> None:
+        """Asynchronous on the current stream; nothing is read back.  The keys are col[0 .. count) (count None: all
+        rows), or with rows col[rows[i]] for i < count; count: a device int64 of one element.  accumulate: add the keys
+        to what the filter holds instead of clearing it first."""
+        _need(col, torch.int32, "col")
+        if rows is not None:
+            _need(rows, torch.int32, "rows")
+        _need_count(count, "count")
+        if self.filter.device != col.device:
+            raise ValueError(f"col: lives on {col.device}, the filter on {self.filter.device}")
+        col_ptr, n_col, _ = _column(col)
+        list_ptr, capacity, count_ptr = _column(rows, count)
+        if rows is None:
+            count_ptr = count.data_ptr() if count is not None and n_col else None
+        elif list_ptr is None:  # an empty list has no address: the build over no keys at all
+            col_ptr, n_col = None, 0
+        _capi.check(bloom_native.build(col_ptr, n_col, list_ptr, count_ptr, capacity, self.seed,
+                                       bloom_native.ACCUMULATE if accumulate else 0, self.filter.data_ptr(), self.n_words,
+                                       self.ws.data_ptr(), self.ws_bytes, _stream()), "bloom_build_u32")
+
+    def status(self) -> int:
+        return workspace_status(self.ws)
+
+
+def bloom_build(col: torch.Tensor, bits_per_key: int = 16, seed: int = 0) -> BloomFilter:
+    """a filter of bloom_words(col.numel(), bits_per_key) words holding every key of col"""
+    words = bloom_words(col.numel(), bits_per_key)
+    _need(col, torch.int32, "col")
+    bloom = BloomFilter(words, seed, col.device)
+    bloom.build(col)
+    return bloom
+
+
+def select_in_bloom(bloom: BloomFilter, col: torch.Tensor, rows: torch.Tensor | None = None,
+                    negate: bool = False) -> torch.Tensor:
+    """Row ids r (ascending, or in the order of `rows`) whose key col[r] the filter may hold — with negate those it
+    certainly does not hold.  A row id >= col.numel() raises."""
+    if not isinstance(bloom, BloomFilter):
+        raise ValueError(f"bloom: expected a BloomFilter, got {type(bloom).__name__}")
+    _need(col, torch.int32, "col")
+    if rows is not None:
+        _need(rows, torch.int32, "rows")
+    plan = SelectRows(col.numel() if rows is None else rows.numel(), col.device)
+    plan.launch_in(bloom, col, rows=rows, negate=negate)
+    return plan.result()
 
 
 # ---------------------------------------------------------------------------------------------
@@ -1708,16 +1827,51 @@ def hash_join(build_keys: torch.Tensor, probe_keys: torch.Tensor):
     return plan.result()
 
 
-def semi_join(build_keys: torch.Tensor, probe_keys: torch.Tensor, anti: bool = False) -> torch.Tensor:
+def semi_join(build_keys: torch.Tensor, probe_keys: torch.Tensor, anti: bool = False,
+              bloom_bits: int | None = None) -> torch.Tensor:
     """EXISTS / IN: the ascending probe row ids with at least one build row of the same key; anti: NOT EXISTS, the
     probe rows with none.  HashJoin.build + probe, then the rows whose match count lies in [1, 0xFFFFFFFF] (outside it
     for anti).  The join's key contract holds: 0xFFFFFFFF is the empty-slot sentinel, a build row carrying it is dropped
-    and flagged (DEV_KEY_RANGE: this call raises), a probe row carrying it has no match."""
+    and flagged (DEV_KEY_RANGE: this call raises), a probe row carrying it has no match.
+    bloom_bits: a number of filter bits per build key (1 .. 64) puts a Bloom filter of the build keys in front: only
+    the probe rows it lets through are joined (their count is read back once, to size the join), and for anti the rows
+    it certainly rules out are united with the survivors that found no partner.  The answer is the same tensor."""
+    if bloom_bits is not None:
+        return _semi_join_prefiltered(build_keys, probe_keys, anti, bloom_bits)
     plan = HashJoin(build_keys.numel(), probe_keys.numel(), build_keys.device)
     plan.build(build_keys)
     plan.probe(probe_keys)
     _, cnt, _ = plan.result()
     return select_range(cnt, 1, 0xFFFFFFFF, negate=anti)
+
+
+def _semi_join_prefiltered(build_keys: torch.Tensor, probe_keys: torch.Tensor, anti: bool, bloom_bits: int) -> torch.Tensor:
+    n_build, n_probe = build_keys.numel(), probe_keys.numel()
+    words = bloom_words(n_build, bloom_bits)
+    _need(build_keys, torch.int32, "build_keys")
+    _need(probe_keys, torch.int32, "probe_keys")
+    device = build_keys.device
+    bloom = BloomFilter(words, 0, device)
+    bloom.build(build_keys)
+    sel = SelectRows(n_probe, device)
+    sel.launch_in(bloom, probe_keys)
+    k = sel.count()  # the one read-back in front of the join: it sizes the join's probe side
+    survivors = sel.rows[sel._last][:k]  # ascending probe row ids; the view stays intact through the plan's next call
+    kept_keys = TakeRows(k, 1, device)
+    kept_keys.launch(probe_keys, survivors)
+    join = HashJoin(n_build, k, device)
+    join.build(build_keys)
+    join.probe(kept_keys.outs[0][:k])
+    _, cnt, _ = join.result()
+    at = select_range(cnt, 1, 0xFFFFFFFF, negate=anti)  # positions in `survivors`
+    rows = take(survivors, at)
+    if not anti:
+        return rows
+    sel.launch_in(bloom, probe_keys, negate=True)  # the rows the filter rules out: no partner, without the join
+    certain, certain_count = sel.output()
+    sets = RowSets(n_probe, rows.numel(), device)
+    sets.launch("union", certain, rows, certain_count, None)
+    return sets.result()
 
 
 class JoinPairs:

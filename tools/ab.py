@@ -124,6 +124,17 @@ the contract numbers come from bench.py.
                   to 16, wider ones are reported.  Report only: pack and the dense unpack against their bytes and against
                   torch.clone of the 32-bit column; unpack through lists of 1 % and 50 % of the rows, ascending and shuffled,
                   against dbench_take_u32 on the decoded column.  BITPACK_PARTS=select,pack,unpack,take picks parts
+  bloom [lg]      Bloom filter (ops.BloomFilter, SelectRows.launch_in, ops.semi_join with bloom_bits: host/bloom_filter.hpp), same
+                  protocol as bitpack (legs alternating, REPS repetitions of a median of 5, HIP events, every leg's result
+                  checked); report only, nothing is gated.  BLOOM_PARTS=build,probe,semi picks parts.
+                  build: 2^24 rows (BLOOM_BUILD_LG), distinct keys and keys in [1, 10000] at 16 bits per key, the distinct keys
+                  also into filters of 2^10, 2^16, 2^20 and 2^26 words; each against the same build without test-before-set
+                  (bloom_filter.cpp compiled with -DDBENCH_BLOOM_ALWAYS_SET into _lib/ab/, built on first use).
+                  probe: 2^lg rows (default 26) at 0 / 1 / 50 / 100 % of rows holding a key of the filter, filters of those
+                  four sizes, against select_range on the same column (the stream the mark kernel shares) and
+                  HashJoin.probe of the same rows (the gather it stands in front of).
+                  semi: ops.semi_join with and without bloom_bits=16, build sides of 2^16, 2^20, 2^24 distinct keys, a probe
+                  side of 2^lg, 0 / 1 / 10 / 50 / 100 % of probe rows with a partner
   launch-join [lg] / launch-sort [lg] / launch-all
                   a few untimed calls and nothing else: the program to put behind `rocprofv3 --kernel-trace --stats` or
                   `--pmc` (tools/pmc_kernel_counters.sh); tools/prof_show.py prints the tables
@@ -1150,6 +1161,126 @@ def bitpack(lg):
         del codes, packer, pc
 
 
+def _bloom_always_set_lib():
+    """bloom_filter.cpp built without test-before-set (measurement only) -> its ctypes handle"""
+    import ctypes
+    import subprocess
+    from dwarf_bench_amd import bloom_native
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    host, lib = os.path.join(root, "dwarf_bench_amd", "host"), os.path.join(root, "dwarf_bench_amd", "_lib")
+    so = os.path.join(lib, "ab", "libbloom_always_set.so")
+    if not os.path.exists(so) or os.path.getmtime(so) < os.path.getmtime(os.path.join(host, "bloom_filter.cpp")):
+        os.makedirs(os.path.dirname(so), exist_ok=True)
+        subprocess.run([os.environ.get("HIPCC", "/opt/rocm/bin/hipcc"), "-O2", "-std=c++17", "-fPIC", "-shared", "-DHIP_ENABLED",
+                        "-DDBENCH_BLOOM_ALWAYS_SET", "-I", host, "-I", os.path.join(root, "include"), "-I",
+                        os.path.join(root, "dwarf_bench_amd", "csrc"), "-x", "hip", "--offload-arch=gfx950",
+                        os.path.join(host, "bloom_filter.cpp"), "-o", so, "-L", lib, "-ldbench", "-ldbhip",
+                        "-Wl,-rpath,$ORIGIN/.."], check=True)
+    bloom_native.lib()  # libdbhip.so and libdbench.so first
+    h = ctypes.CDLL(so)
+    res, args = bloom_native.ENTRY_POINTS["dbench_bloom_build_u32"]
+    h.dbench_bloom_build_u32.restype, h.dbench_bloom_build_u32.argtypes = res, args
+    return h
+
+
+def bloom(lg):
+    """BLOOM_PARTS=build,probe,semi picks parts; BLOOM_BUILD_LG the build's rows"""
+    reps = int(os.environ.get("REPS", "3"))
+    parts = os.environ.get("BLOOM_PARTS", "build,probe,semi").split(",")
+    n = 1 << (lg or 26)
+    nb = 1 << int(os.environ.get("BLOOM_BUILD_LG", "24"))
+    sizes = [1 << 10, 1 << 16, 1 << 20, 1 << 26]
+
+    def run(name, legs_fn, ok, report, extra=""):
+        legs = {leg: [] for leg in legs_fn}
+        for _ in range(reps):  # alternating
+            for leg, fn in legs_fn.items():
+                legs[leg].append(median(times(fn, 5)))
+        mine = median(sorted(legs[report[0]]))
+        ratios = "  ".join(f"{other} / {report[0]} x{median(sorted(legs[other])) / mine:5.2f}" for other in report[1:])
+        _merge_row(name, legs, ok, None, None, f"  (no floor) {ratios}{extra}")
+
+    def distinct(count, salt):  # distinct 32-bit keys: an odd multiple of a permutation; salt moves the set
+        g = torch.Generator(device="cuda")
+        g.manual_seed(salt)
+        return bits32((torch.randperm(count, device="cuda", generator=g) * 2654435761 + salt * 2**27) % 2**32)
+
+    keys = distinct(nb, 1)
+    if "build" in parts:
+        always = _bloom_always_set_lib()
+        few = ops.gen_uniform_u32(nb, 5, 1, 10000)
+        for name, col, words in [("distinct 16 b/key", keys, ops.bloom_words(nb, 16)), ("[1, 10000] 16 b/key", few, ops.bloom_words(nb, 16))] + \
+                [(f"distinct {w} words", keys, w) for w in sizes]:
+            tested, plain = ops.BloomFilter(words), ops.BloomFilter(words)
+            unconditional = lambda: always.dbench_bloom_build_u32(  # noqa: E731
+                col.data_ptr(), nb, None, None, 0, 0, 0, plain.filter.data_ptr(), words, plain.ws.data_ptr(), 256,
+                torch.cuda.current_stream().cuda_stream)
+            tested.build(col)
+            assert unconditional() == 0
+            ok = torch.equal(tested.filter, plain.filter) and tested.status() == 0
+            fill = float((tested.filter.view(torch.uint8).to(torch.int32).unsqueeze(1) >> torch.arange(8, device="cuda") & 1).float().mean()) if words <= 1 << 22 else float("nan")
+            run(f"build n=2^{nb.bit_length() - 1} {name} ({8 * words >> 10} KiB)", {"test-before-set": lambda: tested.build(col), "always-set": unconditional,
+                "clone": lambda: torch.clone(col)}, ok, ("test-before-set", "always-set", "clone"),
+                f"  {nb / median(times(lambda: tested.build(col), 5)) / 1e3:6.2f} G keys/s  fill {fill:.3f}")
+            del tested, plain
+    if "probe" in parts:
+        strangers = distinct(n, 2)  # salt 2: disjoint from `keys` with overwhelming share; the check below is exact anyway
+        for words in sizes:
+            held = keys[: min(4 * words, nb)].contiguous()
+            bl = ops.BloomFilter(words)
+            bl.build(held)
+            join = ops.HashJoin(held.numel(), n)
+            join.build(held)
+            for share in (0.0, 0.01, 0.5, 1.0):
+                g = torch.Generator(device="cuda")
+                g.manual_seed(int(share * 100) + 7)
+                pick = torch.rand(n, device="cuda", generator=g) < share
+                col = torch.where(pick, held[torch.randint(0, held.numel(), (n,), device="cuda", generator=g)], strangers)
+                del pick
+                mine_plan, range_plan = ops.SelectRows(n), ops.SelectRows(n)
+                hi = 0 if share == 0 else min(int(share * 2**32), 2**32 - 1)
+                lo = 1 if share == 0 else 0  # lo > hi: nothing kept
+                mine = lambda: mine_plan.launch_in(bl, col)  # noqa: E731
+                stream = lambda: range_plan.launch(col, lo, hi)  # noqa: E731
+                gather = lambda: join.probe(col)  # noqa: E731
+                mine(), gather()
+                kept = mine_plan.count()
+                _, cnt, _ = join.result()
+                partners = int((cnt != 0).sum())
+                ok = kept >= partners and mine_plan.status() == 0 and bool((cnt[mine_plan.result().long()] != 0).sum() == partners)
+                run(f"probe n=2^{lg or 26} filter {8 * words >> 10} KiB partners {100 * partners / n:5.1f} % kept {100 * kept / n:5.1f} %",
+                    {"bloom": mine, "select_range": stream, "join probe": gather}, ok, ("bloom", "select_range", "join probe"),
+                    f"  {n / median(times(mine, 5)) / 1e3:6.2f} G rows/s")
+                del col, mine_plan, range_plan
+            del bl, join, held
+        del strangers
+    if "semi" in parts:
+        strangers = distinct(n, 2)
+        for lb in (16, 20, 24):
+            build = distinct(1 << lb, 1)
+            for share in (0.0, 0.01, 0.1, 0.5, 1.0):
+                g = torch.Generator(device="cuda")
+                g.manual_seed(int(share * 100) + 11)
+                pick = torch.rand(n, device="cuda", generator=g) < share
+                probe = torch.where(pick, build[torch.randint(0, build.numel(), (n,), device="cuda", generator=g)], strangers)
+                del pick
+                plain = lambda: ops.semi_join(build, probe)  # noqa: E731
+                pre = lambda: ops.semi_join(build, probe, bloom_bits=16)  # noqa: E731
+                a, b = plain(), pre()
+                ok = torch.equal(a, b)
+                m = a.numel()
+                del a, b
+                legs = {"prefiltered": [], "plain": []}
+                for _ in range(reps):
+                    legs["prefiltered"].append(median(times(pre, 5)))
+                    legs["plain"].append(median(times(plain, 5)))
+                verdict = "wins" if max(legs["prefiltered"]) <= min(legs["plain"]) else "MISSED"
+                _merge_row(f"semi_join build 2^{lb} probe 2^{lg or 26} partners {100 * m / n:5.1f} %", legs, ok, None, None,
+                           f"  prefilter {verdict}  x{median(sorted(legs['plain'])) / median(sorted(legs['prefiltered'])):5.2f}")
+                del probe
+            del build
+
+
 def launch_sort_pairs(lg):
     n = 1 << (lg or 24)
     keys0 = ops.gen_uniform_u32(n, 42, 0, 2**32 - 1)
@@ -1853,7 +1984,7 @@ MODES = {"radix": radix, "ramp": ramp, "radix-idle": radix_idle, "radix-stream":
          "join-pairs": join_pairs, "launch-join-pairs": launch_join_pairs, "topk": topk, "launch-topk": launch_topk,
          "groupby-sorted": groupby_sorted, "launch-groupby-sorted": launch_groupby_sorted,
          "window": window, "launch-window": launch_window, "sorted-search": sorted_search, "range-join": range_join,
-         "selection": selection, "merge": merge, "take": take, "dict": dict_encoding, "bitpack": bitpack}
+         "selection": selection, "merge": merge, "take": take, "dict": dict_encoding, "bitpack": bitpack, "bloom": bloom}
 
 if __name__ == "__main__":
     if len(sys.argv) < 2 or sys.argv[1] not in MODES:
