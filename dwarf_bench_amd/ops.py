@@ -10,16 +10,18 @@ aggregate_rows) that of host/take_rows.hpp, and for dictionary encoding (Diction
 encode_columns, and the two compositions over several key columns, groupby_columns and join_pairs_columns) that of
 host/dict_encode.hpp, and for bit-packed columns (PackedColumn, BitPack, pack, unpack, select_range_packed, and SelectRows on
 a PackedColumn) that of host/bitpack.hpp, and for the Bloom filter (BloomFilter, bloom_words, bloom_build, select_in_bloom,
-SelectRows.launch_in and refine_in, semi_join with bloom_bits) that of host/bloom_filter.hpp.  Nothing in this module computes on the host or falls back to torch ops: without the built libraries
+SelectRows.launch_in and refine_in, semi_join with bloom_bits) that of host/bloom_filter.hpp, and for approximate distinct
+counts (HyperLogLog, approx_count_distinct, hll_relative_error) that of host/hll_sketch.hpp.  Nothing in this module computes on the host or falls back to torch ops: without the built libraries
 the first call raises.
 """
 from __future__ import annotations
 
 import ctypes as C
+import math
 
 import torch
 
-from . import _capi, bitpack_native, bloom_native, dict_native, merge_native, select_native, take_native
+from . import _capi, bitpack_native, bloom_native, dict_native, hll_native, merge_native, select_native, take_native
 
 DEV_OK, DEV_SPIN_TIMEOUT, DEV_KEY_RANGE, DEV_TABLE_FULL, DEV_RANK_ORDER = 0, 1, 2, 4, 8
 
@@ -556,6 +558,110 @@ def select_in_bloom(bloom: BloomFilter, col: torch.Tensor, rows: torch.Tensor | 
     plan = SelectRows(col.numel() if rows is None else rows.numel(), col.device)
     plan.launch_in(bloom, col, rows=rows, negate=negate)
     return plan.result()
+
+
+# ---------------------------------------------------------------------------------------------
+# HyperLogLog: approximate COUNT(DISTINCT), mergeable sketches (host/hll_sketch.hpp, libdbench.so)
+# ---------------------------------------------------------------------------------------------
+def _hll_p(p) -> int:
+    if isinstance(p, bool) or not isinstance(p, int) or not hll_native.MIN_P <= p <= hll_native.MAX_P:
+        raise ValueError(f"p: expected an int in [{hll_native.MIN_P}, {hll_native.MAX_P}], got {p!r}")
+    return p
+
+
+def hll_relative_error(p: int) -> float:
+    """the standard error of a sketch of 2^p registers, relative to the count: 1.04 / sqrt(2^p)"""
+    return 1.04 / math.sqrt(1 << _hll_p(p))
+
+
+def _hll_columns(cols):
+    """one tensor or a sequence of up to four int32 columns of equal length -> the list"""
+    cols = [cols] if torch.is_tensor(cols) else list(cols)
+    if not 1 <= len(cols) <= hll_native.MAX_COLS:
+        raise ValueError(f"cols: expected one to {hll_native.MAX_COLS} columns, got {len(cols)}")
+    for i, c in enumerate(cols):
+        if not torch.is_tensor(c):
+            raise ValueError(f"cols[{i}]: expected a tensor, got {type(c).__name__}")
+        if c.numel() != cols[0].numel():
+            raise ValueError(f"cols[{i}]: {c.numel()} rows, cols[0] has {cols[0].numel()}: columns of one table")
+    for i, c in enumerate(cols):
+        _need(c, torch.int32, f"cols[{i}]")
+    return cols
+
+
+class HyperLogLog:
+    """A HyperLogLog sketch of 2^p one-byte registers over the rows of one to four int32 columns (the format is
+    host/hll_sketch.hpp's): owns the registers (uint8, 2^p), the histogram of their values (int32, 64) that every build and
+    merge writes, and the workspace.  estimate() is the one read-back: the 256 bytes of the histogram."""
+
+    def __init__(self, p: int = 12, seed: int = 0, device="cuda"):
+        self.p = _hll_p(p)
+        if isinstance(seed, bool) or not isinstance(seed, int) or not 0 <= seed < (1 << 32):
+            raise ValueError(f"seed: expected a uint32, got {seed!r}")
+        self.seed, self.m = seed, 1 << p
+        self.registers = torch.zeros(self.m, dtype=torch.uint8, device=device)
+        self.hist = torch.zeros(hll_native.HIST_WORDS, dtype=torch.int32, device=device)
+        self.hist[0] = self.m  # the histogram of an empty sketch
+        self.ws_bytes = hll_native.workspace_bytes(p)
+        self.ws = _ws(self.ws_bytes, device)
+
+    def build(self, cols, rows: torch.Tensor | None = None, count: torch.Tensor | None = None,
+              accumulate: bool = False) -> None:
+        """Asynchronous on the current stream; nothing is read back.  The keys are the tuples of rows 0 .. count (count
+        None: all rows), or with rows those of rows[i] for i < count; count: a device int64 of one element.  accumulate: the
+        max with what the sketch holds instead of the sketch of these rows alone."""
+        cols = _hll_columns(cols)
+        if rows is not None:
+            _need(rows, torch.int32, "rows")
+        _need_count(count, "count")
+        if self.registers.device != cols[0].device:
+            raise ValueError(f"cols: live on {cols[0].device}, the sketch on {self.registers.device}")
+        n_col = cols[0].numel()
+        ptrs = [c.data_ptr() if n_col else None for c in cols]
+        list_ptr, capacity, count_ptr = _column(rows, count)
+        if rows is None:
+            count_ptr = count.data_ptr() if count is not None and n_col else None
+        elif list_ptr is None:  # an empty list has no address: the build over no rows at all
+            ptrs, n_col = [None] * len(cols), 0
+        _capi.check(hll_native.build(ptrs, n_col, list_ptr, count_ptr, capacity, self.seed,
+                                     hll_native.ACCUMULATE if accumulate else 0, self.p, self.registers.data_ptr(),
+                                     self.hist.data_ptr(), self.ws.data_ptr(), self.ws_bytes, _stream()), "hll_build_u32")
+
+    def merge(self, other: "HyperLogLog") -> None:
+        """self becomes the sketch of the union: max(self, other) register by register.  Asynchronous."""
+        if not isinstance(other, HyperLogLog):
+            raise ValueError(f"other: expected a HyperLogLog, got {type(other).__name__}")
+        if (other.p, other.seed) != (self.p, self.seed):
+            raise ValueError(f"other: a sketch of p = {other.p}, seed {other.seed} does not merge into p = {self.p}, seed {self.seed}")
+        if other.registers.device != self.registers.device:
+            raise ValueError(f"other: lives on {other.registers.device}, the sketch on {self.registers.device}")
+        if not self.registers.is_cuda:
+            raise ValueError(f"merge: expected sketches on the GPU, got {self.registers.device}")
+        _capi.check(hll_native.merge(self.registers.data_ptr(), other.registers.data_ptr(), self.p, self.hist.data_ptr(),
+                                     self.ws.data_ptr(), self.ws_bytes, _stream()), "hll_merge")
+
+    def estimate(self) -> float:
+        """the estimated number of distinct rows: reads the histogram back (256 bytes; synchronises) and raises on a
+        flagged status word"""
+        hist = self.hist.cpu().tolist()
+        _check_status(self.ws, "HyperLogLog")
+        e = hll_native.estimate(hist, self.p)
+        if e < 0:
+            raise _capi.DbhipError(f"HyperLogLog: the histogram {hist} is not one of 2^{self.p} registers")
+        return e
+
+    def status(self) -> int:
+        return workspace_status(self.ws)
+
+
+def approx_count_distinct(cols, rows: torch.Tensor | None = None, p: int = 12, seed: int = 0) -> float:
+    """the approximate number of distinct rows (tuples) of one to four int32 columns, over all rows or those of a row-id
+    list: within hll_relative_error(p) of the truth, as a standard error.  A row id >= the columns' length raises."""
+    _hll_p(p)
+    cols = _hll_columns(cols)
+    sketch = HyperLogLog(p, seed, cols[0].device)
+    sketch.build(cols, rows=rows)
+    return sketch.estimate()
 
 
 # ---------------------------------------------------------------------------------------------

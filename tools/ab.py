@@ -135,6 +135,15 @@ the contract numbers come from bench.py.
                   HashJoin.probe of the same rows (the gather it stands in front of).
                   semi: ops.semi_join with and without bloom_bits=16, build sides of 2^16, 2^20, 2^24 distinct keys, a probe
                   side of 2^lg, 0 / 1 / 10 / 50 / 100 % of probe rows with a partner
+  hll             HyperLogLog (ops.HyperLogLog: host/hll_sketch.hpp), same protocol as bloom (legs alternating, REPS repetitions of a
+                  median of 5, HIP events, registers and histogram checked against the second build); report only, nothing
+                  is gated.  2^20, 2^24 and 2^26 rows (HLL_LGS) at p = 12 and 14 (HLL_PS); all rows distinct, keys in
+                  [1, 10000], one hot key (99 % of the rows), sorted keys, two columns, and lists of 1 % and 50 % of the rows
+                  (HLL_SHAPES).  Legs: the sketch, the same build without test-before-set (hll_sketch.cpp compiled with
+                  -DDBENCH_HLL_ALWAYS_MAX into _lib/ab/, built on first use), the dictionary build behind ops.factorize
+                  (its cardinality; capacity = the true count), torch.unique(col).numel(), and select_range on the same
+                  column as the stream yardstick.  The floor, HELD or MISSED: the sketch's slowest repetition against the
+                  faster exact route's fastest.  The estimate's relative error is printed for every shape
   launch-join [lg] / launch-sort [lg] / launch-all
                   a few untimed calls and nothing else: the program to put behind `rocprofv3 --kernel-trace --stats` or
                   `--pmc` (tools/pmc_kernel_counters.sh); tools/prof_show.py prints the tables
@@ -1281,6 +1290,106 @@ def bloom(lg):
             del build
 
 
+def _hll_always_max_lib():
+    """hll_sketch.cpp built without test-before-set (measurement only) -> its ctypes handle"""
+    import ctypes
+    import subprocess
+    from dwarf_bench_amd import hll_native
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    host, lib = os.path.join(root, "dwarf_bench_amd", "host"), os.path.join(root, "dwarf_bench_amd", "_lib")
+    so = os.path.join(lib, "ab", "libhll_always_max.so")
+    if not os.path.exists(so) or os.path.getmtime(so) < os.path.getmtime(os.path.join(host, "hll_sketch.cpp")):
+        os.makedirs(os.path.dirname(so), exist_ok=True)
+        subprocess.run([os.environ.get("HIPCC", "/opt/rocm/bin/hipcc"), "-O2", "-std=c++17", "-fPIC", "-shared", "-DHIP_ENABLED",
+                        "-DDBENCH_HLL_ALWAYS_MAX", "-I", host, "-I", os.path.join(root, "include"), "-I",
+                        os.path.join(root, "dwarf_bench_amd", "csrc"), "-x", "hip", "--offload-arch=gfx950",
+                        os.path.join(host, "hll_sketch.cpp"), "-o", so, "-L", lib, "-ldbench", "-ldbhip",
+                        "-Wl,-rpath,$ORIGIN/.."], check=True)
+    hll_native.lib()  # libdbhip.so and libdbench.so first
+    h = ctypes.CDLL(so)
+    res, args = hll_native.ENTRY_POINTS["dbench_hll_build_u32"]
+    h.dbench_hll_build_u32.restype, h.dbench_hll_build_u32.argtypes = res, args
+    return h
+
+
+def hll(_):
+    """HLL_LGS=20,24,26 picks the sizes, HLL_PS=12,14 the precisions, HLL_SHAPES a subset of the shape names, separated by ;"""
+    import ctypes
+    reps = int(os.environ.get("REPS", "3"))
+    lgs = [int(x) for x in os.environ.get("HLL_LGS", "20,24,26").split(",")]
+    ps = [int(x) for x in os.environ.get("HLL_PS", "12,14").split(",")]
+    names = ("distinct", "[1, 10000]", "one hot key", "sorted", "two columns", "list 1 %", "list 50 %")
+    shapes = [s for s in os.environ.get("HLL_SHAPES", ";".join(names)).split(";") if s in names]  # (a name holds a comma)
+    always = _hll_always_max_lib()
+    stream_ptr = lambda: torch.cuda.current_stream().cuda_stream  # noqa: E731
+
+    for lg in lgs:
+        n = 1 << lg
+        g = torch.Generator(device="cuda")
+        g.manual_seed(lg)
+        for shape in shapes:
+            second = rows = None
+            if shape in ("distinct", "list 1 %", "list 50 %"):  # an odd multiple of a permutation
+                col = bits32((torch.randperm(n, device="cuda", generator=g) * 2654435761) % 2**32)
+            elif shape == "[1, 10000]":
+                col = ops.gen_uniform_u32(n, 5, 1, 10000)
+            elif shape == "one hot key":  # 99 % of the rows hold one key
+                col = bits32(torch.randint(0, 2**32, (n,), device="cuda", generator=g))
+                col[torch.rand(n, device="cuda", generator=g) < 0.99] = 12345
+            elif shape == "sorted":
+                col = bits32(torch.sort(torch.randint(0, n // 4, (n,), device="cuda", generator=g))[0])
+            else:  # 2^16 x up to 2^10 tuples
+                col = ops.gen_uniform_u32(n, 6, 0, (1 << 16) - 1)
+                second = ops.gen_uniform_u32(n, 7, 0, (1 << 10) - 1)
+            if shape.startswith("list"):
+                m = n // 100 if shape == "list 1 %" else n // 2
+                rows = torch.randint(0, n, (m,), device="cuda", generator=g).to(torch.int32)  # unsorted, rows repeat
+            cols = [col] if second is None else [col, second]
+            # the exact routes: the dictionary build's cardinality and torch.unique, through the list where there is one
+            if second is not None:
+                exact_in = None
+                truth = int(torch.unique((u64(col) << 32) | u64(second)).numel())
+            else:
+                exact_in = (lambda: col) if rows is None else (lambda: ops.take(col, rows))
+                truth = int(torch.unique(exact_in()).numel())
+            legs_exact = {}
+            if exact_in is not None:
+                d = ops.Dictionary(rows.numel() if rows is not None else n, max(truth, 1))
+                legs_exact["factorize"] = lambda: d.build(exact_in())
+                legs_exact["torch.unique"] = (lambda: torch.unique(col).numel()) if rows is None else (lambda: torch.unique(col[rows.long()]).numel())
+                legs_exact["factorize"]()
+                assert d.count() == truth
+            else:  # two columns: encode_columns' composite codes, and torch.unique over the 64-bit pairs
+                legs_exact["torch.unique"] = lambda: torch.unique((u64(col) << 32) | u64(second)).numel()
+            sel = ops.SelectRows(n)
+            for p in ps:
+                mine, plain = ops.HyperLogLog(p, 0), ops.HyperLogLog(p, 0)
+                ptrs = (ctypes.c_void_p * 4)(*[c.data_ptr() for c in cols])
+                unconditional = lambda: always.dbench_hll_build_u32(  # noqa: E731
+                    ptrs, len(cols), n, rows.data_ptr() if rows is not None else None, None, rows.numel() if rows is not None else 0,
+                    0, 0, p, plain.registers.data_ptr(), plain.hist.data_ptr(), plain.ws.data_ptr(), plain.ws_bytes, stream_ptr())
+                sketch = lambda: mine.build(cols, rows=rows)  # noqa: E731
+                sketch()
+                assert unconditional() == 0
+                estimate = mine.estimate()
+                ok = torch.equal(mine.registers, plain.registers) and torch.equal(mine.hist, plain.hist) and plain.status() == 0
+                err = (estimate - truth) / truth
+                legs_fn = {"sketch": sketch, "always-max": unconditional, **legs_exact, "select_range": lambda: sel.launch(col, 0, 0)}
+                legs = {leg: [] for leg in legs_fn}
+                for _ in range(reps):  # alternating
+                    for leg, fn in legs_fn.items():
+                        legs[leg].append(median(times(fn, 5)))
+                best = min(min(legs[x]) for x in legs_exact)
+                verdict = "HELD" if max(legs["sketch"]) <= best else "MISSED"
+                s = median(sorted(legs["sketch"]))
+                _merge_row(f"hll n=2^{lg} p={p} {shape}", legs, ok, None, None,
+                           f"  floor {verdict} x{best / s:7.2f}  always-max / sketch x{median(sorted(legs['always-max'])) / s:5.2f}"
+                           f"  sketch / select_range x{s / median(sorted(legs['select_range'])):5.2f}"
+                           f"  distinct {truth} estimate {estimate:.0f} error {100 * err:+.2f} % = {err / ops.hll_relative_error(p):+.2f} se")
+                del mine, plain
+            del col, second, rows, cols, sel, legs_exact
+
+
 def launch_sort_pairs(lg):
     n = 1 << (lg or 24)
     keys0 = ops.gen_uniform_u32(n, 42, 0, 2**32 - 1)
@@ -1984,7 +2093,7 @@ MODES = {"radix": radix, "ramp": ramp, "radix-idle": radix_idle, "radix-stream":
          "join-pairs": join_pairs, "launch-join-pairs": launch_join_pairs, "topk": topk, "launch-topk": launch_topk,
          "groupby-sorted": groupby_sorted, "launch-groupby-sorted": launch_groupby_sorted,
          "window": window, "launch-window": launch_window, "sorted-search": sorted_search, "range-join": range_join,
-         "selection": selection, "merge": merge, "take": take, "dict": dict_encoding, "bitpack": bitpack, "bloom": bloom}
+         "selection": selection, "merge": merge, "take": take, "dict": dict_encoding, "bitpack": bitpack, "bloom": bloom, "hll": hll}
 
 if __name__ == "__main__":
     if len(sys.argv) < 2 or sys.argv[1] not in MODES:
