@@ -57,36 +57,56 @@ __device__ __forceinline__ void load_wave_tile(i32x4 (&v)[kScanVpt], const int *
   }
 }
 
-// matches of one wave: the compare IS the ballot (v_cmp -> SGPR pair), totals are scalar popcounts
-__device__ __forceinline__ unsigned count_wave_matches(const i32x4 (&v)[kScanVpt], int filter) {
-  unsigned total = 0;
+// The 32 compare masks of a wave tile, taken ONCE (v_cmp writes the 64-bit ballot straight into an SGPR pair) and used
+// three times: popcounts for the count, the running sums for the "row empty" test and the row bases, the masks
+// themselves for the ranks and the store predicates.  before[k] = matches of the wave in rows < k; before[kScanVpt] is
+// the wave's total.
+struct WaveMasks {
+  unsigned long long b[kScanVpt][4];
+  unsigned before[kScanVpt + 1];
+};
+
+__device__ __forceinline__ void count_wave_matches(const i32x4 (&v)[kScanVpt], int filter, WaveMasks &wm) {
+  wm.before[0] = 0;
 #pragma unroll
   for (int k = 0; k < kScanVpt; ++k) {
-    total += __builtin_popcountll(__ballot(v[k].x < filter));
-    total += __builtin_popcountll(__ballot(v[k].y < filter));
-    total += __builtin_popcountll(__ballot(v[k].z < filter));
-    total += __builtin_popcountll(__ballot(v[k].w < filter));
+    wm.b[k][0] = __builtin_amdgcn_ballot_w64(v[k].x < filter);
+    wm.b[k][1] = __builtin_amdgcn_ballot_w64(v[k].y < filter);
+    wm.b[k][2] = __builtin_amdgcn_ballot_w64(v[k].z < filter);
+    wm.b[k][3] = __builtin_amdgcn_ballot_w64(v[k].w < filter);
+    wm.before[k + 1] = wm.before[k] + __builtin_popcountll(wm.b[k][0]) + __builtin_popcountll(wm.b[k][1]) +
+                       __builtin_popcountll(wm.b[k][2]) + __builtin_popcountll(wm.b[k][3]);
   }
-  return total;
 }
 
-// writes the wave's matches, in source order, to dst_wave[0 .. wave_total)
-// (dst_wave may point to global memory or to the LDS staging buffer)
-__device__ __forceinline__ void emit_wave_matches(const i32x4 (&v)[kScanVpt], int filter,
+__device__ __forceinline__ unsigned mbcnt_acc(unsigned long long mask, unsigned acc) {
+  return __builtin_amdgcn_mbcnt_hi(static_cast<unsigned>(mask >> 32),
+                                   __builtin_amdgcn_mbcnt_lo(static_cast<unsigned>(mask), acc));
+}
+
+// writes the wave's matches, in source order, to dst_wave[0 .. wave total); dst_wave is the same for every lane
+// (an SGPR pair), so every store is `global_store_dword voffset, data, saddr` with a 32-bit byte offset per lane: no
+// 64-bit address arithmetic on the vector unit.  Per non-empty row: one chain of eight v_mbcnt through the four masks
+// (rank of the lane's first match; a lane's matches are neighbours in the output), one add-shift to the byte offset,
+// four stores in line, each under its compare mask, the offset advancing by one v_add inside the region of the store
+// it follows.  The regions are marked likely: the compiler then lays them out in line and drops the branch over them
+// (hintless it parks three of the four stores out of line, a taken branch out and one back per component).
+// An empty row leaves by one scalar compare and branch.  29 instructions per non-empty row, 2 per empty one, where
+// the form before (ballots re-made from saved masks, four rank chains from zero, 64-bit pointer adds) took 63 and 13.
+__device__ __forceinline__ void emit_wave_matches(const i32x4 (&v)[kScanVpt], int filter, const WaveMasks &wm,
                                                   int *dst_wave) {
-  unsigned row_base = 0;
+  char *base = reinterpret_cast<char *>(dst_wave);
 #pragma unroll
   for (int k = 0; k < kScanVpt; ++k) {
-    const bool m0 = v[k].x < filter, m1 = v[k].y < filter, m2 = v[k].z < filter, m3 = v[k].w < filter;
-    const unsigned long long b0 = __ballot(m0), b1 = __ballot(m1), b2 = __ballot(m2), b3 = __ballot(m3);
-    if ((b0 | b1 | b2 | b3) == 0) continue;  // scalar branch: most rows are empty at low selectivity
-    int *dst = dst_wave + row_base + mbcnt(b0) + mbcnt(b1) + mbcnt(b2) + mbcnt(b3);
-    if (m0) *dst++ = v[k].x;
-    if (m1) *dst++ = v[k].y;
-    if (m2) *dst++ = v[k].z;
-    if (m3) *dst++ = v[k].w;
-    row_base += __builtin_popcountll(b0) + __builtin_popcountll(b1) + __builtin_popcountll(b2) +
-                __builtin_popcountll(b3);
+    if (wm.before[k + 1] == wm.before[k]) continue;  // scalar branch: most rows are empty at low selectivity
+    const bool m0 = v[k].x < filter, m1 = v[k].y < filter, m2 = v[k].z < filter;
+    const unsigned a0 = mbcnt_acc(wm.b[k][3], mbcnt_acc(wm.b[k][2], mbcnt_acc(wm.b[k][1], mbcnt_acc(wm.b[k][0], 0u))));
+    unsigned o = (a0 + wm.before[k]) * 4u;  // byte offset of the lane's first match, at most 8 KiB: a wave tile
+    // the offset advances inside the predicated region: one v_add under the store's own exec mask, no select
+    if (__builtin_expect(m0, true)) { *reinterpret_cast<int *>(base + o) = v[k].x; o += 4u; }
+    if (__builtin_expect(m1, true)) { *reinterpret_cast<int *>(base + o) = v[k].y; o += 4u; }
+    if (__builtin_expect(m2, true)) { *reinterpret_cast<int *>(base + o) = v[k].z; o += 4u; }
+    if (__builtin_expect(v[k].w < filter, true)) *reinterpret_cast<int *>(base + o) = v[k].w;
   }
 }
 
@@ -103,11 +123,6 @@ __device__ __forceinline__ void emit_wave_matches(const i32x4 (&v)[kScanVpt], in
 constexpr int kStripRows = 4;
 constexpr int kStripTrash = kWave * kStripRows * 4 + 8;  // first of the 64 per-lane trash words
 constexpr int kStageStride = kStripTrash + kWave;        // ints per wave strip; a multiple of 4: strips stay 16-byte aligned
-
-__device__ __forceinline__ unsigned mbcnt_acc(unsigned long long mask, unsigned acc) {
-  return __builtin_amdgcn_mbcnt_hi(static_cast<unsigned>(mask >> 32),
-                                   __builtin_amdgcn_mbcnt_lo(static_cast<unsigned>(mask), acc));
-}
 
 // matches of rows [K0, K1) of v, in source order, to strip_rows[0 .. count); returns count
 template <int K0, int K1, int N>
@@ -165,6 +180,12 @@ __device__ __forceinline__ void flush_strip(const int *strip, unsigned shift, un
 //                      next tile's loads issued right after the count, a barrier that does not drain vmcnt),
 //                      ranks matches with ballots/mbcnt and writes them to the chunk's own slot of a staging
 //                      buffer at chunk-local offsets; one count per chunk.
+//                      The 32 compare masks of a wave tile are taken once (64 SGPRs held across the barrier, no
+//                      spill of them) and serve the count, the row-empty test, the ranks and the store predicates;
+//                      the 16 wave totals are scanned in one DPP row, so the tile total, the wave's offset and the
+//                      wave's destination are scalars and a store is saddr + 32-bit voffset.  At 1 % selectivity
+//                      (92 % of the rows non-empty) the emission, not the stream, used to set the pace:
+//                      DESIGN.md 4.1 has the instruction counts and the times before and after.
 //   scan_move_kernel   one workgroup per chunk: prefix of the chunk counts (<= 4 KiB, read from L2),
 //                      then a coalesced copy staging -> out at the global offset; writes out_size and the
 //                      (always clean) status word.
@@ -203,19 +224,27 @@ __device__ __forceinline__ unsigned chunk_step(i32x4 (&cur)[kScanVpt], i32x4 (&n
                                                size_t tile, bool has_next, unsigned par,
                                                unsigned (*s_wave_total)[kChWaves], unsigned wave,
                                                unsigned lane) {
-  const unsigned wave_total = count_wave_matches(cur, filter);
+  WaveMasks wm;
+  count_wave_matches(cur, filter, wm);
+  const unsigned wave_total = wm.before[kScanVpt];
   if (lane == 0) s_wave_total[par][wave] = wave_total;
   // keep the CU streaming: the next tile's loads go out before anything else happens
   if (has_next) load_wave_tile<kChWaves, kAligned, kNontemporal>(nxt, src, n, tile + 1, wave, lane);
   wg_barrier_lds_only();  // NOT __syncthreads(): its vmcnt(0) would wait for the prefetch
-  unsigned wave_excl = 0, tile_total = 0;
-#pragma unroll
-  for (int w = 0; w < kChWaves; ++w) {
-    const unsigned t = s_wave_total[par][w];
-    wave_excl += w < static_cast<int>(wave) ? t : 0u;
-    tile_total += t;
+  // Inclusive scan of the 16 wave totals inside every 16-lane DPP row (lane l holds wave l & 15); the two numbers a
+  // wave needs come out as scalars, so `running` and the wave's destination stay in SGPRs.
+  static_assert(kChWaves == 16, "one DPP row holds the wave totals");
+  unsigned t = s_wave_total[par][lane & (kChWaves - 1)];
+  t += __builtin_amdgcn_update_dpp(0u, t, 0x111, 0xf, 0xf, false);  // row_shr:1
+  t += __builtin_amdgcn_update_dpp(0u, t, 0x112, 0xf, 0xf, false);  // row_shr:2
+  t += __builtin_amdgcn_update_dpp(0u, t, 0x114, 0xf, 0xf, false);  // row_shr:4
+  t += __builtin_amdgcn_update_dpp(0u, t, 0x118, 0xf, 0xf, false);  // row_shr:8
+  const unsigned tile_total = __builtin_amdgcn_readlane(t, kChWaves - 1);
+  if (wave_total != 0) {
+    const unsigned wave_s = __builtin_amdgcn_readfirstlane(wave);
+    const unsigned wave_excl = __builtin_amdgcn_readlane(t, wave_s) - wave_total;
+    emit_wave_matches(cur, filter, wm, dst_chunk + running + wave_excl);
   }
-  if (wave_total != 0) emit_wave_matches(cur, filter, dst_chunk + running + wave_excl);
   return running + tile_total;
 }
 
