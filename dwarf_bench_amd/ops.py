@@ -11,17 +11,20 @@ encode_columns, and the two compositions over several key columns, groupby_colum
 host/dict_encode.hpp, and for bit-packed columns (PackedColumn, BitPack, pack, unpack, select_range_packed, and SelectRows on
 a PackedColumn) that of host/bitpack.hpp, and for the Bloom filter (BloomFilter, bloom_words, bloom_build, select_in_bloom,
 SelectRows.launch_in and refine_in, semi_join with bloom_bits) that of host/bloom_filter.hpp, and for approximate distinct
-counts (HyperLogLog, approx_count_distinct, hll_relative_error) that of host/hll_sketch.hpp.  Nothing in this module computes on the host or falls back to torch ops: without the built libraries
+counts (HyperLogLog, approx_count_distinct, hll_relative_error) that of host/hll_sketch.hpp, and for exact order statistics
+(Quantiles, quantiles, kth_value, median, equi_depth_bounds) that of host/quantile_select.hpp.  Nothing in this module computes on the host or falls back to torch ops: without the built libraries
 the first call raises.
 """
 from __future__ import annotations
 
 import ctypes as C
 import math
+from fractions import Fraction
 
 import torch
 
-from . import _capi, bitpack_native, bloom_native, dict_native, hll_native, merge_native, select_native, take_native
+from . import (_capi, bitpack_native, bloom_native, dict_native, hll_native, merge_native, quantile_native, select_native,
+               take_native)
 
 DEV_OK, DEV_SPIN_TIMEOUT, DEV_KEY_RANGE, DEV_TABLE_FULL, DEV_RANK_ORDER = 0, 1, 2, 4, 8
 
@@ -662,6 +665,152 @@ def approx_count_distinct(cols, rows: torch.Tensor | None = None, p: int = 12, s
     sketch = HyperLogLog(p, seed, cols[0].device)
     sketch.build(cols, rows=rows)
     return sketch.estimate()
+
+
+# ---------------------------------------------------------------------------------------------
+# quantiles: exact order statistics by a multi-rank radix select (host/quantile_select.hpp, libdbench.so)
+# ---------------------------------------------------------------------------------------------
+QUANTILE_MAX_RANKS = quantile_native.MAX_RANKS
+
+
+def _quantile_ranks(qs) -> tuple[list[int], list[int]]:
+    """the ranks of a call -> (q_num, q_den) as the entry point takes them.  An int is an absolute 0-based rank (q_den = 0);
+    a (num, den) pair, a Fraction or a float in [0, 1] is PERCENTILE_DISC's fraction (a float through
+    Fraction(q).limit_denominator(10**9))"""
+    if isinstance(qs, (int, float, Fraction)) and not isinstance(qs, bool):
+        qs = [qs]  # (a tuple is a sequence of ranks: one pair is [(num, den)])
+    qs = list(qs)
+    if not 1 <= len(qs) <= QUANTILE_MAX_RANKS:
+        raise ValueError(f"qs: expected one to {QUANTILE_MAX_RANKS} ranks, got {len(qs)}")
+    nums, dens = [], []
+    for i, q in enumerate(qs):
+        if isinstance(q, bool):
+            raise ValueError(f"qs[{i}]: expected an int, a (num, den) pair, a Fraction or a float, got {q!r}")
+        if isinstance(q, int):
+            if not 0 <= q < (1 << 32):
+                raise ValueError(f"qs[{i}]: an absolute rank is in [0, 2^32), got {q!r}")
+            nums.append(q)
+            dens.append(0)
+            continue
+        if isinstance(q, float):
+            if not 0.0 <= q <= 1.0:  # (a NaN compares false)
+                raise ValueError(f"qs[{i}]: q outside [0, 1]: {q!r}")
+            q = Fraction(q).limit_denominator(10 ** 9)
+        if isinstance(q, Fraction):
+            q = (q.numerator, q.denominator)
+        if (not isinstance(q, tuple) or len(q) != 2 or any(isinstance(v, bool) or not isinstance(v, int) for v in q)):
+            raise ValueError(f"qs[{i}]: expected an int, a (num, den) pair, a Fraction or a float, got {q!r}")
+        num, den = q
+        if not 0 < den < (1 << 32):
+            raise ValueError(f"qs[{i}]: a denominator is in [1, 2^32), got {den!r}")
+        if not 0 <= num <= den:
+            raise ValueError(f"qs[{i}]: q outside [0, 1]: {num}/{den}")
+        nums.append(num)
+        dens.append(den)
+    return nums, dens
+
+
+class Quantiles:
+    """Reusable plan for the values at up to n_q ranks of an int32 column (compared as uint32, or as int32 with signed),
+    over all rows or the rows of a row-id list: owns the workspace and the three output columns (values, below, equal: one
+    int32 tensor of 3 x n_q words).  launch() reads nothing back and can be captured; result() is the one read-back."""
+
+    def __init__(self, n_q: int, device="cuda"):
+        if isinstance(n_q, bool) or not isinstance(n_q, int) or not 1 <= n_q <= QUANTILE_MAX_RANKS:
+            raise ValueError(f"n_q: expected an int in [1, {QUANTILE_MAX_RANKS}], got {n_q!r}")
+        self.n_q = n_q
+        self.ws_bytes = quantile_native.workspace_bytes(n_q)
+        self.ws = _ws(self.ws_bytes, device)
+        self.out = torch.zeros(3, n_q, dtype=torch.int32, device=device)
+        self._signed = False
+        self._launched = 0  # ranks of the last launch
+
+    def launch(self, col: torch.Tensor, qs, rows: torch.Tensor | None = None, count: torch.Tensor | None = None,
+               signed: bool = False) -> None:
+        """Asynchronous on the current stream; nothing is read back.  qs: up to n_q ranks, each an int (the absolute 0-based
+        rank), a (num, den) pair, a Fraction or a float in [0, 1] (PERCENTILE_DISC: 1/2 is the lower median); they are host
+        values, frozen into a captured graph, and resolved on the device against the number of candidates.  The candidates
+        are rows 0 .. count of col (count None: all rows), or with rows those of rows[i] for i < count; count: a device
+        int64 of one element."""
+        nums, dens = _quantile_ranks(qs)
+        if len(nums) > self.n_q:
+            raise ValueError(f"qs: {len(nums)} ranks, the plan holds {self.n_q}")
+        _need(col, torch.int32, "col")
+        if rows is not None:
+            _need(rows, torch.int32, "rows")
+        _need_count(count, "count")
+        if self.out.device != col.device:
+            raise ValueError(f"col: lives on {col.device}, the plan on {self.out.device}")
+        n_col = col.numel()
+        col_ptr = col.data_ptr() if n_col else None
+        list_ptr, capacity, count_ptr = _column(rows, count)
+        if rows is None:
+            count_ptr = count.data_ptr() if count is not None and n_col else None
+        elif list_ptr is None:  # an empty list has no address: the call over no rows at all
+            col_ptr, n_col = None, 0
+        _capi.check(quantile_native.select(
+            col_ptr, n_col, list_ptr, count_ptr, capacity, nums, dens, quantile_native.SIGNED if signed else 0,
+            self.out[0].data_ptr(), self.out[1].data_ptr(), self.out[2].data_ptr(), self.ws.data_ptr(), self.ws_bytes,
+            _stream()), "quantile_select_u32")
+        self._signed, self._launched = bool(signed), len(nums)
+
+    def status(self) -> int:
+        return workspace_status(self.ws)
+
+    def result(self):
+        """(values, below, equal) of the last launch's ranks as int64 tensors on the host (one copy of 12 bytes per rank;
+        synchronises), and raises on a flagged status word (a row id outside the column).  values: the keys in the order's
+        own numbers (int32 with signed, uint32 otherwise); below: the candidates strictly before the value, equal: those
+        equal to it.  A rank that names no row (no candidates, or an absolute rank beyond them) has value 0, below = the
+        number of candidates and equal = 0."""
+        if not self._launched:
+            raise ValueError("result: nothing was launched on this plan")
+        host = self.out[:, : self._launched].cpu()
+        _check_status(self.ws, "quantile_select_u32")
+        values, below, equal = (host[i].to(torch.int64) for i in range(3))
+        if not self._signed:
+            values = values & 0xFFFFFFFF
+        return values, below & 0xFFFFFFFF, equal & 0xFFFFFFFF
+
+
+def quantiles(col: torch.Tensor, qs, rows: torch.Tensor | None = None, signed: bool = False):
+    """(values, below, equal), int64 on the host, at the ranks qs of an int32 column — compared as uint32, or as int32 with
+    signed — over all rows or those of a row-id list (a row id as often as the list holds it; one >= col.numel() raises).
+    Exact: PERCENTILE_DISC for a fraction, the k-th smallest for an int."""
+    nums, _ = _quantile_ranks(qs)
+    _need(col, torch.int32, "col")
+    plan = Quantiles(len(nums), col.device)
+    plan.launch(col, qs, rows=rows, signed=signed)
+    return plan.result()
+
+
+def kth_value(col: torch.Tensor, k: int, rows: torch.Tensor | None = None, signed: bool = False) -> int:
+    """the k-th smallest value (k = 0: the minimum) among the candidates; IndexError when there are k or fewer"""
+    if isinstance(k, bool) or not isinstance(k, int):
+        raise ValueError(f"k: expected an int, got {k!r}")
+    values, _, equal = quantiles(col, [k], rows=rows, signed=signed)
+    if int(equal[0]) == 0:
+        raise IndexError(f"kth_value: no row of rank {k}")
+    return int(values[0])
+
+
+def median(col: torch.Tensor, rows: torch.Tensor | None = None, signed: bool = False) -> int:
+    """the lower median (PERCENTILE_DISC(0.5)) of the candidates; IndexError when there are none"""
+    values, _, equal = quantiles(col, [(1, 2)], rows=rows, signed=signed)
+    if int(equal[0]) == 0:
+        raise IndexError("median: no rows")
+    return int(values[0])
+
+
+def equi_depth_bounds(col: torch.Tensor, parts: int, rows: torch.Tensor | None = None, signed: bool = False) -> torch.Tensor:
+    """the parts - 1 values at i / parts, i = 1 .. parts - 1: the upper bounds of equi-depth buckets (deciles for
+    parts = 10; the splitters of a range partition).  parts in 2 .. 17; int64 on the host; IndexError without rows"""
+    if isinstance(parts, bool) or not isinstance(parts, int) or not 2 <= parts <= QUANTILE_MAX_RANKS + 1:
+        raise ValueError(f"parts: expected an int in [2, {QUANTILE_MAX_RANKS + 1}], got {parts!r}")
+    values, _, equal = quantiles(col, [(i, parts) for i in range(1, parts)], rows=rows, signed=signed)
+    if int(equal[0]) == 0:
+        raise IndexError("equi_depth_bounds: no rows")
+    return values
 
 
 # ---------------------------------------------------------------------------------------------

@@ -144,6 +144,15 @@ the contract numbers come from bench.py.
                   (its cardinality; capacity = the true count), torch.unique(col).numel(), and select_range on the same
                   column as the stream yardstick.  The floor, HELD or MISSED: the sketch's slowest repetition against the
                   faster exact route's fastest.  The estimate's relative error is printed for every shape
+  quantile        exact order statistics (ops.Quantiles: host/quantile_select.hpp), same protocol as hll (legs alternating, REPS
+                  repetitions of a median of 5, HIP events, every leg's values checked against the select's).  2^20, 2^24 and
+                  2^26 rows (QUANTILE_LGS); uniform full-range keys, keys in [1, 10000], all keys equal, sorted keys, and
+                  lists of 1 % and 50 % of the rows of the uniform column (QUANTILE_SHAPES); one rank (the median) and nine
+                  (the deciles), int32 order.  Legs: the select, the routes the library had before it — copy +
+                  RadixSort + index, torch.kthvalue per rank, and for one rank TopK(k = r + 1, sorted=False) with the max of
+                  its keys — behind TakeRows where there is a list, and for one rank the same rank sixteen times (the
+                  sixteen-slot kernel with one live slot).  The floor, HELD or MISSED: the select's slowest repetition
+                  against the fastest other route's fastest
   launch-join [lg] / launch-sort [lg] / launch-all
                   a few untimed calls and nothing else: the program to put behind `rocprofv3 --kernel-trace --stats` or
                   `--pmc` (tools/pmc_kernel_counters.sh); tools/prof_show.py prints the tables
@@ -1390,6 +1399,95 @@ def hll(_):
             del col, second, rows, cols, sel, legs_exact
 
 
+def quantile(_):
+    """QUANTILE_LGS=20,24,26 picks the sizes, QUANTILE_SHAPES a subset of the shape names, separated by ;"""
+    reps = int(os.environ.get("REPS", "3"))
+    lgs = [int(x) for x in os.environ.get("QUANTILE_LGS", "20,24,26").split(",")]
+    names = ("uniform", "[1, 10000]", "all equal", "sorted", "list 1 %", "list 50 %")
+    shapes = [s for s in os.environ.get("QUANTILE_SHAPES", ";".join(names)).split(";") if s in names]
+    rank_sets = {"median": [(1, 2)], "deciles": [(i, 10) for i in range(1, 10)]}
+
+    for lg in lgs:
+        n = 1 << lg
+        g = torch.Generator(device="cuda")
+        g.manual_seed(lg)
+        for shape in shapes:
+            rows = None
+            if shape in ("uniform", "list 1 %", "list 50 %"):
+                col = ops.gen_uniform_u32(n, 5, 0, 2**32 - 1)
+            elif shape == "[1, 10000]":
+                col = ops.gen_uniform_u32(n, 5, 1, 10000)
+            elif shape == "all equal":
+                col = torch.full((n,), 12345, dtype=torch.int32, device="cuda")
+            else:
+                col = torch.sort(ops.gen_uniform_u32(n, 5, 0, 2**32 - 1))[0]
+            if shape.startswith("list"):
+                m = n // 100 if shape == "list 1 %" else n // 2
+                rows = torch.randint(0, n, (m,), device="cuda", generator=g).to(torch.int32)  # unsorted, rows repeat
+            m = n if rows is None else rows.numel()
+            taker = ops.TakeRows(m) if rows is not None else None
+            candidates = (lambda: col) if rows is None else (lambda: taker.launch([col], rows) or taker.output()[0][0][:m])
+            tmp = torch.empty(m, dtype=torch.int32, device="cuda")
+            sorter = ops.RadixSort(m)
+            for set_name, qs in rank_sets.items():
+                ranks = [-(-num * m // den) - 1 for num, den in qs]  # ceil(num m / den) - 1
+                at = torch.tensor(ranks, dtype=torch.int64, device="cuda")
+                plan, wide = ops.Quantiles(len(qs)), ops.Quantiles(16)
+                answers = {}
+
+                def mine():
+                    plan.launch(col, qs, rows=rows, signed=True)
+
+                def sixteen():  # one rank sixteen times: the sixteen-slot kernel with one live slot
+                    wide.launch(col, qs * 16, rows=rows, signed=True)
+
+                def by_sort():
+                    tmp.copy_(candidates())
+                    sorter.launch(tmp, True)
+                    answers["sort"] = tmp[at]
+
+                def by_kthvalue():
+                    c = candidates()
+                    answers["kthvalue"] = torch.stack([torch.kthvalue(c, r + 1)[0] for r in ranks])
+
+                legs_fn = {"quantile": mine, "sort": by_sort, "kthvalue": by_kthvalue}
+                if len(qs) == 1:
+                    legs_fn["sixteen-slot"] = sixteen
+                    top = ops.TopK(m, ranks[0] + 1)
+
+                    def by_topk():  # unsorted: the k-th key is the largest of the k it returns
+                        answers["topk"] = top.launch(candidates(), signed=True, sorted=False)[0].max().reshape(1)
+
+                    legs_fn["topk"] = by_topk
+                mine()
+                for leg in [x for x in legs_fn if x != "quantile"]:
+                    try:
+                        legs_fn[leg]()
+                    except RuntimeError as e:  # a route this build of torch does not offer for the shape
+                        print(f"{TAG:10s} quantile n=2^{lg} {shape} {set_name}: leg {leg} left out: {str(e).splitlines()[0]}", flush=True)
+                        del legs_fn[leg]
+                        answers.pop(leg, None)
+                got = plan.result()[0].cuda()
+                ok = all(torch.equal(got, a.to(torch.int64)) for a in answers.values())
+                if len(qs) == 1:
+                    ok = ok and torch.equal(wide.result()[0].cuda(), got.repeat(16))
+                legs = {leg: [] for leg in legs_fn}
+                slow = {leg for leg, fn in legs_fn.items() if times(fn, 1, warm=0)[0] > 20000.0}  # (torch.kthvalue on 2^24 rows up)
+                for _ in range(reps):  # alternating; a leg of more than 20 ms a call is timed once per repetition
+                    for leg, fn in legs_fn.items():
+                        legs[leg].append(times(fn, 1, warm=0)[0] if leg in slow else median(times(fn, 5)))
+                others =[x for x in legs if x not in ("quantile", "sixteen-slot")]
+                best = min(others, key=lambda x: min(legs[x]))
+                verdict = "HELD" if max(legs["quantile"]) <= min(legs[best]) else "MISSED"
+                s = median(sorted(legs["quantile"]))
+                extra = f"  floor {verdict} against {best} x{min(legs[best]) / s:7.2f}  three reads at 8 TB/s {3 * 4 * m / 8e6:7.1f} us"
+                if "sixteen-slot" in legs:
+                    extra += f"  sixteen-slot / quantile x{median(sorted(legs['sixteen-slot'])) / s:5.2f}"
+                _merge_row(f"quantile n=2^{lg} {shape} {set_name}", legs, ok, None, None, extra)
+                del plan, wide
+            del col, rows, tmp, sorter, taker
+
+
 def launch_sort_pairs(lg):
     n = 1 << (lg or 24)
     keys0 = ops.gen_uniform_u32(n, 42, 0, 2**32 - 1)
@@ -2093,7 +2191,8 @@ MODES = {"radix": radix, "ramp": ramp, "radix-idle": radix_idle, "radix-stream":
          "join-pairs": join_pairs, "launch-join-pairs": launch_join_pairs, "topk": topk, "launch-topk": launch_topk,
          "groupby-sorted": groupby_sorted, "launch-groupby-sorted": launch_groupby_sorted,
          "window": window, "launch-window": launch_window, "sorted-search": sorted_search, "range-join": range_join,
-         "selection": selection, "merge": merge, "take": take, "dict": dict_encoding, "bitpack": bitpack, "bloom": bloom, "hll": hll}
+         "selection": selection, "merge": merge, "take": take, "dict": dict_encoding, "bitpack": bitpack, "bloom": bloom, "hll": hll,
+         "quantile": quantile}
 
 if __name__ == "__main__":
     if len(sys.argv) < 2 or sys.argv[1] not in MODES:
